@@ -16,6 +16,11 @@ separately (``neighbor_build_s``).
     torchrun --nproc-per-node N bench.py --gpus N ...
     python bench.py --config {2,4,5}              # the other BASELINE presets (5: the Gibbs sampler;
                                                    # --chains-per-gpu C, --single-chain)
+
+A plain run sets up, warms up, times the steps and prints the result line.  ``--full`` adds what
+takes runs of its own: the CPU baselines (``cpu_baseline``, ``neighbor_build_cpu``; budget
+``--cpu-seconds``) and, for config 5, the separately timed B/F sweep and w sweep (``breakdown``,
+``roofline``).  ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``.
 """
 import argparse
 import json
@@ -54,6 +59,30 @@ def synth(n_total, seed=0):
     coords = rng.uniform(0.0, 1.0, (n_total, 2))
     values = rng.standard_normal(n_total)
     return coords, values
+
+
+DUMP_BUDGET = 48 << 20  # bytes over all files of one --dump-outputs run
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: write every array of ``arrays`` (name -> torch tensor, numpy array or number)
+    as ``dirname/<name><suffix>.npy`` in float64.  If together they exceed DUMP_BUDGET, an array
+    over 1 MB that does not fit its equal share of the budget keeps a fixed sample of its rows
+    (numpy default_rng(0), without replacement, ascending); the sampled row numbers go to
+    ``<name>_rows<suffix>.npy``.  Rows are gathered on the device, so only the sample crosses to the host."""
+    os.makedirs(dirname, exist_ok=True)
+    ts = {k: (v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64)))
+          for k, v in arrays.items()}
+    nbytes = {k: 8 * t.numel() for k, t in ts.items()}
+    big = [k for k in ts if nbytes[k] > 1 << 20] if sum(nbytes.values()) > DUMP_BUDGET else []
+    share = (DUMP_BUDGET - sum(b for k, b in nbytes.items() if k not in big)) // max(1, len(big))
+    for k, t in ts.items():
+        if k in big and nbytes[k] + 8 * t.shape[0] > share:
+            keep = share // (nbytes[k] // t.shape[0] + 8)
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            np.save(os.path.join(dirname, f"{k}_rows{suffix}.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), t.to(torch.float64).cpu().numpy())
 
 
 def knn_cpu_baseline(coords, m, n_full, n_sample=10_000):
@@ -326,40 +355,49 @@ def run_gibbs(args, dev, rank, world, distributed, json_fd):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the fused B/F sweep of one phi proposal, timed on its own (HIP events on the launch stream),
-    # and the colour-ordered w sweep: their shares of an iteration
-    stream = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 50
-    e0.record(stream)
-    for _ in range(reps):
-        if single:  # own rows + halo rows, partials folded over the ranks
-            g._propose(g.phi)
-        else:
-            g._sweep_into(g.phi, g._B2, g._Ft2, g._r2)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    sweep_ms = e0.elapsed_time(e1) / reps
-    w_save, r_save = g.w.clone(), g.r.clone()
-    e0.record(stream)
-    for _ in range(reps):
-        if tiled:
-            g._sweep_tiles()
-        else:
-            g.update_wt()
-            g.update_ws()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    wsweep_ms = e0.elapsed_time(e1) / reps
-    g.w.copy_(w_save)
-    g.r.copy_(r_save)
+    if args.dump_outputs:
+        # every chain's state after its last timed iteration
+        state = {}
+        for k, ch in enumerate(chains):
+            tag = f"_chain{k}" if len(chains) > 1 else ""
+            state["w" + tag] = ch.w
+            state["beta" + tag] = ch.beta
+            state["theta" + tag] = [ch.sigma2, ch.phi, ch.tau2]
+        dump_outputs(args.dump_outputs, state, f"_rank{rank}" if world > 1 else "")
     ms_iter = 1e3 * elapsed / args.steps
+    if args.full:
+        # the fused B/F sweep of one phi proposal, timed on its own (HIP events on the launch stream),
+        # and the colour-ordered w sweep: their shares of an iteration
+        stream = torch.cuda.current_stream(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 50
+        e0.record(stream)
+        for _ in range(reps):
+            if single:  # own rows + halo rows, partials folded over the ranks
+                g._propose(g.phi)
+            else:
+                g._sweep_into(g.phi, g._B2, g._Ft2, g._r2)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        sweep_ms = e0.elapsed_time(e1) / reps
+        w_save, r_save = g.w.clone(), g.r.clone()
+        e0.record(stream)
+        for _ in range(reps):
+            if tiled:
+                g._sweep_tiles()
+            else:
+                g.update_wt()
+                g.update_ws()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        wsweep_ms = e0.elapsed_time(e1) / reps
+        g.w.copy_(w_save)
+        g.r.copy_(r_save)
     if rank == 0:
         sweep_prof = gibbs_profile(args, "sweep") if not single else None
         colour_prof = gibbs_profile(args, "colour") if not single else None
         bpl = bytes_per_location(m) + 8  # + the residual r written for the sampler
         rows = g.hi - g.lo if single else n
-        achieved = bpl * rows / (sweep_ms * 1e-3)
         n_chains = 1 if single else world * cpg
         out = {
             "metric": "NNGP Gibbs sampler iterations/sec (BASELINE config 5: N=1M, m=15, 1,000 sweeps; " + (
@@ -393,26 +431,31 @@ def run_gibbs(args, dev, rank, world, distributed, json_fd):
                 "w_sweep": "tiled" if tiled else "colour",
             },
             "breakdown": {
-                "bf_sweep_ms": sweep_ms, "bf_sweep_share": sweep_ms / ms_iter,
-                "w_sweep_ms": wsweep_ms, "w_sweep_share": wsweep_ms / ms_iter, "n_colors": int(g.n_colors),
+                "n_colors": int(g.n_colors),
                 "w_sweep": ("tiled: one launch per phase of spatial tiles, r in LDS (%d tiles, %d launches)"
                             % (g._tiles.tinfo.shape[0], len(g._tiles.phases))) if tiled else "one launch per colour",
                 "phi_accept_rate": g.n_accept / max(1, g.iteration), "setup_s": setup_s,
             },
-            "roofline": {
+            "roofline": None,  # --full: the phi proposal's sweep timed on its own
+            "roofline_valu": None,
+            "roofline_colour": colour_roofline(colour_prof),
+            "state": {"phi": g.phi, "sigma2": g.sigma2, "tau2": g.tau2, "beta": list(map(float, g.beta))},
+            "lib": os.path.relpath(_lib.LIB_PATH, ROOT),
+        }
+        if args.full:
+            achieved = bpl * rows / (sweep_ms * 1e-3)
+            out["breakdown"].update({"bf_sweep_ms": sweep_ms, "bf_sweep_share": sweep_ms / ms_iter,
+                                     "w_sweep_ms": wsweep_ms, "w_sweep_share": wsweep_ms / ms_iter})
+            out["roofline"] = {
                 "bound": "hbm", "kernel": "fused B/F + residual sweep of a phi proposal",
                 "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK,
                 "traffic": sweep_prof.get("bytes_per_launch") if sweep_prof else None,
                 "traffic_source": (f'{sweep_prof["source"]} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, '
                                    f'{sweep_prof["kernel"]})') if sweep_prof else None,
                 "algorithmic_bytes_per_location": bpl, "kernel_ms": sweep_ms, "kernel_rows": rows,
-            },
-            "roofline_valu": valu_roofline(sweep_prof, rows, sweep_ms) if sweep_prof else None,
-            "roofline_colour": colour_roofline(colour_prof),
-            "state": {"phi": g.phi, "sigma2": g.sigma2, "tau2": g.tau2, "beta": list(map(float, g.beta))},
-            "lib": os.path.relpath(_lib.LIB_PATH, ROOT),
-        }
-        if world == 1 and args.cpu_seconds > 0:
+            }
+            out["roofline_valu"] = valu_roofline(sweep_prof, rows, sweep_ms) if sweep_prof else None
+        if args.full and world == 1 and args.cpu_seconds > 0:
             F_gpu = g.Ft.cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(g.coords.cpu().numpy(), g.w.cpu().numpy(), g.nbr.cpu().numpy(),
                                                "exponential", (1.0, g.phi, 0.0), args.cpu_seconds, F_gpu)
@@ -451,7 +494,14 @@ def main():
     ap.add_argument("--no-order", action="store_true", help="visit rows in index order (no Z-order; natural layout)")
     ap.add_argument("--layout", default="storage", choices=["storage", "natural"],
                     help="storage: per-location arrays relabelled into Z-order storage (default); natural: input rows")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget in seconds of CPU work (a bounded sample; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (cpu_baseline, "
+                         "neighbor_build_cpu) and, for config 5, the B/F sweep and the w sweep timed on their own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (B, F, partials, loglik; config 5: "
+                         "every chain's w, beta, theta) as DIR/<name>.npy in float64, sampled rows beyond 48 MB")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: CPU baseline budget in seconds of CPU work (a bounded sample; 0 = skip)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="testing only: every rank on cuda:0 with gloo collectives (the N-rank flow on one GPU)")
     ap.add_argument("--sweep-api", default="ops", choices=["ops", "ctypes"],
@@ -591,6 +641,12 @@ def main():
     assert all(np.array_equal(q, p, equal_nan=True) for q in per_sweep.cpu().numpy()), \
         "sweeps of the same field must give identical partials"
     ll = -0.5 * (n_total * np.log(2 * np.pi) + p[0] + p[1])
+    if args.dump_outputs:
+        # the last timed sweep's global partials and this rank's B / F rows (left in the engine's buffers)
+        last = {"partials": per_sweep[-1], "loglik": ll}
+        if want_bf:
+            last.update(B=sweep.B, F=sweep.F)
+        dump_outputs(args.dump_outputs, last, f"_rank{rank}" if world > 1 else "")
 
     if rank == 0:
         bpl = bytes_per_location(args.m) if want_bf else bytes_per_location(args.m) - 8 * args.m - 8
@@ -674,7 +730,7 @@ def main():
                           if distributed else "none (one rank)",
             "lib": os.path.relpath(_lib.LIB_PATH, ROOT),
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             F_gpu = sweep.F.cpu().numpy() if want_bf else None
             c_sw = sweep._coords_sweep  # storage- or input-order coordinates the rows / nbr refer to
             if F_gpu is None:

@@ -15,7 +15,7 @@ for p in $presets; do
     3) args="--steps 30 --warmup 30 --cpu-seconds 0" ;;
     2) args="--config 2 --steps 50 --warmup 50 --cpu-seconds 0" ;;
     4) args="--config 4 --steps 10 --warmup 5 --cpu-seconds 0" ;;
-    5) args="--config 5 --steps 20 --warmup 5 --cpu-seconds 0" ;;
+    5) args="--full --config 5 --steps 20 --warmup 5 --cpu-seconds 0" ;;
     *) echo "unknown preset $p"; exit 2 ;;
   esac
   out=gpurun_out/prov_$tag/c$p

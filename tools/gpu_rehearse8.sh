@@ -19,10 +19,10 @@ fi
 if [[ " $parts " == *" 5 "* ]]; then
 echo "[rehearse8] config 5 single chain, 8 ranks $(date +%T)"
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-  --master-port 29582 bench.py --gpus 8 --config 5 --single-chain --rehearse-on-one-gpu --steps 25 \
+  --master-port 29582 bench.py --full --gpus 8 --config 5 --single-chain --rehearse-on-one-gpu --steps 25 \
   --warmup 0 --cpu-seconds 0 > $out/config5_single_w8.json 2> $out/config5_single_w8.err || exit 1
 echo "[rehearse8] config 5 SeqNNGP at N = 8e6 $(date +%T)"
-timeout -k 10 600 python bench.py --config 5 --n 8000000 --steps 25 --warmup 0 --cpu-seconds 0 \
+timeout -k 10 600 python bench.py --full --config 5 --n 8000000 --steps 25 --warmup 0 --cpu-seconds 0 \
   > $out/config5_seq_n8e6.json 2> $out/config5_seq_n8e6.err || exit 1
 fi
 echo "[rehearse8] done $(date +%T)"

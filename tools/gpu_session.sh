@@ -4,7 +4,7 @@
 #   tests            python -m pytest tests -m gpu (log: gpurun_out/<tag>/pytest.log)
 #   tests:<expr>     the same restricted with -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench[:args]     python bench.py <args>  (one JSON line -> bench_<n>.json)
+#   bench[:args]     python bench.py --full <args>  (one JSON line with the CPU baselines -> bench_<n>.json)
 #   ubench           tools/ubench/f64_latency (prebuilt in-tree)
 #   valumix          tools/ubench/valu_mix (prebuilt): VALU cycles per SIMD by class and waves per SIMD
 #   valuclass[:args] / valubusy[:args]   VALU class-count and VALU-busy counter passes over bench.py
@@ -39,7 +39,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke()' > $out/smoke_$n.log 2>&1 || { cat $out/smoke_$n.log; exit 1; }
       tail -1 $out/smoke_$n.log ;;
     bench)
-      timeout -k 10 300 python -u bench.py $arg > $out/bench_$n.json 2> $out/bench_$n.err || { tail -20 $out/bench_$n.err; exit 1; }
+      timeout -k 10 300 python -u bench.py --full $arg > $out/bench_$n.json 2> $out/bench_$n.err || { tail -20 $out/bench_$n.err; exit 1; }
       python -c "import json,sys; d=json.load(open('$out/bench_$n.json')); print('value %.4g' % d['value'], 'ms/step %.4f' % d['ms_per_step'], 'kernel_ms %.4f' % d['roofline']['kernel_ms'], 'frac %.3f' % d['roofline']['frac'])" ;;
     ubench)
       timeout -k 10 120 tools/ubench/f64_latency > $out/f64_latency.txt 2>&1 || exit 1
