@@ -208,6 +208,45 @@ int nngp_bf_sweep_plan(const double *coords, int64_t n_points, int32_t dim, cons
                        void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Neighbour-set certificates: the same sweep without the per-sweep index checks and distance clamps.
+ * In real use (a theta scan, an MCMC chain) coords, nbr and order are fixed for the life of the model;
+ * nngp_bf_sweep still range-checks every neighbour index and clamps every squared distance on every
+ * launch.  A certificate -- built once per (coords, nbr, order, i0), like the neighbour sets -- records
+ * per tile of the pair kernel whether any slot of its rows is < 0 or >= n_points (CHECKED: -1 padding and
+ * bad indices alike; such tiles run exactly as in nngp_bf_sweep), and the squared diagonal of the
+ * coordinates' bounding box, d2_span.  No reference counterpart (same methods as nngp_bf_sweep,
+ * _CNs / _Ccross / _Cs / _Bsi / _Fsi, nngp.py:73-96); B, F, R, the tile records and the partials of
+ * nngp_bf_sweep_cert are bit-identical to nngp_bf_sweep's on the same arguments: the trusted tiles leave
+ * out only operations that are the identity on them.
+ * nngp_nbr_cert_bytes: the certificate buffer's size for n_rows rows (0: n_rows < 0).
+ * nngp_nbr_cert_build: builds it on `stream`, then SYNCHRONISES the stream (a setup call, as
+ *   nngp_pair_plan_build) to fill the host array info[NNGP_CERT_INFO_LEN]: a tag, the coords / nbr / order
+ *   pointers, n_points, dim, n_rows, m, i0, the tile count, the number of checked tiles, and d2_span (a
+ *   double's bits).  NNGP_EINVAL for a non-finite coordinate.  1 <= m <= NNGP_MAX_M, cert 256-B aligned.
+ * nngp_nbr_cert_trusted_tiles: a pure HOST function: the number of tiles a sweep of (kind, theta) runs
+ *   trusted -- 0 when the clamp may bind (d2_span (1 + 2^-40) is not below the kind's clamp distance), when
+ *   the kind is not one of 0..4, or m > 24.  The one place the theta-dependent decision is made;
+ *   nngp_bf_sweep_cert calls it too.
+ * nngp_bf_sweep_cert: nngp_bf_sweep's arguments plus the certificate and its info.  coords, nbr, order,
+ *   n_points, dim, n_rows, m and i0 must be those in info (checked before any launch: NNGP_EINVAL, a caller
+ *   bug).  When the resolved kernel is not the pair kernel or nngp_nbr_cert_trusted_tiles gives 0 it is
+ *   exactly nngp_bf_sweep: the certificate is a hint.
+ * CONTRACT: the caller does not modify the contents of nbr, order or coords after certifying them (the
+ * trusted tiles read coords[nbr[..]] unchecked); rebuild the certificate after any change.
+ * ------------------------------------------------------------------------- */
+#define NNGP_CERT_INFO_LEN 16
+size_t nngp_nbr_cert_bytes(int64_t n_rows);
+int nngp_nbr_cert_build(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                        int64_t n_rows, int32_t m, int64_t i0, void *cert, size_t cert_bytes, int64_t *info,
+                        void *stream);
+int64_t nngp_nbr_cert_trusted_tiles(const int64_t *info, int32_t kind, double sigma2, double phi, double tau2);
+int nngp_bf_sweep_cert(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                       double nu, const double *values, double *B, double *F, double *R, double *partials,
+                       void *workspace, size_t workspace_bytes, int32_t algo, const void *cert, size_t cert_bytes,
+                       const int64_t *info, void *stream);
+
+/* ---------------------------------------------------------------------------
  * B/F of query locations t against a reference set S (prediction / kriging at
  * t not in S).  SURVEY.md 8(f) row 2: the reference builds Nt for refType != 'S=T'
  * (NNGP._make_t_neighbor_sets, pyNNGP/nngp.py:64-71, KDTree(s).query(t, m)) but

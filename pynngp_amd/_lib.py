@@ -63,6 +63,10 @@ SYMBOLS = (
     "nngp_pair_plan_bytes",
     "nngp_pair_plan_build",
     "nngp_bf_sweep_plan",
+    "nngp_nbr_cert_bytes",
+    "nngp_nbr_cert_build",
+    "nngp_nbr_cert_trusted_tiles",
+    "nngp_bf_sweep_cert",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -72,6 +76,7 @@ MAX_M = 63
 MAX_DIM = 3
 ABI_VERSION = 4  # NNGP_ABI_VERSION of include/nngp.h this binding's signatures follow
 PLAN_INFO_LEN = 10  # NNGP_PLAN_INFO_LEN
+CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
 BLOCKS_MAX_M = 32  # nngp_bf_sweep_blocks: 1 <= m <= 32
 
 
@@ -186,6 +191,15 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_sweep_plan.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P, SZ, P,
                                        P]
     lib.nngp_bf_sweep_plan.restype = ctypes.c_int
+    lib.nngp_nbr_cert_bytes.argtypes = [I64]
+    lib.nngp_nbr_cert_bytes.restype = SZ
+    lib.nngp_nbr_cert_build.argtypes = [P, I64, I32, P, P, I64, I32, I64, P, SZ, P, P]
+    lib.nngp_nbr_cert_build.restype = ctypes.c_int
+    lib.nngp_nbr_cert_trusted_tiles.argtypes = [P, I32, D, D, D]
+    lib.nngp_nbr_cert_trusted_tiles.restype = I64
+    lib.nngp_bf_sweep_cert.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, SZ, I32, P,
+                                       SZ, P, P]
+    lib.nngp_bf_sweep_cert.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -423,9 +437,12 @@ def bf_sweep(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2
              partials: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
              order: Optional[torch.Tensor] = None,
              R: Optional[torch.Tensor] = None,
-             defer: bool = False, nu: Optional[float] = None, plan: Optional[PairPlan] = None
-             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor]:
+             defer: bool = False, nu: Optional[float] = None, plan: Optional[PairPlan] = None,
+             cert=None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor]:
     """Fused B/F + log-likelihood sweep over rows ``i0 .. i0 + len(nbr)``.
+
+    ``cert``: ``(buffer, info)`` of :func:`nbr_cert` for exactly these coords / nbr / order tensors and i0
+    (nngp_bf_sweep_cert: the same bits; tiles without padding or bad indices skip the index checks and clamps).
 
     ``plan``: a :func:`pair_plan` of this nbr / order / i0 (the pair kernel with every shared
     covariance evaluated once per tile; kinds exponential .. spherical, algo ``auto`` / ``pairb``).
@@ -492,11 +509,40 @@ def bf_sweep(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2
                                       _ptr(plan.buf), plan.buf.numel(), plan.info, _stream(dev)),
                "nngp_bf_sweep_plan")
         return B, F, partials
+    if cert is not None:
+        cbuf, cinfo = cert
+        if cbuf.device != dev:
+            raise ValueError("cert must be on the sweep's device")
+        _check(lib.nngp_bf_sweep_cert(_ptr(coords), coords.shape[0], d, _ptr(nbr), _ptr(order), rows, m, i0,
+                                      KIND_CODES[kind], float(sigma2), float(phi), float(tau2), nu, _ptr(values),
+                                      _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), a,
+                                      _ptr(cbuf), cbuf.numel(), cinfo, _stream(dev)),
+               "nngp_bf_sweep_cert")
+        return B, F, partials
     _check(lib.nngp_bf_sweep(_ptr(coords), coords.shape[0], d, _ptr(nbr), _ptr(order), rows, m, i0, KIND_CODES[kind],
                              float(sigma2), float(phi), float(tau2), nu, _ptr(values), _ptr(B), _ptr(F), _ptr(R),
                              _ptr(partials), _ptr(workspace), workspace.numel(), a, _stream(dev)),
            "nngp_bf_sweep")
     return B, F, partials
+
+
+def nbr_cert(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, order: Optional[torch.Tensor] = None):
+    """A neighbour-set certificate (``nngp_nbr_cert_build``, include/nngp.h) for sweeps over exactly these
+    (contiguous) tensors: ``(buffer, info)`` for :func:`bf_sweep`'s ``cert``.  A setup call (one host
+    synchronisation).  The tensors must not be modified afterwards."""
+    if not (coords.is_contiguous() and nbr.is_contiguous() and coords.dtype == torch.float64 and coords.dim() == 2
+            and nbr.dtype == torch.int32 and nbr.dim() == 2):
+        raise ValueError("nbr_cert needs contiguous float64 (N, dim) coords and int32 (rows, m) nbr")
+    dev = _require_gpu(coords, nbr, order)
+    rows, m = nbr.shape
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,) or not order.is_contiguous()):
+        raise ValueError("order must be a contiguous int32 (rows,) tensor")
+    lib = load()
+    buf = _workspace(lib.nngp_nbr_cert_bytes(rows), dev)
+    info = (ctypes.c_int64 * CERT_INFO_LEN)()
+    _check(lib.nngp_nbr_cert_build(_ptr(coords), coords.shape[0], coords.shape[1], _ptr(nbr), _ptr(order), rows, m,
+                                   int(i0), _ptr(buf), buf.numel(), info, _stream(dev)), "nngp_nbr_cert_build")
+    return buf, info
 
 
 def bf_finalize(workspace: torch.Tensor, rows: int, m: int, kind: str, dim: int, algo: str = "auto",

@@ -45,6 +45,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "bf_group.h"
 #include "nngp_internal.h"
 #include "nngp_math.h"
@@ -100,6 +102,13 @@ constexpr bool pairb_left(int m) { return m >= kPairbLeftMin && m <= 32; }
 constexpr bool pairb_lk(int m, int kind) {
     return pairb_left(m) && (kind != NNGP_KIND_MATERN || m == kPairbLeftMaternM) &&
            (kind != NNGP_KIND_BLOCKS || m <= 24);
+}
+// kernels that carry a trusted instance of their body for certified neighbour sets (bf_pairb's ckmask): the
+// fused kinds 0..4 with a compile-time dimension up to m = kPairbCertMaxM; the Matern-table, covariance-blocks,
+// planned and runtime-kind kernels ignore the mask
+constexpr int kPairbCertMaxM = 24;
+constexpr bool pairb_cert_trustable(int m, int kind, int d, bool planned) {
+    return !planned && kind >= 0 && kind <= 4 && d >= 1 && d <= 3 && m >= 1 && m <= kPairbCertMaxM;
 }
 // static per-phase budgets (tools/isa_phases.py): tools/variants/phases.h defines NNGP_PHASE to fence the
 // phases with named markers (hipcc -include tools/variants/phases.h); a product build leaves them empty
@@ -341,9 +350,15 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                                                 double* __restrict__ Fout, double* __restrict__ Rout,
                                                 double4* __restrict__ rec, int32_t* __restrict__ lexp, int dim,
                                                 const double* __restrict__ cblk, int64_t tq, int64_t trem,
-                                                int64_t* __restrict__ hdr, const PairPlanArgs pp) {
+                                                int64_t* __restrict__ hdr, const PairPlanArgs pp,
+                                                const uint32_t* __restrict__ ckmask) {
     static_assert(M >= 1 && M <= 32, "pairb instantiated for 1 <= m <= 32");
     static_assert(D >= 0 && D <= 3, "0 (runtime dimension) <= D <= 3");
+    // ckmask: the neighbour-set certificate's checked-tile bits (nngp_nbr_cert_build, pairb_cert_trustable), or
+    // null: every tile checked.  A tile whose bit is 0 runs the TRUSTED instance of the body below: every
+    // neighbour index of its rows is in [0, n_points) and no squared distance reaches the clamp, so the range
+    // checks, the far-point / zero-value selects and the clamp -- the identity on such a tile -- are left out.
+    constexpr bool TRUSTABLE = pairb_cert_trustable(M, KIND, D, PL);
     constexpr bool CM = KIND == NNGP_KIND_BLOCKS;
     constexpr bool MT = KIND == NNGP_KIND_MATERN;  // cblk: the launch's Matern table (matern_table.hip)
     constexpr int DA = point_arity<D>();  // coordinates held per point
@@ -400,11 +415,21 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
     const double wq1 = q1 ? 1.0 : 0.0, wq0 = 1.0 - wq1;
     uint32_t mask1 = q1 ? 0xffffffffu : 0u;
     asm volatile("" : "+v"(mask1));  // opaque to the optimizer (see pr_pick)
-    {
+    // the body, instantiated checked (TRUST = false: the kernel as it always was) and, for the kernels
+    // pairb_cert_trustable names, trusted; the block takes one of them by a scalar branch on its tile's bit
+    auto body = [&](auto trust_tag) __attribute__((always_inline)) {
+        constexpr bool TRUST = decltype(trust_tag)::value;
+        // for even M the last pair's second row (M + 1) is far-away padding in every tile: covariances with that
+        // row pair keep the clamp, which is what makes them exact zeros (s, t: row pairs of the operands)
+        auto cov = [&](double d2, int s, int t) __attribute__((always_inline)) -> double {
+            const bool clamp = !TRUST || (M % 2 == 0 && (s == NP - 1 || t == NP - 1));  // folds after unrolling
+            return clamp ? nngp_cov_unit<KIND, true>(Pc, ctab, d2) : nngp_cov_unit<KIND, false>(Pc, ctab, d2);
+        };
         const int64_t lr = threadIdx.x >> 1;  // the tile's local row (pairb_tiling)
         const int64_t r = tile * tq + (tile < trem ? tile : trem) + lr;
         const bool live = lr < tq + (tile < trem ? 1 : 0);
-        const int64_t rl = live ? r : n_rows - 1;
+        // (a trusted tile's idle lanes redo the tile's first row: the last row's tile may not be trusted)
+        const int64_t rl = live ? r : (TRUST ? r - lr : n_rows - 1);
         // branch-free (a branch here makes the compiler drain every outstanding load, the
         // early exp-table fetch included, at the join): without an order, read nbr's word
         const int32_t ov = (order != nullptr ? order : nbr)[rl];
@@ -431,7 +456,9 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
             const int32_t j = a < M ? jn[s] : -1;
             jmax = max(jmax, j);
             jmin = min(jmin, j);
-            const bool in_range = (uint32_t)j < n32;
+            // trusted: every neighbour slot's index is in range; only row M + 1 (even M: lane 1 of the last
+            // pair) is padding
+            const bool in_range = TRUST ? (s < NP - 1 || M % 2 == 1) : (uint32_t)j < n32;
             const bool self = a == M;
             const double* pc = self ? qcoords + i * ds : (in_range ? coords + (int64_t)j * ds : far_point<DA>(a));
             const double* pv = self ? (qvalues != nullptr ? qvalues + i : kZeroValue)
@@ -444,7 +471,7 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
             }
             if constexpr (!LEFT) z[s] = *pv;  // (the left-looking kernel gathers the values late)
         }
-        const bool bad_index = (int64_t)jmax >= n_points || jmin < -1;
+        const bool bad_index = !TRUST && ((int64_t)jmax >= n_points || jmin < -1);
         if constexpr (LEFT) {  // the late state waits in LDS (read back by this thread only)
 #pragma unroll
             for (int s = 0; s < NP; ++s) lidx[s][threadIdx.x] = jn[s];
@@ -689,8 +716,8 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
             for (int s = 0; s < NP; ++s) {
 #pragma unroll
                 for (int t = 0; t < s; ++t) {
-                    R[s][t][0] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s], o[t]));
-                    R[s][t][1] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s], p[t]));
+                    R[s][t][0] = cov(point_d2<DA>(o[s], o[t]), s, t);
+                    R[s][t][1] = cov(point_d2<DA>(o[s], p[t]), s, t);
                 }
                 R[s][s][0] = Pc.diag;
             }
@@ -707,12 +734,12 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                         a[k] = pr_pick(mask1, o[s1][k], o[s0][k]);
                         b[k] = pr_pick(mask1, p[s1][k], p[s0][k]);
                     }
-                    const double c = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(a, b));
+                    const double c = cov(point_d2<DA>(a, b), s0, s1);
                     R[s1][s1][1] = c;
                     R[s0][s0][1] = pr_from0(c);
                 } else {
-                    R[s0][s0][1] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s0], p[s0]));
-                    if (s1 < NP) R[s1][s1][1] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s1], p[s1]));
+                    R[s0][s0][1] = cov(point_d2<DA>(o[s0], p[s0]), s0, s0);
+                    if (s1 < NP) R[s1][s1][1] = cov(point_d2<DA>(o[s1], p[s1]), s1, s1);
                 }
             }
         }
@@ -857,8 +884,8 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                 for (int k = 0; k < DA; ++k) pu[k] = (u % 2 == 1) ? pnext[k] : pr_swap(o[u][k]);
 #pragma unroll
                 for (int s = u + 1; s < NP; ++s) {
-                    R[s][u][0] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s], o[u]));
-                    R[s][u][1] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[s], pu));
+                    R[s][u][0] = cov(point_d2<DA>(o[s], o[u]), s, u);
+                    R[s][u][1] = cov(point_d2<DA>(o[s], pu), s, u);
                 }
                 R[u][u][0] = Pc.diag;
                 // the within-pair entry (2u+1, 2u) is read from lane 1 only: for pairs u, u+1 (u even)
@@ -872,12 +899,12 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                         a[k] = pr_pick(mask1, o[u + 1][k], o[u][k]);
                         b[k] = pr_pick(mask1, pnext[k], pu[k]);
                     }
-                    wpnext = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(a, b));
+                    wpnext = cov(point_d2<DA>(a, b), u, u + 1);
                     R[u][u][1] = pr_from0(wpnext);
                 } else if (u % 2 == 1) {
                     R[u][u][1] = wpnext;
                 } else {
-                    R[u][u][1] = nngp_cov_unit<KIND>(Pc, ctab, point_d2<DA>(o[u], pu));  // (2u+1, 2u): lane 1's
+                    R[u][u][1] = cov(point_d2<DA>(o[u], pu), u, u);  // (2u+1, 2u): lane 1's
                 }
                 }
 #pragma unroll
@@ -949,7 +976,7 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             rrl = (int64_t)(((uint64_t)(uint32_t)lidx[NP + 1][threadIdx.x] << 32) | (uint32_t)lidx[NP][threadIdx.x]);
             il = i0 + rrl;
-            bidx = lidx[NP + 2][threadIdx.x] != 0;
+            bidx = !TRUST && lidx[NP + 2][threadIdx.x] != 0;
         }
 
         {
@@ -966,7 +993,7 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                 for (int s = 0; s < NP; ++s) {
                     const int a = 2 * s + q;
                     const int32_t j = a < M ? lidx[s][threadIdx.x] : -1;
-                    const bool in_range = (uint32_t)j < n32;
+                    const bool in_range = TRUST ? (s < NP - 1 || M % 2 == 1) : (uint32_t)j < n32;
                     const double* pv = a == M ? (qvalues != nullptr ? qvalues + il : kZeroValue)
                                               : ((values != nullptr && in_range) ? values + j : kZeroValue);
                     z[s] = *pv;
@@ -1047,7 +1074,18 @@ __global__ __launch_bounds__(kPairbThreads) NNGP_PAIRB_ATTR void bf_pairb(const 
                          (live && bidx) ? (double)il : INFINITY, sh, 0, rec, lexp, tile);
         __syncthreads();
         if (threadIdx.x == 0) pairb_tile_fold(sh, 0, rec, lexp, tile);
+    };
+    if constexpr (TRUSTABLE) {
+        // block-uniform: one scalar load and branch; the two instances share nothing until the kernel ends
+        const bool trusted =
+            ckmask != nullptr &&
+            ((uint32_t)__builtin_amdgcn_readfirstlane((int)ckmask[tile >> 5]) >> (uint32_t)(tile & 31) & 1u) == 0u;
+        if (trusted) {
+            body(std::true_type{});
+            return;
+        }
     }
+    body(std::false_type{});
 }
 
 // workspace: a 256-B header (int64 tile count, written by the sweep and read by the fold; the second word,
@@ -1081,7 +1119,7 @@ static void launch_pairb_mkd(const BfArgs& a, const CovParams& Pc, hipStream_t s
     hipLaunchKernelGGL((bf_pairb<M, KIND, D, PL>), dim3((unsigned)nb), dim3(kPairbThreads), lds, s, a.coords,
                        a.n_points, a.nbr, a.order, a.n_rows, a.i0, Pc, KIND == NNGP_KIND_BLOCKS ? 1.0 : a.sigma2, a.values,
                        a.qcoords, a.qvalues, a.B, a.F, a.R, pairb_rec(a.bpart), pairb_lexp(a.bpart, a.n_rows), a.dim,
-                       a.cblk, tl.q, tl.rem, pairb_hdr(a.bpart), pp);
+                       a.cblk, tl.q, tl.rem, pairb_hdr(a.bpart), pp, a.checked);
 }
 
 // the planned regions of a planned sweep (pair_plan.h; the direct ones go through bf_pairb_launch with

@@ -9,6 +9,7 @@
 #include "../../include/nngp.h"
 #include "nngp_internal.h"
 #include "bf_pairb.h"
+#include "nbr_cert.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -112,7 +113,7 @@ static int bf_common(const double* coords, int64_t n_points, int32_t dim, const 
                      const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
                      double sigma2, double phi, double tau2, double nu, const double* values, const double* qvalues, double* B,
                      double* F, double* R, double* partials, void* workspace, size_t workspace_bytes, int32_t algo,
-                     void* stream) {
+                     void* stream, const uint32_t* checked = nullptr) {
     if (coords == nullptr || qcoords == nullptr || workspace == nullptr)
         return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
     if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
@@ -162,6 +163,7 @@ static int bf_common(const double* coords, int64_t n_points, int32_t dim, const 
     hipStream_t s = (hipStream_t)stream;
     nngp::BfArgs args{coords, n_points, nbr, n_rows, i0, m, kind, dim, sigma2, phi, tau2, nu, order, values, qcoords,
                       qvalues, B, F, R, partials, (double*)workspace};
+    if (a == nngp::kAlgoPairB) args.checked = checked;  // a certificate's checked-tile bits (nngp_bf_sweep_cert)
     hipError_t e = nngp::bf_launch(args, a, s);
     if (e != hipSuccess) return hip_fail(e, "bf_sweep launch");
     return NNGP_OK;
@@ -173,6 +175,81 @@ int nngp_bf_sweep(const double* coords, int64_t n_points, int32_t dim, const int
                   size_t workspace_bytes, int32_t algo, void* stream) {
     return bf_common(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2, nu,
                      values, values, B, F, R, partials, workspace, workspace_bytes, algo, stream);
+}
+
+size_t nngp_nbr_cert_bytes(int64_t n_rows) { return n_rows < 0 ? 0 : nngp::cert_total_bytes(n_rows); }
+
+int nngp_nbr_cert_build(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                        int64_t n_rows, int32_t m, int64_t i0, void* cert, size_t cert_bytes, int64_t* info,
+                        void* stream) {
+    if (coords == nullptr || cert == nullptr || info == nullptr || (n_rows > 0 && nbr == nullptr))
+        return fail(NNGP_EINVAL, "coords, cert, info (and nbr for n_rows > 0) must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EUNSUP, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (((uintptr_t)cert & 255) != 0) return fail(NNGP_EINVAL, "cert must be 256-byte aligned");
+    const size_t need = nngp::cert_total_bytes(n_rows);
+    if (cert_bytes < need) return fail(NNGP_EINVAL, "cert too small: %zu < %zu bytes", cert_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = nngp::nbr_cert_launch(coords, n_points, dim, nbr, n_rows, m, cert, s);
+    if (e != hipSuccess) return hip_fail(e, "nbr_cert build");
+    const int64_t tiles = nngp::cert_tiles(n_rows);
+    int32_t n_checked = 0;
+    double rec[nngp::kCertSpanBlocks * 8];
+    e = hipMemcpyAsync(&n_checked, cert, sizeof n_checked, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(rec, (const char*)cert + nngp::cert_span_off(tiles), sizeof rec, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "nbr_cert counts");
+    double span = 0.0;
+    if (!nngp::cert_span_fold(rec, nngp::kCertSpanBlocks, dim, &span))
+        return fail(NNGP_EINVAL, "coordinates must be finite (and their bounding box's squared diagonal too)");
+    for (int k = 0; k < NNGP_CERT_INFO_LEN; ++k) info[k] = 0;
+    info[nngp::kCertIMagic] = nngp::kCertMagic;
+    info[nngp::kCertICoords] = (int64_t)(uintptr_t)coords;
+    info[nngp::kCertINbr] = (int64_t)(uintptr_t)nbr;
+    info[nngp::kCertIOrder] = (int64_t)(uintptr_t)order;
+    info[nngp::kCertINPoints] = n_points;
+    info[nngp::kCertIDim] = dim;
+    info[nngp::kCertINRows] = n_rows;
+    info[nngp::kCertIM] = m;
+    info[nngp::kCertII0] = i0;
+    info[nngp::kCertITiles] = tiles;
+    info[nngp::kCertIChecked] = n_checked;
+    memcpy(&info[nngp::kCertISpan], &span, sizeof span);
+    return NNGP_OK;
+}
+
+int64_t nngp_nbr_cert_trusted_tiles(const int64_t* info, int32_t kind, double sigma2, double phi, double tau2) {
+    return nngp::cert_trusted_tiles(info, kind, sigma2, phi, tau2);
+}
+
+int nngp_bf_sweep_cert(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                       double nu, const double* values, double* B, double* F, double* R, double* partials,
+                       void* workspace, size_t workspace_bytes, int32_t algo, const void* cert, size_t cert_bytes,
+                       const int64_t* info, void* stream) {
+    if (cert == nullptr || info == nullptr) return fail(NNGP_EINVAL, "cert and info must be non-null");
+    if (info[nngp::kCertIMagic] != nngp::kCertMagic) return fail(NNGP_EINVAL, "info is not a certificate's");
+    if (info[nngp::kCertICoords] != (int64_t)(uintptr_t)coords || info[nngp::kCertINbr] != (int64_t)(uintptr_t)nbr ||
+        info[nngp::kCertIOrder] != (int64_t)(uintptr_t)order)
+        return fail(NNGP_EINVAL, "the certificate was built for other coords / nbr / order buffers (rebuild it for "
+                                 "this sweep's)");
+    if (info[nngp::kCertINPoints] != n_points || info[nngp::kCertIDim] != dim || info[nngp::kCertINRows] != n_rows ||
+        info[nngp::kCertIM] != m || info[nngp::kCertII0] != i0)
+        return fail(NNGP_EINVAL, "the certificate was built for (n_points %lld, dim %lld, n_rows %lld, m %lld, i0 %lld), "
+                                 "not this sweep's (%lld, %d, %lld, %d, %lld)", (long long)info[nngp::kCertINPoints],
+                    (long long)info[nngp::kCertIDim], (long long)info[nngp::kCertINRows], (long long)info[nngp::kCertIM],
+                    (long long)info[nngp::kCertII0], (long long)n_points, dim, (long long)n_rows, m, (long long)i0);
+    if (n_rows < 0 || cert_bytes < nngp::cert_total_bytes(n_rows) || info[nngp::kCertITiles] != nngp::cert_tiles(n_rows))
+        return fail(NNGP_EINVAL, "cert too small for %lld rows", (long long)n_rows);
+    // the certificate is a hint: without a trusted tile at this theta (or on another kernel) today's sweep
+    const bool use = nngp_nbr_cert_trusted_tiles(info, kind, sigma2, phi, tau2) > 0;
+    const uint32_t* checked = use ? (const uint32_t*)((const char*)cert + nngp::kCertMaskOff) : nullptr;
+    return bf_common(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2, nu,
+                     values, values, B, F, R, partials, workspace, workspace_bytes, algo, stream, checked);
 }
 
 int nngp_bf_cross(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,

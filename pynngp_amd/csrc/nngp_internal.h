@@ -103,6 +103,9 @@ struct BfArgs {
     // n_tiles in all), or, for the planned launch, n_plan_blocks regions of the plan
     const int32_t* tiles = nullptr;
     int64_t n_tiles = 0, n_tile_list = 0, n_plan_blocks = 0;
+    // pair kernel: the checked-tile bits of a neighbour-set certificate (nngp_nbr_cert_build; bit t of word
+    // t / 32 set: tile t keeps its index checks and clamps), or null: every tile checked
+    const uint32_t* checked = nullptr;
 };
 
 int64_t bf_record_count(int64_t n_rows, int algo, int m);
@@ -123,6 +126,9 @@ hipError_t bf_launch_planned(const BfArgs& a, const PlanLaunch& pl, hipStream_t 
 size_t pair_plan_build_lds(int m);
 hipError_t pair_plan_build_launch(const int32_t* nbr, const int32_t* order, int64_t n_rows, int m, int dim, int64_t i0,
                                   int64_t n_points, int64_t tq, int64_t trem, void* plan, hipStream_t s);
+// neighbour-set certificates (nbr_cert.h, nbr_cert.hip): the checked-tile bits and the coordinate records
+hipError_t nbr_cert_launch(const double* coords, int64_t n_points, int dim, const int32_t* nbr, int64_t n_rows, int m,
+                           void* cert, hipStream_t s);
 bool bf_pairb_blocks_supported(int m);
 bool bf_group_blocks_launch(const BfArgs& a, hipStream_t s);  // NNGP_KIND_BLOCKS at m = 25..32 (bf_group.h)
 bool bf_group_blocks_supported(int m);

@@ -592,11 +592,14 @@ NNGP_FN double nngp_exp_unit(const CovParams& P, const double* tab, double u) {
     return fma(Ts, fq, Ts);
 }
 
-// unit-variance covariance of kind KIND at squared distance d2 (tab: nngp_exp_table_load_unit)
-template <int KIND>
+// unit-variance covariance of kind KIND at squared distance d2 (tab: nngp_exp_table_load_unit).
+// CLAMP = false leaves out the clamp at d2max: for callers that know d2 < d2max (a certified neighbour set,
+// nngp_nbr_cert_trusted_tiles: no far-away padding point, the coordinates' bounding box inside the clamp),
+// where fmin(d2, d2max) is d2 itself and the result has the same bits.
+template <int KIND, bool CLAMP = true>
 NNGP_FN double nngp_cov_unit(const CovParams& P, const double* tab, double d2) {
     if (KIND == NNGP_KIND_MATERN) return nngp_matern_tab(P, tab, d2);  // tab: the Matern table
-    const double x = fmin(d2, P.d2max);
+    const double x = CLAMP ? fmin(d2, P.d2max) : d2;
     if (KIND == NNGP_KIND_GAUSSIAN) return nngp_exp_unit(P, tab, x);
     const double d = nngp_sqrt(x);
     if (KIND == NNGP_KIND_SPHERICAL) {

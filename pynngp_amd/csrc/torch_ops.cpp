@@ -116,7 +116,8 @@ void bf_sweep_out(const at::Tensor& coords, const at::Tensor& nbr, const c10::op
                   const c10::optional<at::Tensor>& B, const c10::optional<at::Tensor>& F,
                   const c10::optional<at::Tensor>& R, const at::Tensor& partials, const at::Tensor& ws,
                   int64_t algo, double nu, const c10::optional<at::Tensor>& plan,
-                  const c10::optional<at::Tensor>& plan_info) {
+                  const c10::optional<at::Tensor>& plan_info, const c10::optional<at::Tensor>& cert,
+                  const c10::optional<at::Tensor>& cert_info) {
     check_coords(coords, "coords");
     const at::OptionalDeviceGuard guard(coords.device());
     check_nbr(nbr, coords);
@@ -149,6 +150,21 @@ void bf_sweep_out(const at::Tensor& coords, const at::Tensor& nbr, const c10::op
                  "nngp_bf_sweep_plan");
         return;
     }
+    if (cert.has_value()) {
+        // a neighbour-set certificate (nbr_cert op): trusted tiles skip the index checks and clamps, same bits
+        TORCH_CHECK(cert_info.has_value() && cert_info->device().is_cpu() && cert_info->scalar_type() == at::kLong &&
+                        cert_info->numel() == NNGP_CERT_INFO_LEN && cert_info->is_contiguous(),
+                    "cert_info must be the nbr_cert op's CPU int64 (", NNGP_CERT_INFO_LEN, ",) tensor");
+        TORCH_CHECK(cert->scalar_type() == at::kByte && cert->is_contiguous(), "cert must be a contiguous uint8 tensor");
+        check_same_device(coords, *cert, "cert");
+        check_rc(nngp_bf_sweep_cert(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order),
+                                    rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2, nu, ptr<double>(values),
+                                    ptr<double>(B), ptr<double>(F), ptr<double>(R), partials.data_ptr<double>(),
+                                    ws.data_ptr(), (size_t)ws.nbytes(), (int32_t)algo, cert->data_ptr(),
+                                    (size_t)cert->nbytes(), cert_info->data_ptr<int64_t>(), stream(coords)),
+                 "nngp_bf_sweep_cert");
+        return;
+    }
     check_rc(nngp_bf_sweep(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows,
                            (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2, nu, ptr<double>(values), ptr<double>(B),
                            ptr<double>(F), ptr<double>(R), partials.data_ptr<double>(), ws.data_ptr(),
@@ -174,7 +190,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_sweep(const at::Tensor& coords
     bf_sweep_out(coords, nbr, order, i0, kind, sigma2, phi, tau2, values,
                  want_bf ? c10::optional<at::Tensor>(B) : c10::nullopt,
                  want_bf ? c10::optional<at::Tensor>(F) : c10::nullopt, c10::nullopt, p, ws, algo, nu, c10::nullopt,
-                 c10::nullopt);
+                 c10::nullopt, c10::nullopt, c10::nullopt);
     return {B, F, p};
 }
 
@@ -230,6 +246,28 @@ std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::o
     return {plan, info};
 }
 
+// the neighbour-set certificate of a sweep over (coords, nbr, order, i0) (include/nngp.h nngp_nbr_cert_build):
+// (certificate bytes on the GPU, CPU int64 info).  A setup call: it synchronises the tensors' stream once.
+std::tuple<at::Tensor, at::Tensor> nbr_cert(const at::Tensor& coords, const at::Tensor& nbr,
+                                            const c10::optional<at::Tensor>& order, int64_t i0) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->sizes() == at::IntArrayRef{rows} && order->is_contiguous(),
+                    "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(coords, *order, "order");
+    }
+    auto cert = workspace((int64_t)nngp_nbr_cert_bytes(rows), coords);
+    auto info = at::empty({NNGP_CERT_INFO_LEN}, at::TensorOptions().dtype(at::kLong));
+    check_rc(nngp_nbr_cert_build(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order),
+                                 rows, (int32_t)m, i0, cert.data_ptr(), (size_t)cert.nbytes(), info.data_ptr<int64_t>(),
+                                 stream(coords)),
+             "nngp_nbr_cert_build");
+    return {cert, info};
+}
+
 std::tuple<at::Tensor, at::Tensor> row_order(const at::Tensor& coords, int64_t i0, int64_t rows,
                                              const c10::optional<at::Tensor>& nbr) {
     check_coords(coords, "coords");
@@ -278,7 +316,9 @@ TORCH_LIBRARY(nngp, m) {
           "bool want_bf, int algo, Tensor? order=None, float nu=-1.0) -> (Tensor, Tensor, Tensor)");
     m.def("bf_sweep_out(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, "
           "float tau2, Tensor? values, Tensor(a!)? B, Tensor(b!)? F, Tensor(c!)? R, Tensor(d!) partials, "
-          "Tensor(e!) workspace, int algo, float nu=-1.0, Tensor? plan=None, Tensor? plan_info=None) -> ()");
+          "Tensor(e!) workspace, int algo, float nu=-1.0, Tensor? plan=None, Tensor? plan_info=None, "
+          "Tensor? cert=None, Tensor? cert_info=None) -> ()");
+    m.def("nbr_cert(Tensor coords, Tensor nbr, Tensor? order, int i0) -> (Tensor, Tensor)");
     m.def("pair_plan(Tensor nbr, Tensor? order, int i0, int n_points, int dim) -> (Tensor, Tensor)");
     m.def("bf_cross(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
           "Tensor? ref_values, int algo, float nu=-1.0) -> (Tensor, Tensor, Tensor)");
@@ -295,5 +335,6 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_cross", &bf_cross);
     m.impl("row_order", &row_order);
     m.impl("pair_plan", &pair_plan);
+    m.impl("nbr_cert", &nbr_cert);
     m.impl("combine_partials_out", &combine_partials_out);
 }

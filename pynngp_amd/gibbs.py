@@ -355,6 +355,12 @@ class SeqNNGP:
         if (self._use_plan and self._custom is None and algo in ("auto", "pairb")
                 and _lib.pair_plan_supported(self.m, kind, self.coords.shape[1])):
             self._plan = ops.pair_plan(self.nbr, None, 0, n, self.coords.shape[1])
+        # neighbour-set certificate for the unplanned phi-proposal sweeps (include/nngp.h nngp_nbr_cert_build): the
+        # DAG and the coordinates never change, so the index checks and distance clamps are settled once (the
+        # same B / F / r bits).  NNGP_NBR_CERT=0 turns it off.
+        self._cert = (None, None)
+        if self._custom is None and self._plan[0] is None and self.m >= 1 and ops.cert_default():
+            self._cert = ops.nbr_cert(self.coords, self.nbr, None, 0)
         self._stats_buf = z(2 + self.p)
         self._sweep_into(self.phi, self.B, self.Ft, self.r)
         self._prep = _lib.gibbs_prepare(self.B, self.Ft, self.off, self.rev_j, self.rev_k)
@@ -410,7 +416,8 @@ class SeqNNGP:
                                  partials=self._part, workspace=self._ws)
             return
         torch.ops.nngp.bf_sweep_out(self.coords, self.nbr, None, 0, self._kind_code, 1.0, float(phi), 0.0, self.w, B,
-                                    Ft, r, self._part, self._ws, self._algo_code, self._nu_arg, *self._plan)
+                                    Ft, r, self._part, self._ws, self._algo_code, self._nu_arg, *self._plan,
+                                    *self._cert)
 
     @staticmethod
     def _check(p):

@@ -14,8 +14,9 @@ for tracing.
     torch.ops.nngp.bf_sweep(coords, nbr, i0, kind, sigma2, phi, tau2, values, want_bf, algo, order=None, nu=-1.0)
         -> (B, F, partials)
     torch.ops.nngp.bf_sweep_out(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, B, F, R, partials,
-                                workspace, algo, nu=-1.0, plan=None, plan_info=None) -> ()
-                                                                      # the hot path: caller-owned buffers
+                                workspace, algo, nu=-1.0, plan=None, plan_info=None, cert=None, cert_info=None)
+        -> ()                                                         # the hot path: caller-owned buffers
+    torch.ops.nngp.nbr_cert(coords, nbr, order, i0) -> (cert, cert_info)   # neighbour-set certificate (setup)
     torch.ops.nngp.pair_plan(nbr, order, i0, n_points, dim) -> (plan, plan_info)   # wave pair plan (setup)
     torch.ops.nngp.bf_cross(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0) -> (B, F, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
@@ -81,8 +82,12 @@ def _register_fakes() -> None:
 
     @fake("bf_sweep_out")
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, B, F, R, partials, workspace, algo, nu=-1.0,
-          plan=None, plan_info=None):
+          plan=None, plan_info=None, cert=None, cert_info=None):
         return None
+
+    @fake("nbr_cert")
+    def _(coords, nbr, order, i0):
+        raise RuntimeError("nbr_cert is a setup call (it synchronises to read its tile counts): build it eagerly")
 
     @fake("pair_plan")
     def _(nbr, order, i0, n_points, dim):
@@ -118,17 +123,43 @@ def algo_code(algo: str) -> int:
 
 
 def bf_sweep_out(coords, nbr, order, i0, kind: str, theta, values, B, F, R, partials, workspace,
-                 algo: str = "auto", plan=None) -> None:
+                 algo: str = "auto", plan=None, cert=None) -> None:
     """The fused sweep into caller-owned buffers through ``torch.ops.nngp.bf_sweep_out``
     (stream-ordered on torch's current stream, no host synchronisation).  ``theta`` =
     (sigma2, phi, tau2), or (sigma2, phi, tau2, nu) for the ``matern`` kind.  ``plan``: a
-    ``(plan, plan_info)`` pair from :func:`pair_plan` for this nbr / order / i0."""
+    ``(plan, plan_info)`` pair from :func:`pair_plan` for this nbr / order / i0.  ``cert``: a
+    ``(cert, cert_info)`` pair from :func:`nbr_cert` for these coords / nbr / order / i0 (same bits, fewer
+    instructions: trusted tiles skip the index checks and clamps)."""
     load()
     nu = float(theta[3]) if len(theta) > 3 else -1.0
     pbuf, pinfo = plan if plan is not None else (None, None)
+    cbuf, cinfo = cert if cert is not None else (None, None)
     torch.ops.nngp.bf_sweep_out(coords, nbr, order, int(i0), kind_code(kind), float(theta[0]), float(theta[1]),
                                 float(theta[2]), values, B, F, R, partials, workspace, algo_code(algo), nu, pbuf,
-                                pinfo)
+                                pinfo, cbuf, cinfo)
+
+
+def nbr_cert(coords, nbr, order, i0: int):
+    """The neighbour-set certificate of a sweep over ``(coords, nbr, order, i0)`` (``torch.ops.nngp.nbr_cert``):
+    ``(cert, cert_info)``.  A setup call (one host synchronisation).  The contract: coords, nbr and order are
+    not modified afterwards (rebuild the certificate if they are)."""
+    load()
+    return torch.ops.nngp.nbr_cert(coords, nbr, order, int(i0))
+
+
+def nbr_cert_trusted_tiles(cert_info, kind: str, theta) -> int:
+    """Tiles a sweep of ``kind`` at ``theta`` = (sigma2, phi, tau2) runs trusted (``nngp_nbr_cert_trusted_tiles``,
+    a host function): 0 when the distance clamp may bind or the kind is not one of the five fused ones."""
+    import ctypes
+
+    info = (ctypes.c_int64 * _lib.CERT_INFO_LEN)(*[int(v) for v in cert_info.tolist()])
+    return int(_lib.load().nngp_nbr_cert_trusted_tiles(info, _lib.KIND_CODES.get(kind, 99), float(theta[0]),
+                                                       float(theta[1]), float(theta[2])))
+
+
+def cert_default() -> bool:
+    """Whether models certify their neighbour sets at construction: on unless NNGP_NBR_CERT=0 (an A/B switch)."""
+    return os.environ.get("NNGP_NBR_CERT", "1") != "0"
 
 
 def pair_plan(nbr, order, i0: int, n_points: int, dim: int):

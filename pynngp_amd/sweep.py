@@ -16,6 +16,7 @@ the default compute is the HIP kernel through the native operator
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import time
 from typing import Callable, Optional
@@ -162,6 +163,13 @@ class ShardedLogLik:
             self.plan_read_bytes = _lib.pair_plan_read_bytes(self._plan[0], self.m)
         elif plan:
             raise ValueError(f"pair plans serve algo auto / pairb, 2 <= m <= 17, dim 1..3 (m={self.m}, dim={d})")
+        # neighbour-set certificate (include/nngp.h nngp_nbr_cert_build): coords, nbr and order are fixed for the
+        # life of this object, so the per-sweep index checks and distance clamps are settled once here (one
+        # host synchronisation); every sweep passes it on (the same bits).  NNGP_NBR_CERT=0 turns it off.
+        self._cert = self._cert_ctypes = None
+        if compute is None and self._plan is None and self.hi > self.lo and self.m >= 1 and ops.cert_default():
+            self._cert = ops.nbr_cert(self._coords_sweep, self._nbr_sweep, self.order, self.lo)
+            self._cert_ctypes = (self._cert[0], (ctypes.c_int64 * _lib.CERT_INFO_LEN)(*self._cert[1].tolist()))
 
     @property
     def planned(self) -> bool:
@@ -190,12 +198,14 @@ class ShardedLogLik:
         if self.api == "ctypes":  # the same C-ABI call without the dispatcher (A/B of the op overhead)
             _lib.bf_sweep(self._coords_sweep, self._nbr_sweep, self.lo, cov.kind, s2, phi, tau2, values=values,
                           want_bf=want_bf, algo=self.algo, B=B, F=F, partials=p, workspace=self._ws, order=self.order,
-                          nu=cov.nu_arg, plan=self._plan_ctypes if plan is not None else None)
+                          nu=cov.nu_arg, plan=self._plan_ctypes if plan is not None else None,
+                          cert=self._cert_ctypes)
             return p
         pb, pi = plan if plan is not None else (None, None)
+        cb, ci = self._cert if self._cert is not None else (None, None)
         self._sweep_op(self._coords_sweep, self._nbr_sweep, self.order, self.lo, ops.kind_code(cov.kind),
                        float(s2), float(phi), float(tau2), values, B, F, None, p, self._ws, self._algo_code,
-                       -1.0 if cov.nu_arg is None else cov.nu_arg, pb, pi)
+                       -1.0 if cov.nu_arg is None else cov.nu_arg, pb, pi, cb, ci)
         return p
 
     def partials(self, cov: Covariance, values: Optional[torch.Tensor], want_bf: bool = True,
