@@ -83,7 +83,9 @@ const char *nngp_version(void);
  * chains' sweeps (nngp_gibbs_w_sweep_chains, _il) and the device colouring (nngp_color_moral_graph_dev);
  * NNGP_ALGO_AUTO / PAIRB / QUAD take the general Matern kind for every nu; nothing earlier moved.
  * Revision 4 (library 0.4.0): the pair plans are per wave (a new plan format, m <= 17) and their info
- * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan). */
+ * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan).
+ * Added within revision 4 (nothing earlier moved): the gradient sweep nngp_bf_grad_workspace_bytes /
+ * nngp_bf_grad. */
 #define NNGP_ABI_VERSION 4
 int32_t nngp_abi_version(void);
 
@@ -171,6 +173,25 @@ int nngp_bf_sweep(const double *coords, int64_t n_points, int32_t dim, const int
  * sweep needed, so a mismatched call fails with NNGP_EINVAL instead of reading past it. */
 int nngp_bf_finalize(const void *workspace, size_t workspace_bytes, int64_t n_rows, int32_t m, int32_t kind,
                      int32_t dim, int32_t algo, double *partials, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Analytic gradient of the log-likelihood in (sigma2, phi, tau2), one fused sweep over locations
+ * i0 .. i0 + n_rows - 1 (S = T sweeps: coords, nbr, order, i0 and values as nngp_bf_sweep, values required).
+ *   partials[4]: as nngp_bf_sweep (its own fixed fold order: equal to nngp_bf_sweep's to rounding, not bit
+ *                for bit)
+ *   grad[3]    = sum_i d l_i / d (sigma2, phi, tau2), a fixed-order fold: bit-reproducible run to run
+ *   G          : NULL or (n_rows, 3), the term of location i0 + r in row r (r = order[t] for nbr row t, else t)
+ * Rows flagged in partials[2] get NaN in G, and either flag makes grad meaningless (nngp_check_partials).
+ * Slots without a point (-1 padding) and out-of-range indices contribute exactly 0 to every sum.
+ * kind: NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL (the general-nu Matern kind: NNGP_EUNSUP); 1 <= m <= 32
+ * (else NNGP_EUNSUP); 1 <= dim <= 3.  workspace: nngp_bf_grad_workspace_bytes(n_rows, m) bytes (0 for an
+ * unsupported m or n_rows < 0), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_grad_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_grad(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                 int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                 const double *values, double *G, double *partials, double *grad, void *workspace,
+                 size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Wave pair plans: the same sweep with every covariance a wavefront's locations share evaluated once.

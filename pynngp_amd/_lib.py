@@ -67,6 +67,8 @@ SYMBOLS = (
     "nngp_nbr_cert_build",
     "nngp_nbr_cert_trusted_tiles",
     "nngp_bf_sweep_cert",
+    "nngp_bf_grad_workspace_bytes",
+    "nngp_bf_grad",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -116,6 +118,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_sweep_workspace_bytes.argtypes = [I64, I32, I32, I32, I32]
     lib.nngp_bf_sweep_workspace_bytes.restype = SZ
     lib.nngp_bf_sweep.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, SZ, I32, P]
+    lib.nngp_bf_grad_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_grad_workspace_bytes.restype = SZ
+    lib.nngp_bf_grad.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad.restype = ctypes.c_int
     lib.nngp_bf_cross.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, P, SZ,
                                   I32, P]
     lib.nngp_bf_cross.restype = ctypes.c_int
@@ -524,6 +530,55 @@ def bf_sweep(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2
                              _ptr(partials), _ptr(workspace), workspace.numel(), a, _stream(dev)),
            "nngp_bf_sweep")
     return B, F, partials
+
+
+GRAD_MAX_M = 32  # nngp_bf_grad: 1 <= m <= 32, kinds exponential .. spherical
+
+
+def bf_grad(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,
+            values: torch.Tensor, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+            workspace: Optional[torch.Tensor] = None
+            ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Analytic log-likelihood gradient sweep (``nngp_bf_grad``, include/nngp.h) over rows ``i0 .. i0 + len(nbr)``.
+
+    Returns ``(partials, grad, G)``: the four partials of :func:`bf_sweep`, ``grad`` = the summed
+    d loglik / d (sigma2, phi, tau2) (float64 (3,) device tensors, fixed fold order) and, with ``want_rows``,
+    ``G`` (rows, 3), the per-location terms at their natural rows (NaN in rows flagged in partials[2]).
+    Stream-ordered on torch's current stream; no host synchronisation.  Kinds exponential .. spherical,
+    1 <= m <= 32; ``order`` as in :func:`bf_sweep`.
+    """
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if values is None or values.dtype != torch.float64 or values.shape != (coords.shape[0],):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    rows, m = nbr.shape
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "matern":
+        raise NotImplementedError("the gradient sweep serves the kinds exponential .. spherical, not the general-nu "
+                                  "matern kind")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the gradient sweep serves 1 <= m <= {GRAD_MAX_M} (m={m})")
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_grad_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    if workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the sweep's device")
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(3, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, 3), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad(_ptr(coords), coords.shape[0], coords.shape[1], _ptr(nbr), _ptr(order), rows, m, i0,
+                            KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(values), _ptr(G),
+                            _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_grad")
+    return partials, grad, G
 
 
 def nbr_cert(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, order: Optional[torch.Tensor] = None):

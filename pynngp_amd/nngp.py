@@ -718,15 +718,68 @@ class NNGP:
         quad = qyy - 2.0 * mu * qy1 + mu * mu * q11
         return -0.5 * (n * LOG_2PI + logF + quad), float(mu)
 
+    def _grad_cov(self, cov) -> Covariance:
+        """The covariance of a gradient sweep: a fused kind other than the general-nu Matern, m >= 1."""
+        cv = self._covariance(cov)
+        if not isinstance(cv, Covariance):
+            raise TypeError("the analytic gradient needs a Covariance of a fused kind (exponential, matern32, "
+                            f"matern52, gaussian, spherical), not {type(cv).__name__}")
+        if cv.kind == "matern":
+            raise NotImplementedError("the analytic gradient does not serve the general-nu matern kind")
+        if not 1 <= self.m <= _lib.GRAD_MAX_M:
+            raise NotImplementedError(f"the analytic gradient serves 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
+        return cv
+
+    def _values_dev(self, values):
+        v = self.y if values is None else values
+        v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
+                            dtype=torch.float64).to(self.device)
+        if v.dim() != 1 or v.shape[0] != self.nbr.shape[0]:
+            raise ValueError(f"one value per location is needed ({self.nbr.shape[0]}, 1-D)")
+        return v
+
+    def loglik_grad(self, values=None, cov: Optional[Covariance] = None):
+        """:meth:`loglik` and its analytic gradient in (sigma2, phi, tau2) from one fused gradient sweep
+        (``nngp_bf_grad``): ``(loglik, grad)`` with ``grad`` a float64 ndarray (3,)."""
+        cv = self._grad_cov(cov)
+        v = self._values_dev(values)
+        p, g, _ = _lib.bf_grad(self._s_dev, self._nbr_sorted, 0, cv.kind, cv.sigma2, cv.phi, cv.tau2, v,
+                               order=self._order)
+        h = torch.cat([p, g]).cpu().numpy()
+        _raise_on_bad(h[:4])
+        n = self.nbr.shape[0]
+        return -0.5 * (n * LOG_2PI + h[0] + h[1]), h[4:7].copy()
+
+    def profile_loglik_grad(self, cov: Covariance, values=None, mean: str = "constant"):
+        """:meth:`profile_loglik` and its gradient in (sigma2, phi, tau2): ``(loglik, mu, grad)``.  By the
+        envelope theorem the gradient of the profiled likelihood is the plain gradient at ``values - mu``:
+        the two sweeps for mu plus one gradient sweep."""
+        cv = self._grad_cov(cov)
+        v = self._values_dev(values)
+        if mean == "zero":  # one gradient sweep gives both
+            ll, g = self.loglik_grad(v, cv)
+            return ll, 0.0, g
+        ll, mu = self.profile_loglik(cv, v, mean=mean)
+        return ll, mu, self.loglik_grad(v - mu, cv)[1]
+
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
-            method: str = "Nelder-Mead", maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None):
+            method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
+            gradient: bool = False):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
         latent model); ``nu`` the (fixed) smoothness of the ``matern`` kind, default ``cov``'s.
         Sets ``cov`` to the estimate and returns a dict with theta, mu, loglik and the
-        optimizer's evaluation count."""
+        optimizer's evaluation count.  ``method`` defaults to Nelder-Mead.
+
+        ``gradient=True``: the objective also returns the analytic gradient
+        (:meth:`profile_loglik_grad`, d/d log theta = theta d/d theta) and scipy runs with ``jac=True``,
+        L-BFGS-B by default; fused kinds other than ``matern`` and 1 <= m <= 32 only.  The result gains
+        ``n_grad_evals``."""
         from scipy.optimize import minimize
+
+        if method is None:
+            method = "L-BFGS-B" if gradient else "Nelder-Mead"
 
         base = self.cov if isinstance(self.cov, Covariance) else None
         kind = kind or (base.kind if base is not None else "exponential")
@@ -751,6 +804,30 @@ class NNGP:
                 best.update(ll=ll, mu=mu, theta=th)
             return -ll
 
+        n_grad, last_failed = [0], [False]
+
+        def obj_grad(z):
+            th = theta_of(z)
+            try:
+                ll, mu, g = self.profile_loglik_grad(Covariance(kind, *th, nu=nu), mean=mean)
+            except NNGPNumericalError:
+                # no gradient exists here: the zero one can end a line search early, so the failure is kept
+                # and shows in ``converged`` when the optimiser stops on such a point
+                last_failed[0] = True
+                return 1e300, np.zeros(len(z))
+            last_failed[0] = False
+            n_grad[0] += 1
+            if ll > best["ll"]:
+                best.update(ll=ll, mu=mu, theta=th)
+            return -ll, -np.array([th[k] * g[k] for k in range(len(z))])
+
+        if gradient:
+            self._grad_cov(Covariance(kind, *th0, nu=nu))  # refuse unsupported kinds / m before optimising
+            res = minimize(obj_grad, np.array(z0), jac=True, method=method, options={"maxiter": maxiter})
+            self.cov = Covariance(kind, *best["theta"], nu=nu)
+            self._B = self._F = None
+            return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
+                    "n_grad_evals": n_grad[0], "converged": bool(res.success) and not last_failed[0]}
         res = minimize(obj, np.array(z0), method=method, options={"maxiter": maxiter, "xatol": 1e-6,
                                                                   "fatol": 1e-9} if method == "Nelder-Mead"
                        else {"maxiter": maxiter})

@@ -80,6 +80,11 @@ def _register_fakes() -> None:
             return coords.new_empty((rows, m)), coords.new_empty((rows,)), coords.new_empty((4,))
         return coords.new_empty((0, m)), coords.new_empty((0,)), coords.new_empty((4,))
 
+    @fake("bf_grad")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
+        return (coords.new_empty((4,)), coords.new_empty((3,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, 3)))
+
     @fake("bf_sweep_out")
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, B, F, R, partials, workspace, algo, nu=-1.0,
           plan=None, plan_info=None, cert=None, cert_info=None):
