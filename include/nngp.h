@@ -13,7 +13,9 @@
  *     nngp_loglik_from_partials is a DEVICE pointer (hipMalloc / torch CUDA
  *     tensor memory); the caller owns every buffer.
  *   - `stream` is a hipStream_t (NULL = default stream).  All work is
- *     stream-ordered; no call synchronises the host, allocates, or frees.
+ *     stream-ordered; no call synchronises the host, allocates, or frees (the exceptions say so:
+ *     the setup calls nngp_pair_plan_build / nngp_nbr_cert_build / nngp_color_moral_graph_dev and
+ *     the solver nngp_latent_cg synchronise the stream).
  *   - Coordinates are fp64 (n_points, dim) row-major, dim = 1, 2 or 3 (the
  *     reference's KDTree takes ordinates of any dimension, nngp.py:55-61); they
  *     must be finite.  Neighbour sets are int32 (rows, m) row-major, padded with -1
@@ -85,7 +87,8 @@ const char *nngp_version(void);
  * Revision 4 (library 0.4.0): the pair plans are per wave (a new plan format, m <= 17) and their info
  * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan).
  * Added within revision 4 (nothing earlier moved): the gradient sweep nngp_bf_grad_workspace_bytes /
- * nngp_bf_grad. */
+ * nngp_bf_grad; the latent-field posterior nngp_precision_workspace_bytes / nngp_precision_apply /
+ * nngp_precision_sqrt_t_apply / nngp_latent_cg_workspace_bytes / nngp_latent_cg. */
 #define NNGP_ABI_VERSION 4
 int32_t nngp_abi_version(void);
 
@@ -488,6 +491,50 @@ size_t nngp_gibbs_stats_workspace_bytes(int64_t n, int32_t p);
 int nngp_gibbs_stats(int64_t n, const double *r, const double *Ft, const double *yres, const double *y,
                      const double *X, int32_t p, const double *w, const double *noise_w, double *out,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Latent-field posterior at fixed theta (S = T).  The reference keeps the latent state as ws / wt
+ * (pyNNGP/nngp.py:42-47) and only names a sampler for it (oneSample, nngp.py:98-101); for fixed
+ * (sigma2, phi, tau2) the posterior is Gaussian and explicit,
+ *   A = (I - B)^T (sigma2 F)^-1 (I - B) + diag(d),   d_i = h_i / tau2,   b = h (y - X beta) / tau2,
+ *   w | y, theta ~ N(A^-1 b, A^-1),
+ * with B (n, m) and F the unit-variance factors of nngp_bf_sweep (sigma2 = 1, tau2 = 0) and h_i the noise
+ * weight (0 at a location without an observation).  A is never assembled.  Geometry arguments of every
+ * call: nbr (n, m) and B (n, m) as nngp_bf_sweep's, off / rev_j / rev_k from nngp_reverse_neighbors of nbr,
+ * prep from nngp_gibbs_prepare of (B, F) (nngp_gibbs_prep_bytes(n, m) bytes, 256-B aligned); 1 <= m <=
+ * NNGP_MAX_M, sigma2 > 0; d: NULL (the prior precision alone) or (n,) non-negative.  rev_k is accepted for
+ * symmetry with the Gibbs calls and not read (prep already holds B in reverse-list order).
+ * nngp_precision_apply: out = A x, two stream-ordered launches without atomics: a gather over nbr
+ *   (t = (I - B) x scaled by 1 / (sigma2 F)), then a gather over the reverse lists ((I - B)^T t + d x).
+ *   Slots holding -1 contribute exactly 0.  Every sum has a fixed order that depends on m and the list's
+ *   length only, so out is bit-identical run to run.  workspace: nngp_precision_workspace_bytes(n) bytes,
+ *   256-B aligned; x and out must not alias.
+ * nngp_precision_sqrt_t_apply: out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2, the perturbation of exact
+ *   posterior draws: Cov(out) = A for standard normal z1, z2 (z2 may be NULL when d is).  Same workspace.
+ * nngp_latent_cg: Jacobi-preconditioned conjugate gradients for A x = b (M = diag(A) = d + (invF + P) /
+ *   sigma2, straight from prep), x: the start on entry, the solution on return.  Stops when
+ *   |r|^2 <= rtol^2 |b|^2 (r the recurrence residual) or after max_iter iterations; alpha and beta stay on
+ *   the device and every dot is a fixed-order fold of per-block records, so a solve is bit-reproducible.
+ *   A SOLVER CALL THAT SYNCHRONISES the stream once per chunk of check_every iterations (as the setup calls
+ *   nngp_pair_plan_build and nngp_nbr_cert_build do once): each chunk ends with one small device-to-host
+ *   copy.  info_host (HOST, 4 doubles): iterations done, converged (1; 0: max_iter reached; -1: breakdown,
+ *   p.Ap not above 0 or not finite, e.g. NaN in B), |r|^2, |b|^2 -- numerical outcomes are data, the
+ *   return code stays NNGP_OK.  0 < rtol < 1, max_iter >= 0, check_every >= 1; workspace:
+ *   nngp_latent_cg_workspace_bytes(n) bytes (0 for n < 0), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_precision_workspace_bytes(int64_t n);
+int nngp_precision_apply(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                         const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2, const double *d,
+                         const double *x, double *out, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_precision_sqrt_t_apply(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2,
+                                const double *d, const double *z1, const double *z2, double *out, void *workspace,
+                                size_t workspace_bytes, void *stream);
+size_t nngp_latent_cg_workspace_bytes(int64_t n);
+int nngp_latent_cg(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                   const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2, const double *d,
+                   const double *b, double *x, double rtol, int64_t max_iter, int32_t check_every, double *info_host,
+                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident

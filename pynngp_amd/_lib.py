@@ -69,6 +69,11 @@ SYMBOLS = (
     "nngp_bf_sweep_cert",
     "nngp_bf_grad_workspace_bytes",
     "nngp_bf_grad",
+    "nngp_precision_workspace_bytes",
+    "nngp_precision_apply",
+    "nngp_precision_sqrt_t_apply",
+    "nngp_latent_cg_workspace_bytes",
+    "nngp_latent_cg",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -206,6 +211,16 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_sweep_cert.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, SZ, I32, P,
                                        SZ, P, P]
     lib.nngp_bf_sweep_cert.restype = ctypes.c_int
+    lib.nngp_precision_workspace_bytes.argtypes = [I64]
+    lib.nngp_precision_workspace_bytes.restype = SZ
+    lib.nngp_precision_apply.argtypes = [P, P, P, P, P, P, I64, I32, D, P, P, P, P, SZ, P]
+    lib.nngp_precision_apply.restype = ctypes.c_int
+    lib.nngp_precision_sqrt_t_apply.argtypes = [P, P, P, P, P, P, I64, I32, D, P, P, P, P, P, SZ, P]
+    lib.nngp_precision_sqrt_t_apply.restype = ctypes.c_int
+    lib.nngp_latent_cg_workspace_bytes.argtypes = [I64]
+    lib.nngp_latent_cg_workspace_bytes.restype = SZ
+    lib.nngp_latent_cg.argtypes = [P, P, P, P, P, P, I64, I32, D, P, P, P, D, I64, I32, P, P, SZ, P]
+    lib.nngp_latent_cg.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1107,3 +1122,89 @@ def gibbs_stats(r: torch.Tensor, Ft: torch.Tensor, yres: torch.Tensor, y: torch.
     _check(lib.nngp_gibbs_stats(n, _ptr(r), _ptr(Ft), _ptr(yres), _ptr(y), _ptr(X), p, _ptr(w), _ptr(noise_w), _ptr(out),
                                 _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_gibbs_stats")
     return out
+
+
+# ---------------------------------------------------------------------------- latent-field posterior
+def _latent_geometry(nbr, B, off, rev_j, rev_k, prep, *vectors):
+    """Shape / dtype checks of the operator's arguments (raw pointers below: a short array must never reach a
+    kernel); returns (device, n, m)."""
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    n, m = nbr.shape
+    if not 1 <= m <= MAX_M:
+        raise ValueError(f"m={m} outside [1, {MAX_M}]")
+    if B.dtype != torch.float64 or tuple(B.shape) != (n, m):
+        raise ValueError(f"B must be float64 ({n}, {m}), got {B.dtype} {tuple(B.shape)}")
+    if off.dtype != torch.int32 or tuple(off.shape) != (n + 1,):
+        raise ValueError(f"off must be int32 ({n + 1},)")
+    for name, t in (("rev_j", rev_j), ("rev_k", rev_k)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n * m:
+            raise ValueError(f"{name} must be int32 with at least n * m = {n * m} entries")
+    for t in vectors:
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (n,)):
+            raise ValueError(f"vectors must be float64 ({n},), got {t.dtype} {tuple(t.shape)}")
+    for t in (nbr, B, off, rev_j, rev_k, prep) + tuple(vectors):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("the operator's arguments must be contiguous")
+    dev = _require_gpu(nbr, B, off, rev_j, rev_k, prep, *vectors)
+    if prep.dtype != torch.uint8 or prep.numel() < load().nngp_gibbs_prep_bytes(n, m):
+        raise ValueError("prep must be the uint8 buffer of gibbs_prepare for these factors")
+    return dev, n, m
+
+
+def precision_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
+                    prep: torch.Tensor, sigma2: float, x: torch.Tensor, d: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = [(I - B)^T (sigma2 F)^-1 (I - B) + diag(d)] x (nngp_precision_apply): ``prep`` from
+    :func:`gibbs_prepare` of the unit-variance (B, F), the reverse lists from :func:`reverse_neighbors`;
+    ``d`` None = the prior precision alone.  Bit-reproducible; stream-ordered, no host synchronisation."""
+    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, x, d, out)
+    lib = load()
+    out = torch.empty_like(x) if out is None else out
+    need = lib.nngp_precision_workspace_bytes(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_precision_apply(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
+                                    float(sigma2), _ptr(d), _ptr(x), _ptr(out), _ptr(workspace), workspace.numel(),
+                                    _stream(dev)), "nngp_precision_apply")
+    return out
+
+
+def precision_sqrt_t_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
+                           rev_k: torch.Tensor, prep: torch.Tensor, sigma2: float, z1: torch.Tensor,
+                           z2: Optional[torch.Tensor] = None, d: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2 (nngp_precision_sqrt_t_apply): Cov(out) = A for standard
+    normal z1, z2 -- the perturbation of exact posterior draws."""
+    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, z1, z2, d, out)
+    if d is not None and z2 is None:
+        raise ValueError("z2 is needed when d is given")
+    lib = load()
+    out = torch.empty_like(z1) if out is None else out
+    need = lib.nngp_precision_workspace_bytes(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_precision_sqrt_t_apply(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
+                                           float(sigma2), _ptr(d), _ptr(z1), _ptr(z2), _ptr(out), _ptr(workspace),
+                                           workspace.numel(), _stream(dev)), "nngp_precision_sqrt_t_apply")
+    return out
+
+
+def latent_cg(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
+              prep: torch.Tensor, sigma2: float, b: torch.Tensor, x: torch.Tensor, d: Optional[torch.Tensor] = None,
+              rtol: float = 1e-8, max_iter: int = 1000, check_every: int = 8,
+              workspace: Optional[torch.Tensor] = None):
+    """Jacobi-preconditioned CG for A x = b in place on ``x`` (its start; nngp_latent_cg).  Returns
+    ``(x, info)``, info = [iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2] as host floats.
+    Synchronises the stream once per ``check_every`` iterations."""
+    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, b, x, d)
+    lib = load()
+    need = lib.nngp_latent_cg_workspace_bytes(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    info = (ctypes.c_double * 4)()
+    _check(lib.nngp_latent_cg(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m, float(sigma2),
+                              _ptr(d), _ptr(b), _ptr(x), float(rtol), int(max_iter), int(check_every), info,
+                              _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_latent_cg")
+    return x, [float(v) for v in info]

@@ -11,6 +11,7 @@
 #include "bf_pairb.h"
 #include "nbr_cert.h"
 #include "bf_grad.h"
+#include "latent.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -763,6 +764,85 @@ int nngp_gibbs_stats(int64_t n, const double* r, const double* Ft, const double*
     hipError_t e = nngp::gibbs_stats_launch(n, r, Ft, yres, y, X, p, w, noise_w, out, workspace,
                                               (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gibbs_stats launch");
+    return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- latent-field posterior (latent.hip)
+// the checks the three calls share, before any launch; fills g
+static int latent_common(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                         const void* prep, int64_t n, int32_t m, double sigma2, const double* d, void* workspace,
+                         size_t workspace_bytes, size_t need, nngp::LatentGeom* g) {
+    if (nbr == nullptr || B == nullptr || off == nullptr || rev_j == nullptr || prep == nullptr ||
+        workspace == nullptr)
+        return fail(NNGP_EINVAL, "nbr, B, off, rev_j, prep and workspace must be non-null");
+    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
+        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
+    if (((uintptr_t)workspace & 255) != 0 || ((uintptr_t)prep & 255) != 0)
+        return fail(NNGP_EINVAL, "workspace and prep must be 256-byte aligned");
+    if (workspace_bytes < need)
+        return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    *g = nngp::LatentGeom{nbr, B, off, rev_j, nngp::latent_prep_view(prep, n, m), n, m, sigma2, d};
+    return NNGP_OK;
+}
+
+size_t nngp_precision_workspace_bytes(int64_t n) { return n < 0 ? 0 : nngp::latent_apply_workspace_bytes(n); }
+
+int nngp_precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                         const double* x, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;  // prep holds B in reverse-list order already
+    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_precision_workspace_bytes(n), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_apply_launch(g, x, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_apply launch");
+    return NNGP_OK;
+}
+
+int nngp_precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                                const double* d, const double* z1, const double* z2, double* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
+        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
+    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_precision_workspace_bytes(n), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_sqrt_t_apply_launch(g, z1, z2, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_sqrt_t_apply launch");
+    return NNGP_OK;
+}
+
+size_t nngp_latent_cg_workspace_bytes(int64_t n) { return n < 0 ? 0 : nngp::latent_cg_workspace_bytes(n); }
+
+int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                   const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                   const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every, double* info_host,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (b == nullptr || x == nullptr || info_host == nullptr)
+        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
+    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
+    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
+    if (max_iter < 0 || check_every < 1)
+        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
+                    check_every);
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_latent_cg_workspace_bytes(n), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_cg_run(g, b, x, rtol, max_iter, check_every, info_host, workspace,
+                                       (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "latent_cg");
     return NNGP_OK;
 }
 

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "nngp_internal.h"
+#include "latent.h"
 
 namespace nngp {
 
@@ -419,6 +420,12 @@ static GibbsPrep prep_layout(void* prep, int64_t n, int m) {
 
 size_t gibbs_prep_bytes(int64_t n, int m) {
     return 2 * align256((size_t)(n * m) * 8) + 2 * align256((size_t)n * 8);
+}
+
+// the arrays the latent-field operator reads (latent.hip), from the one layout above
+LatentPrep latent_prep_view(const void* prep, int64_t n, int m) {
+    const GibbsPrep g = prep_layout(const_cast<void*>(prep), n, m);
+    return LatentPrep{g.Brev, g.P, g.invF};
 }
 
 hipError_t gibbs_prepare_range_launch(const double* B, const double* Ft, const int32_t* off, const int32_t* rev_j,

@@ -1,0 +1,43 @@
+// Latent-field posterior at fixed theta (latent.hip): the precision operator
+//   A = (I - B)^T (sigma2 F)^-1 (I - B) + diag(d)
+// applied matrix-free from the Gibbs `prep` buffer, and a Jacobi-preconditioned CG on it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace nngp {
+
+// the arrays of a nngp_gibbs_prepare buffer the operator reads (gibbs.hip owns the layout)
+struct LatentPrep {
+    const double* Brev;  // B_{j,i} per reverse entry
+    const double* P;     // sum_e B_{j,i}^2 / F_j per location
+    const double* invF;  // 1 / F_i
+};
+LatentPrep latent_prep_view(const void* prep, int64_t n, int m);
+
+struct LatentGeom {
+    const int32_t* nbr;    // (n, m), -1 padded
+    const double* B;       // (n, m)
+    const int32_t* off;    // (n + 1,) reverse lists (nngp_reverse_neighbors)
+    const int32_t* rev_j;  // child row per reverse entry
+    LatentPrep prep;
+    int64_t n;
+    int m;
+    double sigma2;
+    const double* d;  // (n,) diagonal term, or null
+};
+
+size_t latent_apply_workspace_bytes(int64_t n);
+size_t latent_cg_workspace_bytes(int64_t n);
+// out = A x (workspace: latent_apply_workspace_bytes(n))
+hipError_t latent_apply_launch(const LatentGeom& g, const double* x, double* out, void* workspace, hipStream_t s);
+// out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2
+hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s);
+// Jacobi-PCG for A x = b from the start in x; info_host: iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2.
+// Synchronises the stream once per chunk of check_every iterations.
+hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s);
+
+}  // namespace nngp

@@ -1,0 +1,428 @@
+// Latent-field posterior at fixed theta: w | y, theta ~ N(A^-1 b, A^-1) with
+//   A = (I - B)^T (sigma2 F)^-1 (I - B) + diag(d),   d = h / tau2,   b = h (y - X beta) / tau2
+// (B, F the unit-variance factors of nngp_bf_sweep; oracle/nngp_gibbs_oracle.py::dag_posterior).  A is
+// never assembled.  The reference keeps the latent state as ws / wt (pyNNGP/nngp.py:42-47) and has no
+// estimator for it; this is the deterministic one next to the Gibbs sampler (gibbs.hip), whose reverse
+// lists and `prep` buffer (Brev, P, invF) it reuses.
+//
+// One product with A is two stream-ordered phases, no atomics:
+//   row phase     t_i   = (x_i - sum_s B[i,s] x[nbr[i,s]]) invF_i / sigma2       (gather over nbr)
+//   column phase  out_i = t_i - sum_{e in [off_i, off_i+1)} Brev[e] t[rev_j[e]] + d_i x_i   (gather over the
+//                 reverse list, in its stored order)
+// Every sum has a fixed order that depends on (m, the list's length) only: a row's slots and a short
+// list's entries are dealt lane-strided over an aligned lane group and folded by a fixed xor butterfly; a
+// list longer than kLongList is summed by the whole 256-thread block (thread-strided, the fixed wave
+// butterfly, then the four wave sums in order).  Which block or tile a location lands in changes nothing,
+// so the result is bit-identical run to run and independent of the grid.
+//
+// The CG keeps alpha and beta on the device.  Its dots go through per-block records folded in a fixed
+// order by every block that needs the scalar (the same bits in each), so a solve is bit-reproducible.
+#include "latent.h"
+
+#include <math.h>
+
+#include "nngp_internal.h"
+
+namespace nngp {
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kColLanes = 16;                    // lanes per location in the column phase
+constexpr int kColRows = kBlock / kColLanes;     // locations per tile
+constexpr int kLongList = 32 * kColLanes;        // a lane group's budget; longer lists go to the block
+constexpr int kMaxTileBlocks = 2048;             // persistent grid of the operator phases (= p.q records)
+constexpr int kMaxVecBlocks = 1024;              // grid of the CG's vector kernels (= records per dot)
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// sum over an aligned group of G lanes, every lane getting the bits of the descending xor butterfly
+template <int G>
+__device__ __forceinline__ double lane_group_sum(double v) {
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// fixed-order sum over the 256-thread block, the same bits in every thread; all threads call it
+__device__ __forceinline__ double block_sum(double v, double* sh4) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
+}
+
+// fold of n_rec per-block records: thread-strided partial sums, then block_sum.  Every block that folds the
+// same records gets the same bits.
+__device__ __forceinline__ double fold_records(const double* __restrict__ rec, int n_rec, double* sh4) {
+    double a = 0.0;
+    for (int k = threadIdx.x; k < n_rec; k += kBlock) a += rec[k];
+    return block_sum(a, sh4);
+}
+
+// the contiguous run of tiles a block of a persistent grid owns (XCD-contiguous: neighbours meet in one L2)
+__device__ __forceinline__ void tile_range(int64_t n_tiles, int64_t* lo, int64_t* hi) {
+    const int64_t nb = gridDim.x, lb = xcd_logical_block(blockIdx.x, nb);
+    *lo = lb * n_tiles / nb;
+    *hi = (lb + 1) * n_tiles / nb;
+}
+
+// CG state words (doubles) at the end of the workspace
+enum { kRz0 = 0, kRz1 = 1, kRr = 2, kBb = 3, kTol2 = 4, kAlpha = 5, kBeta = 6, kIter = 7, kStatus = 8, kFlag0 = 9,
+       kFlag1 = 10, kBrk = 11, kStateWords = 32 };
+
+// ---------------------------------------------------------------- row phase
+// G lanes per location (G = 4, 8 or 16 by m alone); lane l takes slots l, l + G, ...: the nbr and B rows are
+// read coalesced.  stop: null, or a device word that makes the launch a no-op when non-zero (a finished CG).
+template <int G>
+__global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __restrict__ nbr,
+                                                            const double* __restrict__ B,
+                                                            const double* __restrict__ invF,
+                                                            const double* __restrict__ x, double* __restrict__ t,
+                                                            int64_t n, int m, double inv_s2,
+                                                            const double* __restrict__ stop) {
+    if (stop != nullptr && *stop != 0.0) return;
+    constexpr int kRows = kBlock / G;
+    const int g = threadIdx.x / G, l = threadIdx.x % G;
+    int64_t lo, hi;
+    tile_range((n + kRows - 1) / kRows, &lo, &hi);
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t i = tile * kRows + g;
+        double acc = 0.0;
+        if (i < n) {
+            const int32_t* nb = nbr + i * m;
+            const double* bb = B + i * m;
+            for (int s = l; s < m; s += G) {
+                const int32_t j = nb[s];
+                if (j >= 0 && (int64_t)j < n) acc = fma(bb[s], x[j], acc);  // a slot without a point: exactly 0
+            }
+        }
+        acc = lane_group_sum<G>(acc);
+        if (i < n && l == 0) t[i] = (x[i] - acc) * (invF[i] * inv_s2);
+    }
+}
+
+// u_i = z1_i sqrt(invF_i / sigma2): the column phase's input for the square-root operator
+__global__ __launch_bounds__(kBlock) void latent_scale_kernel(const double* __restrict__ invF,
+                                                              const double* __restrict__ z1, double* __restrict__ u,
+                                                              int64_t n, double inv_s2) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        u[i] = z1[i] * sqrt(invF[i] * inv_s2);
+}
+
+// ---------------------------------------------------------------- column phase
+// out_i = t_i - sum_e Brev[e] t[rev_j[e]] + dd_i x_i, dd = d (SQRT: sqrt(d)); d null: no diagonal term.
+// rec: null, or the block's record of sum_i x_i out_i (the CG's p.q) at rec[blockIdx.x].
+template <bool SQRT>
+__global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __restrict__ off,
+                                                            const int32_t* __restrict__ rev_j,
+                                                            const double* __restrict__ Brev,
+                                                            const double* __restrict__ t,
+                                                            const double* __restrict__ d,
+                                                            const double* __restrict__ x, double* __restrict__ out,
+                                                            int64_t n, double* __restrict__ rec,
+                                                            const double* __restrict__ stop) {
+    __shared__ int32_t sh_e0[kColRows], sh_e1[kColRows];
+    __shared__ double sh4[4];
+    if (stop != nullptr && *stop != 0.0) return;
+    const int g = threadIdx.x / kColLanes, l = threadIdx.x % kColLanes;
+    int64_t lo, hi;
+    tile_range((n + kColRows - 1) / kColRows, &lo, &hi);
+    double dot = 0.0;
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t i = tile * kColRows + g;
+        const bool live = i < n;
+        const int32_t e0 = live ? off[i] : 0, e1 = live ? off[i + 1] : 0;
+        const bool is_long = e1 - e0 > kLongList;
+        double acc = 0.0;
+        if (!is_long) {
+            for (int32_t e = e0 + l; e < e1; e += kColLanes) {
+                const int32_t j = rev_j[e];
+                if ((uint32_t)j < (uint64_t)n) acc = fma(Brev[e], t[j], acc);
+            }
+        }
+        acc = lane_group_sum<kColLanes>(acc);
+        if (__syncthreads_or(is_long)) {  // block-uniform; rare (hubs)
+            if (l == 0) {
+                sh_e0[g] = e0;
+                sh_e1[g] = is_long ? e1 : e0;
+            }
+            __syncthreads();
+            for (int k = 0; k < kColRows; ++k) {
+                const int32_t a0 = sh_e0[k], a1 = sh_e1[k];
+                if (a1 <= a0) continue;  // block-uniform
+                double s = 0.0;
+                for (int32_t e = a0 + (int32_t)threadIdx.x; e < a1; e += kBlock) {
+                    const int32_t j = rev_j[e];
+                    if ((uint32_t)j < (uint64_t)n) s = fma(Brev[e], t[j], s);
+                }
+                s = block_sum(s, sh4);
+                if (g == k) acc = s;
+            }
+            __syncthreads();
+        }
+        if (live && l == 0) {
+            double o = t[i] - acc;
+            const double xi = (d != nullptr || rec != nullptr) && x != nullptr ? x[i] : 0.0;
+            if (d != nullptr) o = fma(SQRT ? sqrt(d[i]) : d[i], xi, o);
+            out[i] = o;
+            dot = fma(xi, o, dot);
+        }
+    }
+    if (rec != nullptr) {
+        dot = block_sum(dot, sh4);
+        if (threadIdx.x == 0) rec[blockIdx.x] = dot;
+    }
+}
+
+// ---------------------------------------------------------------- CG vector kernels
+// start: M^-1 = 1 / (d + (invF + P) / sigma2), r = b - A x0 (q holds A x0), z = M^-1 r, p = z; records of
+// r.z, r.r and b.b
+__global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(int64_t n, const double* __restrict__ b,
+                                                                const double* __restrict__ q,
+                                                                const double* __restrict__ d,
+                                                                const double* __restrict__ invF,
+                                                                const double* __restrict__ P, double inv_s2,
+                                                                double* __restrict__ r, double* __restrict__ z,
+                                                                double* __restrict__ p, double* __restrict__ Minv,
+                                                                double* __restrict__ rec) {
+    __shared__ double sh4[4];
+    double rz = 0.0, rr = 0.0, bb = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double diag = (d != nullptr ? d[i] : 0.0) + (invF[i] + P[i]) * inv_s2;
+        const double mi = 1.0 / diag;
+        const double bi = b[i], ri = bi - q[i], zi = mi * ri;
+        Minv[i] = mi;
+        r[i] = ri;
+        z[i] = zi;
+        p[i] = zi;
+        rz = fma(ri, zi, rz);
+        rr = fma(ri, ri, rr);
+        bb = fma(bi, bi, bb);
+    }
+    rz = block_sum(rz, sh4);
+    rr = block_sum(rr, sh4);
+    bb = block_sum(bb, sh4);
+    if (threadIdx.x == 0) {
+        rec[blockIdx.x] = rz;
+        rec[kMaxVecBlocks + blockIdx.x] = rr;
+        rec[2 * kMaxVecBlocks + blockIdx.x] = bb;
+    }
+}
+
+// one block: fold the start's records into the state
+__global__ __launch_bounds__(kBlock) void latent_cg_start_kernel(const double* __restrict__ rec, int n_rec,
+                                                                 double rtol, double* __restrict__ st) {
+    __shared__ double sh4[4];
+    const double rz = fold_records(rec, n_rec, sh4);
+    const double rr = fold_records(rec + kMaxVecBlocks, n_rec, sh4);
+    const double bb = fold_records(rec + 2 * kMaxVecBlocks, n_rec, sh4);
+    if (threadIdx.x == 0) {
+        const double tol2 = rtol * rtol * bb;
+        const double done = rr <= tol2 ? 1.0 : 0.0;
+        st[kRz0] = rz;
+        st[kRz1] = 0.0;
+        st[kRr] = rr;
+        st[kBb] = bb;
+        st[kTol2] = tol2;
+        st[kAlpha] = st[kBeta] = 0.0;
+        st[kIter] = 0.0;
+        st[kStatus] = done;
+        st[kFlag0] = done;
+        st[kFlag1] = 0.0;
+        st[kBrk] = 0.0;
+    }
+}
+
+// iteration k, after q = A p and the p.q records: alpha = r.z / p.q (a breakdown -- p.q not above 0 or not
+// finite -- is flagged and nothing moves), x += alpha p, r -= alpha q, z = M^-1 r; records of r.z and r.r
+__global__ __launch_bounds__(kBlock) void latent_cg_update_kernel(int64_t n, int64_t k, const double* __restrict__ pq_rec,
+                                                                  int n_pq, const double* __restrict__ p,
+                                                                  const double* __restrict__ q,
+                                                                  const double* __restrict__ Minv,
+                                                                  double* __restrict__ x, double* __restrict__ r,
+                                                                  double* __restrict__ z, double* __restrict__ rec,
+                                                                  double* __restrict__ st) {
+    __shared__ double sh4[4];
+    if (st[kFlag0 + (k & 1)] != 0.0) return;
+    const double pq = fold_records(pq_rec, n_pq, sh4);
+    if (!(pq > 0.0) || pq > 1.7976931348623157e308) {  // not above 0, NaN or +inf
+        if (blockIdx.x == 0 && threadIdx.x == 0) st[kBrk] = 1.0;
+        return;
+    }
+    const double alpha = st[kRz0 + (k & 1)] / pq;
+    double rz = 0.0, rr = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        x[i] = fma(alpha, p[i], x[i]);
+        const double ri = fma(-alpha, q[i], r[i]);
+        const double zi = Minv[i] * ri;
+        r[i] = ri;
+        z[i] = zi;
+        rz = fma(ri, zi, rz);
+        rr = fma(ri, ri, rr);
+    }
+    rz = block_sum(rz, sh4);
+    rr = block_sum(rr, sh4);
+    if (threadIdx.x == 0) {
+        rec[blockIdx.x] = rz;
+        rec[kMaxVecBlocks + blockIdx.x] = rr;
+        if (blockIdx.x == 0) st[kAlpha] = alpha;
+    }
+}
+
+// iteration k, last launch: beta = r.z' / r.z, p = z + beta p; block 0 moves the state on (the scalars of
+// iteration k + 1 live in the other slot, so no block reads a word this launch writes)
+__global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, int64_t k, const double* __restrict__ rec,
+                                                                     int n_rec, const double* __restrict__ z,
+                                                                     double* __restrict__ p, double* __restrict__ st) {
+    __shared__ double sh4[4];
+    const int cur = (int)(k & 1), nxt = cur ^ 1;
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    const double flag = st[kFlag0 + cur];
+    if (flag != 0.0) {
+        if (lead) st[kFlag0 + nxt] = flag;
+        return;
+    }
+    if (st[kBrk] != 0.0) {
+        if (lead) st[kFlag0 + nxt] = st[kStatus] = -1.0;
+        return;
+    }
+    const double rz = fold_records(rec, n_rec, sh4);
+    const double rr = fold_records(rec + kMaxVecBlocks, n_rec, sh4);
+    const double beta = rz / st[kRz0 + cur];
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        p[i] = fma(beta, p[i], z[i]);
+    if (lead) {
+        const double done = rr <= st[kTol2] ? 1.0 : 0.0;
+        st[kRz0 + nxt] = rz;
+        st[kRr] = rr;
+        st[kBeta] = beta;
+        st[kIter] = (double)(k + 1);
+        st[kFlag0 + nxt] = st[kStatus] = done;
+    }
+}
+
+int tile_blocks(int64_t n, int rows_per_tile) {
+    const int64_t tiles = (n + rows_per_tile - 1) / rows_per_tile;
+    return (int)(tiles < kMaxTileBlocks ? tiles : kMaxTileBlocks);
+}
+
+int vec_blocks(int64_t n) {
+    const int64_t b = (n + kBlock - 1) / kBlock;
+    return (int)(b < kMaxVecBlocks ? b : kMaxVecBlocks);
+}
+
+void row_launch(const LatentGeom& g, const double* x, double* t, const double* stop, hipStream_t s) {
+    const double inv_s2 = 1.0 / g.sigma2;
+    // lanes per location from m alone (part of the fixed summation order)
+    if (g.m <= 4)
+        hipLaunchKernelGGL(latent_row_kernel<4>, dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s, g.nbr, g.B,
+                           g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
+    else if (g.m <= 8)
+        hipLaunchKernelGGL(latent_row_kernel<8>, dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s, g.nbr, g.B,
+                           g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
+    else
+        hipLaunchKernelGGL(latent_row_kernel<16>, dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0, s, g.nbr,
+                           g.B, g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
+}
+
+// the CG workspace: six vectors, the records, the state
+struct CgLayout {
+    double *t, *r, *z, *p, *q, *Minv, *rec, *pq_rec, *st;
+};
+
+CgLayout cg_layout(void* workspace, int64_t n) {
+    char* w = (char*)workspace;
+    const size_t v = align256((size_t)n * 8);
+    CgLayout L;
+    L.t = (double*)w;
+    L.r = (double*)(w + v);
+    L.z = (double*)(w + 2 * v);
+    L.p = (double*)(w + 3 * v);
+    L.q = (double*)(w + 4 * v);
+    L.Minv = (double*)(w + 5 * v);
+    w += 6 * v;
+    L.rec = (double*)w;
+    w += align256((size_t)3 * kMaxVecBlocks * 8);
+    L.pq_rec = (double*)w;
+    w += align256((size_t)kMaxTileBlocks * 8);
+    L.st = (double*)w;
+    return L;
+}
+
+}  // namespace
+
+size_t latent_apply_workspace_bytes(int64_t n) { return align256((size_t)(n > 0 ? n : 1) * 8); }
+
+size_t latent_cg_workspace_bytes(int64_t n) {
+    return 6 * align256((size_t)n * 8) + align256((size_t)3 * kMaxVecBlocks * 8) +
+           align256((size_t)kMaxTileBlocks * 8) + align256((size_t)kStateWords * 8);
+}
+
+hipError_t latent_apply_launch(const LatentGeom& g, const double* x, double* out, void* workspace, hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* t = (double*)workspace;
+    row_launch(g, x, t, nullptr, s);
+    hipLaunchKernelGGL(latent_col_kernel<false>, dim3(tile_blocks(g.n, kColRows)), dim3(kBlock), 0, s, g.off, g.rev_j,
+                       g.prep.Brev, t, g.d, x, out, g.n, (double*)nullptr, (const double*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* u = (double*)workspace;
+    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n,
+                       1.0 / g.sigma2);
+    hipLaunchKernelGGL(latent_col_kernel<true>, dim3(tile_blocks(g.n, kColRows)), dim3(kBlock), 0, s, g.off, g.rev_j,
+                       g.prep.Brev, u, g.d, z2, out, g.n, (double*)nullptr, (const double*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s) {
+    info_host[0] = 0.0;
+    info_host[1] = 1.0;
+    info_host[2] = info_host[3] = 0.0;
+    if (g.n == 0) return hipSuccess;
+    const CgLayout L = cg_layout(workspace, g.n);
+    const int nv = vec_blocks(g.n), nt = tile_blocks(g.n, kColRows);
+    const double inv_s2 = 1.0 / g.sigma2;
+    hipError_t e;
+    // r = b - A x0, z = M^-1 r, p = z
+    row_launch(g, x, L.t, nullptr, s);
+    hipLaunchKernelGGL(latent_col_kernel<false>, dim3(nt), dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev, L.t, g.d,
+                       (const double*)x, L.q, g.n, (double*)nullptr, (const double*)nullptr);
+    hipLaunchKernelGGL(latent_cg_init_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, b, (const double*)L.q, g.d,
+                       g.prep.invF, g.prep.P, inv_s2, L.r, L.z, L.p, L.Minv, L.rec);
+    hipLaunchKernelGGL(latent_cg_start_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, rtol, L.st);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    double st[kStateWords];
+    int64_t k = 0;
+    for (;;) {
+        // one chunk: no host synchronisation inside; a finished solve turns the remaining launches into no-ops
+        for (int c = 0; c < check_every && k < max_iter; ++c, ++k) {
+            const double* stop = L.st + kFlag0 + (k & 1);
+            row_launch(g, L.p, L.t, stop, s);
+            hipLaunchKernelGGL(latent_col_kernel<false>, dim3(nt), dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev,
+                               (const double*)L.t, g.d, (const double*)L.p, L.q, g.n, L.pq_rec, stop);
+            hipLaunchKernelGGL(latent_cg_update_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, k,
+                               (const double*)L.pq_rec, nt, (const double*)L.p, (const double*)L.q,
+                               (const double*)L.Minv, x, L.r, L.z, L.rec, L.st);
+            hipLaunchKernelGGL(latent_cg_direction_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, k,
+                               (const double*)L.rec, nv, (const double*)L.z, L.p, L.st);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(st, L.st, sizeof st, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        if (st[kStatus] != 0.0 || k >= max_iter) break;
+    }
+    info_host[0] = st[kIter];
+    info_host[1] = st[kStatus];
+    info_host[2] = st[kRr];
+    info_host[3] = st[kBb];
+    return hipSuccess;
+}
+
+}  // namespace nngp

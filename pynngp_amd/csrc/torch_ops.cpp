@@ -334,9 +334,81 @@ void combine_partials_out(const at::Tensor& gathered, const at::Tensor& out) {
              "nngp_combine_partials_batch");
 }
 
+// ---------------------------------------------------------------- latent-field posterior
+// the shared argument checks of precision_apply / latent_cg (raw pointers below: every length is checked)
+void check_latent(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off, const at::Tensor& rev_j,
+                  const at::Tensor& rev_k, const at::Tensor& prep) {
+    TORCH_CHECK(nbr.is_cuda(), "nbr must be a ROCm GPU tensor (there is no CPU fallback)");
+    check_nbr(nbr, nbr);
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    TORCH_CHECK(m >= 1 && m <= NNGP_MAX_M, "m=", m, " outside [1, ", NNGP_MAX_M, "]");
+    check_f64(B, {n, m}, nbr, "B");
+    TORCH_CHECK(off.scalar_type() == at::kInt && off.dim() == 1 && off.size(0) == n + 1 && off.is_contiguous(),
+                "off must be a contiguous int32 (n + 1,) tensor");
+    check_same_device(nbr, off, "off");
+    for (const at::Tensor* t : {&rev_j, &rev_k}) {
+        TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) >= n * m && t->is_contiguous(),
+                    "rev_j / rev_k must be contiguous int32 tensors of at least n * m entries");
+        check_same_device(nbr, *t, "rev_j / rev_k");
+    }
+    TORCH_CHECK(prep.scalar_type() == at::kByte && prep.is_contiguous() &&
+                    (size_t)prep.numel() >= nngp_gibbs_prep_bytes(n, (int32_t)m),
+                "prep must be the contiguous uint8 buffer of nngp_gibbs_prepare for these factors");
+    check_same_device(nbr, prep, "prep");
+}
+
+// out = [(I - B)^T (sigma2 F)^-1 (I - B) + diag(d)] x (nngp_precision_apply)
+at::Tensor precision_apply(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off, const at::Tensor& rev_j,
+                           const at::Tensor& rev_k, const at::Tensor& prep, double sigma2,
+                           const c10::optional<at::Tensor>& d, const at::Tensor& x) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(d, {n}, nbr, "d");
+    check_f64(x, {n}, nbr, "x");
+    auto out = at::empty_like(x);
+    auto ws = at::empty({(int64_t)nngp_precision_workspace_bytes(n)}, nbr.options().dtype(at::kByte));
+    check_rc(nngp_precision_apply(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                                  rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), n, (int32_t)m,
+                                  sigma2, ptr<double>(d), x.data_ptr<double>(), out.data_ptr<double>(), ws.data_ptr(),
+                                  (size_t)ws.nbytes(), stream(nbr)),
+             "nngp_precision_apply");
+    return out;
+}
+
+// Jacobi-PCG for A x = b (nngp_latent_cg; synchronises once per check_every iterations): (x, info), info a
+// CPU float64 (4,): iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2
+std::tuple<at::Tensor, at::Tensor> latent_cg(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off,
+                                             const at::Tensor& rev_j, const at::Tensor& rev_k, const at::Tensor& prep,
+                                             double sigma2, const c10::optional<at::Tensor>& d, const at::Tensor& b,
+                                             const c10::optional<at::Tensor>& x0, double rtol, int64_t max_iter,
+                                             int64_t check_every) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(d, {n}, nbr, "d");
+    check_f64(b, {n}, nbr, "b");
+    check_f64(x0, {n}, nbr, "x0");
+    at::Tensor x = x0.has_value() ? x0->clone() : at::zeros_like(b);
+    auto info = at::empty({4}, at::TensorOptions().dtype(at::kDouble));
+    auto ws = at::empty({(int64_t)nngp_latent_cg_workspace_bytes(n)}, nbr.options().dtype(at::kByte));
+    check_rc(nngp_latent_cg(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                            rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), n, (int32_t)m, sigma2,
+                            ptr<double>(d), b.data_ptr<double>(), x.data_ptr<double>(), rtol, max_iter,
+                            (int32_t)check_every, info.data_ptr<double>(), ws.data_ptr(), (size_t)ws.nbytes(),
+                            stream(nbr)),
+             "nngp_latent_cg");
+    return {x, info};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
+    m.def("precision_apply(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
+          "Tensor? d, Tensor x) -> Tensor");
+    m.def("latent_cg(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
+          "Tensor? d, Tensor b, Tensor? x0=None, float rtol=1e-08, int max_iter=1000, int check_every=8) -> "
+          "(Tensor, Tensor)");
     m.def("knn_prior(Tensor coords, int m, int q0, int q1) -> Tensor");
     m.def("knn_prior_rows(Tensor coords, int m, Tensor rows) -> Tensor");
     m.def("knn_query(Tensor ref, Tensor query, int k) -> Tensor");
@@ -368,4 +440,6 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("pair_plan", &pair_plan);
     m.impl("nbr_cert", &nbr_cert);
     m.impl("combine_partials_out", &combine_partials_out);
+    m.impl("precision_apply", &precision_apply);
+    m.impl("latent_cg", &latent_cg);
 }

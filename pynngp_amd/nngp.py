@@ -836,6 +836,49 @@ class NNGP:
         return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
                 "converged": bool(res.success)}
 
+    # -- latent field at fixed theta --------------------------------------------
+    def _latent_posterior(self, cov, mean: str):
+        """The :class:`pynngp_amd.LatentPosterior` of this instance's ``y`` / ``eps`` / neighbour sets at ``cov``
+        (kept between calls; a new theta of the same mean is one ``update``)."""
+        if not self._same_sets():
+            raise NotImplementedError("the latent posterior serves refType == 'S=T' (the field on the data "
+                                      f"locations), not {self.refType!r}")
+        if mean not in ("constant", "zero"):
+            raise ValueError("mean must be 'constant' or 'zero'")
+        from .latent import LatentPosterior
+
+        cv = self.cov if cov is None else cov
+        held = getattr(self, "_latent", None)
+        if held is not None and held[0] == mean and held[1] is self.nbr:
+            if held[2].cov != cv:
+                held[2].update(cv)
+            return held[2]
+        y = np.asarray(self.y, dtype=np.float64)
+        eps = None
+        if self.eps is not None:  # per-location measurement sigmas (nngp.py:9), as oneSample takes them
+            ev = np.asarray(self.eps, dtype=np.float64)
+            if ev.shape == y.shape and np.all(np.isfinite(ev)) and np.all(ev > 0):
+                eps = ev
+        X = np.ones((y.shape[0], 1)) if mean == "constant" and y.ndim == 1 else None
+        lp = LatentPosterior(self.t, y, cv, m=self.m, X=X, eps=eps, device=self.device, nbr=self.nbr)
+        self._latent = (mean, self.nbr, lp)
+        return lp
+
+    def latent_mean(self, cov: Optional[Covariance] = None, rtol: float = 1e-8, mean: str = "constant"):
+        """Posterior mean of the latent field w on the data locations at a fixed ``cov`` (default ``self.cov``,
+        e.g. after :meth:`fit`): ``(w_hat, beta_hat)`` from a conjugate-gradient solve with the NNGP posterior
+        precision (:class:`pynngp_amd.LatentPosterior`) -- the deterministic estimator of the reference's ``ws`` /
+        ``wt`` state (nngp.py:42-47).  ``mean="constant"`` estimates an intercept by GLS (as :meth:`fit`
+        profiles it out), ``"zero"`` takes y as centred.  NaN in ``y`` = unobserved; ``eps``, when it is one
+        positive sigma per location, scales the noise variance to tau2 eps_i^2.  refType 'S=T' only.
+        The latent mean at new locations is ``predict(values=w_hat, cov=cov.replace(tau2=0), query=...)``."""
+        return self._latent_posterior(cov, mean).mean(rtol=rtol)
+
+    def latent_sample(self, n: int, cov: Optional[Covariance] = None, seed: int = 0, mean: str = "constant"):
+        """``(n, N)`` exact draws of w | y, theta at a fixed ``cov`` (perturbation sampling on the same solver;
+        Philox normals keyed by ``seed``).  refType 'S=T' only; arguments as :meth:`latent_mean`."""
+        return self._latent_posterior(cov, mean).sample(n, seed=seed)
+
     def oneSample(self, seed: int = 0, X=None, **sampler_kw):
         """One Gibbs iteration of the response model y = X beta + w + eps: the reference's
         ``update_wt`` / ``update_ws`` / ``update_y_unobserved`` (nngp.py:98-101, which do not

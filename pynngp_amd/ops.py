@@ -21,6 +21,9 @@ for tracing.
     torch.ops.nngp.bf_cross(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0) -> (B, F, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.combine_partials_out(gathered, out) -> ()
+    torch.ops.nngp.precision_apply(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # latent-field precision
+    torch.ops.nngp.latent_cg(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
+                             check_every=8) -> (x, info)                 # Jacobi-PCG for A x = b (a solver call)
 
 ``kind`` / ``algo`` are the integer codes of include/nngp.h (:func:`kind_code`, :func:`algo_code`);
 ``nu`` is the smoothness of the ``matern`` kind (0 < nu <= 50; ignored by the other kinds).
@@ -111,6 +114,14 @@ def _register_fakes() -> None:
     @fake("combine_partials_out")
     def _(gathered, out):
         return None
+
+    @fake("precision_apply")
+    def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x):
+        return torch.empty_like(x)
+
+    @fake("latent_cg")
+    def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
+        raise RuntimeError("latent_cg is a solver call (it synchronises once per chunk of iterations): run it eagerly")
 
 
 def kind_code(kind: str) -> int:

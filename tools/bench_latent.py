@@ -1,0 +1,134 @@
+"""Latent-field posterior timing at BASELINE config 3's size (N = 1e6, m = 15, exponential, tau2 / sigma2 = 0.1).
+
+Measures, on one GPU and in one process:
+  * ms per application of the precision operator A = (I - B)^T (sigma2 F)^-1 (I - B) + diag(h / tau2)
+    (nngp_precision_apply: two gathers, nothing assembled) and its share of the HBM roofline -- bench.py's peak
+    constant and algorithmic-bytes convention; bytes counted per location: nbr 4m, B 8m, rev_j 4m, Brev 8m and
+    the vectors (row phase: x, invF, t; column phase: off, t, d, x, out);
+  * the same operator through stock PyTorch: (I - B) and its transpose as fp64 ``torch.sparse_csr_tensor``s,
+    two sparse products plus the diagonal scalings, after the same warm-up and with the same repeat count;
+  * the CG iteration count and the wall time of the posterior mean to rtol 1e-8, beside what a Gibbs estimate
+    of the same iteration count would cost at --gibbs-ms per sweep.
+Synthetic data as bench.py (uniform coordinates, standard-normal values, seed 0); prints one JSON line.
+    python tools/bench_latent.py [--n 1000000 --m 15 --reps 1000 --warmup 100]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from bench import HBM_PEAK, synth  # noqa: E402
+from pynngp_amd import Covariance, LatentPosterior, _lib  # noqa: E402
+
+
+def bytes_per_location(m):
+    # nbr 4m + B 8m (row phase), rev_j 4m + Brev 8m (column phase), vectors: x, invF, t | off, t, d, x, out
+    return 24 * m + 3 * 8 + (4 + 4 * 8)
+
+
+def timed(fn, warmup, reps):
+    """ms per call from device events around `reps` back-to-back calls, after `warmup` calls."""
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--m", type=int, default=15)
+    ap.add_argument("--sigma2", type=float, default=1.0)
+    ap.add_argument("--phi", type=float, default=30.0)
+    ap.add_argument("--tau2", type=float, default=0.1)
+    ap.add_argument("--rtol", type=float, default=1e-8)
+    ap.add_argument("--reps", type=int, default=1000)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--solves", type=int, default=5)
+    ap.add_argument("--gibbs-ms", type=float, default=0.80, help="ms per Gibbs iteration to compare against")
+    ap.add_argument("--no-baseline", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_latent needs a ROCm GPU (a timing without one says nothing)")
+    dev = torch.device("cuda", 0)
+    n, m = args.n, args.m
+    coords, y = synth(n)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    lp = LatentPosterior(coords, y, Covariance("exponential", args.sigma2, args.phi, args.tau2), m=m, device=dev)
+    torch.cuda.synchronize()
+    setup_s = time.perf_counter() - t0
+
+    geom = lp._geom()
+    x = torch.randn(n, dtype=torch.float64, device=dev, generator=torch.Generator(dev).manual_seed(1))
+    out = torch.empty_like(x)
+    op_ms = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws), args.warmup, args.reps)
+    bpl = bytes_per_location(m)
+    res = {"workload": f"latent posterior, N={n}, m={m}, exponential, sigma2={args.sigma2}, phi={args.phi}, "
+                       f"tau2={args.tau2}",
+           "setup_s": setup_s, "operator_ms": op_ms, "algorithmic_bytes_per_location": bpl,
+           "operator_GBps": bpl * n / (op_ms * 1e-3) / 1e9, "hbm_peak_GBps": HBM_PEAK / 1e9,
+           "operator_hbm_frac": bpl * n / (op_ms * 1e-3) / HBM_PEAK, "reps": args.reps, "warmup": args.warmup}
+
+    if not args.no_baseline:
+        # the same operator through stock PyTorch sparse products (storage order, as the kernel sees it)
+        nbr = lp.nbr.long()
+        valid = nbr >= 0
+        rows = torch.arange(n, device=dev)[:, None].expand(n, m)[valid]
+        ii = torch.cat([torch.arange(n, device=dev), rows])
+        jj = torch.cat([torch.arange(n, device=dev), nbr[valid]])
+        vv = torch.cat([torch.ones(n, dtype=torch.float64, device=dev), -lp.B[valid]])
+        IB = torch.sparse_coo_tensor(torch.stack([ii, jj]), vv, (n, n)).coalesce().to_sparse_csr()
+        IBt = torch.sparse_coo_tensor(torch.stack([jj, ii]), vv, (n, n)).coalesce().to_sparse_csr()
+        scale = (1.0 / (lp.F * args.sigma2)).contiguous()
+        x2 = x[:, None].contiguous()
+
+        def stock():
+            t = torch.mm(IB, x2)
+            t.mul_(scale[:, None])
+            o = torch.mm(IBt, t)
+            return o.addcmul_(lp.d[:, None], x2)
+
+        ref = stock()[:, 0]  # (a torch build without sparse CSR products on the GPU fails here, loudly)
+        _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws)
+        res["baseline_max_rel_diff"] = float(((out - ref).abs().max() / ref.abs().max()).item())
+        base_ms = timed(stock, args.warmup, args.reps)
+        # alternate once more, to see the spread of both on a shared machine
+        op_ms2 = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws), 10, args.reps)
+        base_ms2 = timed(stock, 10, args.reps)
+        res.update(baseline="torch.sparse_csr_tensor fp64: (I - B) x, scale, (I - B)^T t, + d x",
+                   baseline_ms=base_ms, operator_ms_repeat=op_ms2, baseline_ms_repeat=base_ms2,
+                   speedup_vs_baseline=base_ms / op_ms)
+        del IB, IBt
+
+    # the posterior mean: CG to rtol (b = h y / tau2; no covariates)
+    b = lp._rhs(())
+    lp._solve(b, args.rtol, None)  # warm-up solve
+    walls, iters = [], 0
+    for _ in range(args.solves):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, info = lp._solve(b, args.rtol, None)
+        torch.cuda.synchronize()
+        walls.append(1e3 * (time.perf_counter() - t0))
+        iters = info.iterations
+    res.update(cg_rtol=args.rtol, cg_iterations=iters, cg_converged=bool(info.converged),
+               cg_wall_ms=statistics.median(walls), cg_wall_ms_all=walls,
+               cg_ms_per_iteration=statistics.median(walls) / max(iters, 1),
+               gibbs_ms_per_iteration=args.gibbs_ms, gibbs_ms_for_as_many_sweeps=args.gibbs_ms * iters)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
