@@ -15,7 +15,7 @@
  *   - `stream` is a hipStream_t (NULL = default stream).  All work is
  *     stream-ordered; no call synchronises the host, allocates, or frees (the exceptions say so:
  *     the setup calls nngp_pair_plan_build / nngp_nbr_cert_build / nngp_color_moral_graph_dev and
- *     the solver nngp_latent_cg synchronise the stream).
+ *     the solvers nngp_latent_cg / nngp_latent_cg_batch synchronise the stream).
  *   - Coordinates are fp64 (n_points, dim) row-major, dim = 1, 2 or 3 (the
  *     reference's KDTree takes ordinates of any dimension, nngp.py:55-61); they
  *     must be finite.  Neighbour sets are int32 (rows, m) row-major, padded with -1
@@ -88,7 +88,10 @@ const char *nngp_version(void);
  * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan).
  * Added within revision 4 (nothing earlier moved): the gradient sweep nngp_bf_grad_workspace_bytes /
  * nngp_bf_grad; the latent-field posterior nngp_precision_workspace_bytes / nngp_precision_apply /
- * nngp_precision_sqrt_t_apply / nngp_latent_cg_workspace_bytes / nngp_latent_cg. */
+ * nngp_precision_sqrt_t_apply / nngp_latent_cg_workspace_bytes / nngp_latent_cg; their forms for several
+ * right-hand sides nngp_precision_batch_workspace_bytes / nngp_precision_apply_batch /
+ * nngp_precision_sqrt_t_apply_batch / nngp_latent_cg_batch_workspace_bytes / nngp_latent_cg_batch, and
+ * nngp_precision_diag. */
 #define NNGP_ABI_VERSION 4
 int32_t nngp_abi_version(void);
 
@@ -535,6 +538,42 @@ int nngp_latent_cg(const int32_t *nbr, const double *B, const int32_t *off, cons
                    const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2, const double *d,
                    const double *b, double *x, double rtol, int64_t max_iter, int32_t check_every, double *info_host,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* Several right-hand sides at once.  Vectors are (n, nrhs) row-major, 1 <= nrhs <= NNGP_LATENT_MAX_RHS: each
+ * index and coefficient is read once for all columns and a gather fetches nrhs contiguous doubles.  Geometry,
+ * prep, sigma2, d and the argument checks are those of the calls above (nrhs outside its range: NNGP_EINVAL).
+ * THE CONTRACT: column c of every result is bit-identical to the single call on that column alone, for every
+ * nrhs and whatever the other columns hold (the lane groups, tiles, grids and each column's expression
+ * sequence are the single call's).
+ * nngp_precision_apply_batch / nngp_precision_sqrt_t_apply_batch: out = A x / the square-root operator, per
+ *   column; workspace: nngp_precision_batch_workspace_bytes(n, nrhs) bytes (0 for n < 0 or a bad nrhs); x
+ *   (z1 / z2) and out must not alias.
+ * nngp_latent_cg_batch: nrhs Jacobi-PCG recurrences in lock step, one set of launches per iteration.  Each
+ *   column has its own alpha, beta, dots, tolerance, iteration count and status; a column that has converged
+ *   or broken down is frozen from that iteration on (its x is no longer written) and does not disturb the
+ *   others; the launches become no-ops once every column is finished.  Synchronises as nngp_latent_cg does,
+ *   once per check_every iterations.  info_host (HOST, nrhs x 4 doubles): one row per column with
+ *   nngp_latent_cg's meaning; the return code stays NNGP_OK.  n = 0: nothing is launched, every row reads
+ *   converged.  workspace: nngp_latent_cg_batch_workspace_bytes(n, nrhs) bytes.
+ * nngp_precision_diag: out_i = A_ii = d_i + (invF_i + P_i) / sigma2 (d NULL: 0), the very expression whose
+ *   reciprocal preconditions the CG; one stream-ordered launch, no workspace. */
+#define NNGP_LATENT_MAX_RHS 8
+size_t nngp_precision_batch_workspace_bytes(int64_t n, int32_t nrhs);
+int nngp_precision_apply_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                               const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2,
+                               const double *d, int32_t nrhs, const double *x, double *out, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int nngp_precision_sqrt_t_apply_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                      const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2,
+                                      const double *d, int32_t nrhs, const double *z1, const double *z2, double *out,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+size_t nngp_latent_cg_batch_workspace_bytes(int64_t n, int32_t nrhs);
+int nngp_latent_cg_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                         const int32_t *rev_k, const void *prep, int64_t n, int32_t m, double sigma2, const double *d,
+                         int32_t nrhs, const double *b, double *x, double rtol, int64_t max_iter, int32_t check_every,
+                         double *info_host, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_precision_diag(const void *prep, int64_t n, int32_t m, double sigma2, const double *d, double *out,
+                        void *stream);
 
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident

@@ -11,6 +11,7 @@ import ctypes
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +75,12 @@ SYMBOLS = (
     "nngp_precision_sqrt_t_apply",
     "nngp_latent_cg_workspace_bytes",
     "nngp_latent_cg",
+    "nngp_precision_batch_workspace_bytes",
+    "nngp_precision_apply_batch",
+    "nngp_precision_sqrt_t_apply_batch",
+    "nngp_latent_cg_batch_workspace_bytes",
+    "nngp_latent_cg_batch",
+    "nngp_precision_diag",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -85,6 +92,7 @@ ABI_VERSION = 4  # NNGP_ABI_VERSION of include/nngp.h this binding's signatures 
 PLAN_INFO_LEN = 10  # NNGP_PLAN_INFO_LEN
 CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
 BLOCKS_MAX_M = 32  # nngp_bf_sweep_blocks: 1 <= m <= 32
+LATENT_MAX_RHS = 8  # NNGP_LATENT_MAX_RHS: right-hand sides per batched latent call
 
 
 class NNGPExtensionError(RuntimeError):
@@ -221,6 +229,18 @@ def load() -> ctypes.CDLL:
     lib.nngp_latent_cg_workspace_bytes.restype = SZ
     lib.nngp_latent_cg.argtypes = [P, P, P, P, P, P, I64, I32, D, P, P, P, D, I64, I32, P, P, SZ, P]
     lib.nngp_latent_cg.restype = ctypes.c_int
+    lib.nngp_precision_batch_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_precision_batch_workspace_bytes.restype = SZ
+    lib.nngp_precision_apply_batch.argtypes = [P, P, P, P, P, P, I64, I32, D, P, I32, P, P, P, SZ, P]
+    lib.nngp_precision_apply_batch.restype = ctypes.c_int
+    lib.nngp_precision_sqrt_t_apply_batch.argtypes = [P, P, P, P, P, P, I64, I32, D, P, I32, P, P, P, P, SZ, P]
+    lib.nngp_precision_sqrt_t_apply_batch.restype = ctypes.c_int
+    lib.nngp_latent_cg_batch_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_latent_cg_batch_workspace_bytes.restype = SZ
+    lib.nngp_latent_cg_batch.argtypes = [P, P, P, P, P, P, I64, I32, D, P, I32, P, P, D, I64, I32, P, P, SZ, P]
+    lib.nngp_latent_cg_batch.restype = ctypes.c_int
+    lib.nngp_precision_diag.argtypes = [P, I64, I32, D, P, P, P]
+    lib.nngp_precision_diag.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1208,3 +1228,104 @@ def latent_cg(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torc
                               _ptr(d), _ptr(b), _ptr(x), float(rtol), int(max_iter), int(check_every), info,
                               _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_latent_cg")
     return x, [float(v) for v in info]
+
+
+def _latent_batch(nbr, B, off, rev_j, rev_k, prep, first, others=(), d=None):
+    """Checks of the batched calls: ``first`` float64 (n, nrhs) with 1 <= nrhs <= LATENT_MAX_RHS, ``others``
+    (None allowed) of its shape, ``d`` (n,) or None; returns (device, n, m, nrhs)."""
+    if first.dim() != 2 or first.dtype != torch.float64:
+        raise ValueError(f"batched vectors must be float64 (n, nrhs), got {first.dtype} {tuple(first.shape)}")
+    n, nrhs = first.shape
+    if not 1 <= nrhs <= LATENT_MAX_RHS:
+        raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
+    for t in others:
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (n, nrhs)):
+            raise ValueError(f"batched vectors must be float64 ({n}, {nrhs}), got {t.dtype} {tuple(t.shape)}")
+    for t in (first,) + tuple(others):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("the operator's arguments must be contiguous")
+    if nbr.dim() == 2 and nbr.shape[0] != n:
+        raise ValueError(f"batched vectors must have one row per location ({nbr.shape[0]}), got {n}")
+    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, d)
+    _require_gpu(nbr, first, *others)
+    return dev, n, m, nrhs
+
+
+def precision_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
+                          rev_k: torch.Tensor, prep: torch.Tensor, sigma2: float, x: torch.Tensor,
+                          d: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = A x for ``x`` (n, nrhs), 1 <= nrhs <= LATENT_MAX_RHS (nngp_precision_apply_batch): every index and
+    coefficient is read once for all columns.  Column c is bit-identical to :func:`precision_apply` on it."""
+    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, x, (out,), d)
+    lib = load()
+    out = torch.empty_like(x) if out is None else out
+    need = lib.nngp_precision_batch_workspace_bytes(n, nrhs)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_precision_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
+                                          float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(out), _ptr(workspace),
+                                          workspace.numel(), _stream(dev)), "nngp_precision_apply_batch")
+    return out
+
+
+def precision_sqrt_t_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
+                                 rev_k: torch.Tensor, prep: torch.Tensor, sigma2: float, z1: torch.Tensor,
+                                 z2: Optional[torch.Tensor] = None, d: Optional[torch.Tensor] = None,
+                                 out: Optional[torch.Tensor] = None,
+                                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2 for ``z1`` / ``z2`` (n, nrhs)
+    (nngp_precision_sqrt_t_apply_batch); column c is bit-identical to :func:`precision_sqrt_t_apply` on it."""
+    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, z1, (z2, out), d)
+    if d is not None and z2 is None:
+        raise ValueError("z2 is needed when d is given")
+    lib = load()
+    out = torch.empty_like(z1) if out is None else out
+    need = lib.nngp_precision_batch_workspace_bytes(n, nrhs)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_precision_sqrt_t_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep),
+                                                 n, m, float(sigma2), _ptr(d), nrhs, _ptr(z1), _ptr(z2), _ptr(out),
+                                                 _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_precision_sqrt_t_apply_batch")
+    return out
+
+
+def latent_cg_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
+                    prep: torch.Tensor, sigma2: float, b: torch.Tensor, x: torch.Tensor,
+                    d: Optional[torch.Tensor] = None, rtol: float = 1e-8, max_iter: int = 1000, check_every: int = 8,
+                    workspace: Optional[torch.Tensor] = None):
+    """nrhs Jacobi-PCG solves in lock step, in place on ``x`` (n, nrhs) (its start; nngp_latent_cg_batch).
+    Returns ``(x, info)``, info a numpy (nrhs, 4) array whose row c is :func:`latent_cg`'s info of column c;
+    column c of ``x`` is bit-identical to that single solve.  Synchronises once per ``check_every`` iterations."""
+    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, b, (x,), d)
+    lib = load()
+    need = lib.nngp_latent_cg_batch_workspace_bytes(n, nrhs)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    info = np.zeros((nrhs, 4), dtype=np.float64)
+    _check(lib.nngp_latent_cg_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
+                                    float(sigma2), _ptr(d), nrhs, _ptr(b), _ptr(x), float(rtol), int(max_iter),
+                                    int(check_every), info.ctypes.data_as(ctypes.c_void_p), _ptr(workspace),
+                                    workspace.numel(), _stream(dev)), "nngp_latent_cg_batch")
+    return x, info
+
+
+def precision_diag(prep: torch.Tensor, n: int, m: int, sigma2: float, d: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """diag(A) = d + (invF + P) / sigma2 from the ``prep`` buffer (nngp_precision_diag): the expression whose
+    reciprocal preconditions the CG."""
+    n, m = int(n), int(m)
+    if n < 0 or not 1 <= m <= MAX_M:
+        raise ValueError(f"need n >= 0 and 1 <= m <= {MAX_M}, got n={n}, m={m}")
+    for t in (d, out):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise ValueError(f"d and out must be contiguous float64 ({n},)")
+    dev = _require_gpu(prep, d, out)
+    lib = load()
+    if prep.dtype != torch.uint8 or not prep.is_contiguous() or prep.numel() < lib.nngp_gibbs_prep_bytes(n, m):
+        raise ValueError("prep must be the uint8 buffer of gibbs_prepare for these factors")
+    out = torch.empty(n, dtype=torch.float64, device=dev) if out is None else out
+    _check(lib.nngp_precision_diag(_ptr(prep), n, m, float(sigma2), _ptr(d), _ptr(out), _stream(dev)),
+           "nngp_precision_diag")
+    return out

@@ -846,6 +846,93 @@ int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, cons
     return NNGP_OK;
 }
 
+// several right-hand sides: the single calls' checks, plus nrhs
+static bool bad_nrhs(int32_t nrhs) { return nrhs < 1 || nrhs > NNGP_LATENT_MAX_RHS; }
+static int fail_nrhs(int32_t nrhs) {
+    return fail(NNGP_EINVAL, "nrhs=%d outside [1, %d]", nrhs, NNGP_LATENT_MAX_RHS);
+}
+
+size_t nngp_precision_batch_workspace_bytes(int64_t n, int32_t nrhs) {
+    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_apply_batch_workspace_bytes(n, nrhs);
+}
+
+int nngp_precision_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                               const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                               const double* d, int32_t nrhs, const double* x, double* out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_apply_batch_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_apply_batch launch");
+    return NNGP_OK;
+}
+
+int nngp_precision_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                      const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                                      const double* d, int32_t nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
+        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
+    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_sqrt_t_apply_batch_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_sqrt_t_apply_batch launch");
+    return NNGP_OK;
+}
+
+size_t nngp_latent_cg_batch_workspace_bytes(int64_t n, int32_t nrhs) {
+    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_cg_batch_workspace_bytes(n, nrhs);
+}
+
+int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                         int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every,
+                         double* info_host, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (b == nullptr || x == nullptr || info_host == nullptr)
+        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
+    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
+    if (max_iter < 0 || check_every < 1)
+        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
+                    check_every);
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_latent_cg_batch_workspace_bytes(n, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_cg_batch_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "latent_cg_batch");
+    return NNGP_OK;
+}
+
+int nngp_precision_diag(const void* prep, int64_t n, int32_t m, double sigma2, const double* d, double* out,
+                        void* stream) {
+    if (prep == nullptr || out == nullptr) return fail(NNGP_EINVAL, "prep and out must be non-null");
+    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
+        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
+    if (((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
+    hipError_t e = nngp::latent_diag_launch(nngp::latent_prep_view(prep, n, m), n, sigma2, d, out,
+                                            (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_diag launch");
+    return NNGP_OK;
+}
+
 size_t nngp_row_order_workspace_bytes(int64_t n_rows) { return nngp::row_order_workspace_bytes(n_rows); }
 
 int nngp_row_order(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, int32_t m, int64_t i0,

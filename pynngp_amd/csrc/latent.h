@@ -40,4 +40,21 @@ hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, const double* z1, con
 hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double rtol, int64_t max_iter,
                          int check_every, double* info_host, void* workspace, hipStream_t s);
 
+// Several right-hand sides at once: vectors are (n, nrhs) row-major, 1 <= nrhs <= NNGP_LATENT_MAX_RHS.  Column c
+// of every result is bit-identical to the call above on that column alone, whatever the other columns hold.
+size_t latent_apply_batch_workspace_bytes(int64_t n, int nrhs);
+size_t latent_cg_batch_workspace_bytes(int64_t n, int nrhs);
+hipError_t latent_apply_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
+                                     hipStream_t s);
+hipError_t latent_sqrt_t_apply_batch_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2,
+                                            double* out, void* workspace, hipStream_t s);
+// nrhs Jacobi-PCG recurrences in lock step, each with its own scalars and stopping; info_host: (nrhs, 4) rows
+// as latent_cg_run's.  A finished column is frozen; the launches are no-ops once every column is finished.
+hipError_t latent_cg_batch_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol,
+                               int64_t max_iter, int check_every, double* info_host, void* workspace,
+                               hipStream_t s);
+// out_i = diag(A)_i = d_i + (invF_i + P_i) / sigma2 (d null: 0), the CG's preconditioner before its reciprocal
+hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
+                              hipStream_t s);
+
 }  // namespace nngp

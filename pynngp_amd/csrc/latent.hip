@@ -21,6 +21,7 @@
 
 #include <math.h>
 
+#include "../../include/nngp.h"
 #include "nngp_internal.h"
 
 namespace nngp {
@@ -177,6 +178,14 @@ __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __res
 }
 
 // ---------------------------------------------------------------- CG vector kernels
+// diag(A)_i = d_i + (invF_i + P_i) / sigma2, the Jacobi preconditioner's and nngp_precision_diag's.  One fused
+// multiply-add, written out: it is what the compiler contracted the plain expression to, and every kernel that
+// needs the diagonal must get these bits whatever its surroundings.
+__device__ __forceinline__ double latent_diag(const double* __restrict__ d, const double* __restrict__ invF,
+                                              const double* __restrict__ P, double inv_s2, int64_t i) {
+    return fma(invF[i] + P[i], inv_s2, d != nullptr ? d[i] : 0.0);
+}
+
 // start: M^-1 = 1 / (d + (invF + P) / sigma2), r = b - A x0 (q holds A x0), z = M^-1 r, p = z; records of
 // r.z, r.r and b.b
 __global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(int64_t n, const double* __restrict__ b,
@@ -190,8 +199,7 @@ __global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(int64_t n, const
     __shared__ double sh4[4];
     double rz = 0.0, rr = 0.0, bb = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double diag = (d != nullptr ? d[i] : 0.0) + (invF[i] + P[i]) * inv_s2;
-        const double mi = 1.0 / diag;
+        const double mi = 1.0 / latent_diag(d, invF, P, inv_s2, i);
         const double bi = b[i], ri = bi - q[i], zi = mi * ri;
         Minv[i] = mi;
         r[i] = ri;
@@ -300,6 +308,377 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, 
         st[kBeta] = beta;
         st[kIter] = (double)(k + 1);
         st[kFlag0 + nxt] = st[kStatus] = done;
+    }
+}
+
+// ================================================================ several right-hand sides at once
+// Vectors are (n, nrhs) row-major, 1 <= nrhs <= kMaxRhs: an index or coefficient is loaded once for all
+// columns and a gather fetches nrhs contiguous doubles.  Column c of every kernel below is bit-identical to
+// the single-RHS kernel above run on that column alone: the lane groups, tiles, grids, thread -> location and
+// tile -> block mappings are the same, and so is each column's expression sequence (every multiply-add is an
+// explicit fma or cannot fuse).  KP is the padded column count (2, 4, 8): register arrays are indexed by
+// compile-time constants only; a padding column c >= nrhs re-reads column nrhs - 1 (a valid address, no
+// branch around the load) and is never stored.
+constexpr int kMaxRhs = NNGP_LATENT_MAX_RHS;
+enum { kAll0 = 0, kAll1 = 1 };  // the "every column finished" words, after the kMaxRhs per-column state blocks
+
+template <int G, int KP>
+__global__ __launch_bounds__(kBlock) void latent_row_batch_kernel(const int32_t* __restrict__ nbr,
+                                                                  const double* __restrict__ B,
+                                                                  const double* __restrict__ invF,
+                                                                  const double* __restrict__ x,
+                                                                  double* __restrict__ t, int64_t n, int m,
+                                                                  int nrhs, double inv_s2,
+                                                                  const double* __restrict__ stop) {
+    if (stop != nullptr && *stop != 0.0) return;
+    constexpr int kRows = kBlock / G;
+    const int g = threadIdx.x / G, l = threadIdx.x % G;
+    int cc[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) cc[c] = c < nrhs ? c : nrhs - 1;
+    int64_t lo, hi;
+    tile_range((n + kRows - 1) / kRows, &lo, &hi);
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t i = tile * kRows + g;
+        double acc[KP];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = 0.0;
+        if (i < n) {
+            const int32_t* nb = nbr + i * m;
+            const double* bb = B + i * m;
+            for (int s = l; s < m; s += G) {
+                const int32_t j = nb[s];
+                if (j >= 0 && (int64_t)j < n) {  // a slot without a point: exactly 0 in every column
+                    const double b = bb[s];
+                    const double* xj = x + (int64_t)j * nrhs;
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) acc[c] = fma(b, xj[cc[c]], acc[c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = lane_group_sum<G>(acc[c]);
+        if (i < n && l == 0) {
+            const double sc = invF[i] * inv_s2;
+            const double* xi = x + i * nrhs;
+            double* ti = t + i * nrhs;
+#pragma unroll
+            for (int c = 0; c < KP; ++c)
+                if (c < nrhs) ti[c] = (xi[c] - acc[c]) * sc;
+        }
+    }
+}
+
+// u[i, c] = z1[i, c] sqrt(invF_i / sigma2)
+__global__ __launch_bounds__(kBlock) void latent_scale_batch_kernel(const double* __restrict__ invF,
+                                                                    const double* __restrict__ z1,
+                                                                    double* __restrict__ u, int64_t n, int nrhs,
+                                                                    double inv_s2) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double sc = sqrt(invF[i] * inv_s2);
+        for (int c = 0; c < nrhs; ++c) u[i * nrhs + c] = z1[i * nrhs + c] * sc;
+    }
+}
+
+// rec: null, or column c's record of the block at rec[c * kMaxTileBlocks + blockIdx.x]
+template <bool SQRT, int KP>
+__global__ __launch_bounds__(kBlock) void latent_col_batch_kernel(const int32_t* __restrict__ off,
+                                                                  const int32_t* __restrict__ rev_j,
+                                                                  const double* __restrict__ Brev,
+                                                                  const double* __restrict__ t,
+                                                                  const double* __restrict__ d,
+                                                                  const double* __restrict__ x,
+                                                                  double* __restrict__ out, int64_t n, int nrhs,
+                                                                  double* __restrict__ rec,
+                                                                  const double* __restrict__ stop) {
+    __shared__ int32_t sh_e0[kColRows], sh_e1[kColRows];
+    __shared__ double sh4[4];
+    if (stop != nullptr && *stop != 0.0) return;
+    const int g = threadIdx.x / kColLanes, l = threadIdx.x % kColLanes;
+    int cc[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) cc[c] = c < nrhs ? c : nrhs - 1;
+    int64_t lo, hi;
+    tile_range((n + kColRows - 1) / kColRows, &lo, &hi);
+    double dot[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) dot[c] = 0.0;
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t i = tile * kColRows + g;
+        const bool live = i < n;
+        const int32_t e0 = live ? off[i] : 0, e1 = live ? off[i + 1] : 0;
+        const bool is_long = e1 - e0 > kLongList;
+        double acc[KP];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = 0.0;
+        if (!is_long) {
+            for (int32_t e = e0 + l; e < e1; e += kColLanes) {
+                const int32_t j = rev_j[e];
+                if ((uint32_t)j < (uint64_t)n) {
+                    const double b = Brev[e];
+                    const double* tj = t + (int64_t)j * nrhs;
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) acc[c] = fma(b, tj[cc[c]], acc[c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = lane_group_sum<kColLanes>(acc[c]);
+        if (__syncthreads_or(is_long)) {  // block-uniform; rare (hubs)
+            if (l == 0) {
+                sh_e0[g] = e0;
+                sh_e1[g] = is_long ? e1 : e0;
+            }
+            __syncthreads();
+            for (int k = 0; k < kColRows; ++k) {
+                const int32_t a0 = sh_e0[k], a1 = sh_e1[k];
+                if (a1 <= a0) continue;  // block-uniform
+                double s[KP];
+#pragma unroll
+                for (int c = 0; c < KP; ++c) s[c] = 0.0;
+                for (int32_t e = a0 + (int32_t)threadIdx.x; e < a1; e += kBlock) {
+                    const int32_t j = rev_j[e];
+                    if ((uint32_t)j < (uint64_t)n) {
+                        const double b = Brev[e];
+                        const double* tj = t + (int64_t)j * nrhs;
+#pragma unroll
+                        for (int c = 0; c < KP; ++c) s[c] = fma(b, tj[cc[c]], s[c]);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < KP; ++c) {
+                    const double sc = block_sum(s[c], sh4);
+                    if (g == k) acc[c] = sc;
+                }
+            }
+            __syncthreads();
+        }
+        if (live && l == 0) {
+            const bool want_x = (d != nullptr || rec != nullptr) && x != nullptr;
+            double dd = 0.0;
+            if (d != nullptr) dd = SQRT ? sqrt(d[i]) : d[i];
+#pragma unroll
+            for (int c = 0; c < KP; ++c) {
+                double o = t[i * nrhs + cc[c]] - acc[c];
+                const double xi = want_x ? x[i * nrhs + cc[c]] : 0.0;
+                if (d != nullptr) o = fma(dd, xi, o);
+                if (c < nrhs) out[i * nrhs + c] = o;
+                dot[c] = fma(xi, o, dot[c]);
+            }
+        }
+    }
+    if (rec != nullptr) {
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            const double v = block_sum(dot[c], sh4);
+            if (threadIdx.x == 0 && c < nrhs) rec[c * kMaxTileBlocks + blockIdx.x] = v;
+        }
+    }
+}
+
+// out_i = diag(A)_i
+__global__ __launch_bounds__(kBlock) void latent_diag_kernel(int64_t n, const double* __restrict__ d,
+                                                             const double* __restrict__ invF,
+                                                             const double* __restrict__ P, double inv_s2,
+                                                             double* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        out[i] = latent_diag(d, invF, P, inv_s2, i);
+}
+
+// ---------------------------------------------------------------- batched CG: nrhs recurrences in lock step
+// Column c owns the state block st + c * kStateWords and the record rows rec + c * 3 * kMaxVecBlocks and
+// pq_rec + c * kMaxTileBlocks; the two words after the kMaxRhs state blocks say "every column is finished" for
+// the even and the odd iterations (the operator launches' stop word).  A finished column (converged or broken
+// down) is frozen: from then on none of its x, r, z, p or state is written.  M^-1 does not depend on the column.
+template <int KP>
+__global__ __launch_bounds__(kBlock) void latent_cg_init_batch_kernel(
+    int64_t n, int nrhs, const double* __restrict__ b, const double* __restrict__ q, const double* __restrict__ d,
+    const double* __restrict__ invF, const double* __restrict__ P, double inv_s2, double* __restrict__ r,
+    double* __restrict__ z, double* __restrict__ p, double* __restrict__ Minv, double* __restrict__ rec) {
+    __shared__ double sh4[4];
+    int cc[KP];
+    double rz[KP], rr[KP], bb[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        cc[c] = c < nrhs ? c : nrhs - 1;
+        rz[c] = rr[c] = bb[c] = 0.0;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double mi = 1.0 / latent_diag(d, invF, P, inv_s2, i);
+        Minv[i] = mi;
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            const int64_t e = i * nrhs + cc[c];
+            const double bi = b[e], ri = bi - q[e], zi = mi * ri;
+            if (c < nrhs) {
+                r[e] = ri;
+                z[e] = zi;
+                p[e] = zi;
+            }
+            rz[c] = fma(ri, zi, rz[c]);
+            rr[c] = fma(ri, ri, rr[c]);
+            bb[c] = fma(bi, bi, bb[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        const double a0 = block_sum(rz[c], sh4), a1 = block_sum(rr[c], sh4), a2 = block_sum(bb[c], sh4);
+        if (threadIdx.x == 0 && c < nrhs) {
+            double* rc = rec + (size_t)c * 3 * kMaxVecBlocks;
+            rc[blockIdx.x] = a0;
+            rc[kMaxVecBlocks + blockIdx.x] = a1;
+            rc[2 * kMaxVecBlocks + blockIdx.x] = a2;
+        }
+    }
+}
+
+// one block: fold each column's start records into its state
+__global__ __launch_bounds__(kBlock) void latent_cg_start_batch_kernel(const double* __restrict__ rec, int n_rec,
+                                                                       int nrhs, double rtol,
+                                                                       double* __restrict__ st) {
+    __shared__ double sh4[4];
+    double all = 1.0;
+    for (int c = 0; c < nrhs; ++c) {
+        const double* rc = rec + (size_t)c * 3 * kMaxVecBlocks;
+        const double rz = fold_records(rc, n_rec, sh4);
+        const double rr = fold_records(rc + kMaxVecBlocks, n_rec, sh4);
+        const double bb = fold_records(rc + 2 * kMaxVecBlocks, n_rec, sh4);
+        const double tol2 = rtol * rtol * bb;
+        const double done = rr <= tol2 ? 1.0 : 0.0;
+        if (done == 0.0) all = 0.0;
+        if (threadIdx.x == 0) {
+            double* sc = st + c * kStateWords;
+            sc[kRz0] = rz;
+            sc[kRz1] = 0.0;
+            sc[kRr] = rr;
+            sc[kBb] = bb;
+            sc[kTol2] = tol2;
+            sc[kAlpha] = sc[kBeta] = 0.0;
+            sc[kIter] = 0.0;
+            sc[kStatus] = done;
+            sc[kFlag0] = done;
+            sc[kFlag1] = 0.0;
+            sc[kBrk] = 0.0;
+        }
+    }
+    if (threadIdx.x == 0) {
+        st[kMaxRhs * kStateWords + kAll0] = all;
+        st[kMaxRhs * kStateWords + kAll1] = 0.0;
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(kBlock) void latent_cg_update_batch_kernel(
+    int64_t n, int nrhs, int64_t k, const double* __restrict__ pq_rec, int n_pq, const double* __restrict__ p,
+    const double* __restrict__ q, const double* __restrict__ Minv, double* __restrict__ x, double* __restrict__ r,
+    double* __restrict__ z, double* __restrict__ rec, double* __restrict__ st) {
+    __shared__ double sh4[4];
+    const int cur = (int)(k & 1);
+    if (st[kMaxRhs * kStateWords + kAll0 + cur] != 0.0) return;
+    int cc[KP];
+    bool act[KP];
+    double alpha[KP], rz[KP], rr[KP];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        cc[c] = c < nrhs ? c : nrhs - 1;
+        act[c] = false;
+        alpha[c] = rz[c] = rr[c] = 0.0;
+        if (c < nrhs) {  // block-uniform, as is everything read from the state
+            double* sc = st + c * kStateWords;
+            if (sc[kFlag0 + cur] == 0.0) {
+                const double pq = fold_records(pq_rec + (size_t)c * kMaxTileBlocks, n_pq, sh4);
+                if (!(pq > 0.0) || pq > 1.7976931348623157e308) {  // not above 0, NaN or +inf: this column only
+                    if (blockIdx.x == 0 && threadIdx.x == 0) sc[kBrk] = 1.0;
+                } else {
+                    alpha[c] = sc[kRz0 + cur] / pq;
+                    act[c] = any = true;
+                }
+            }
+        }
+    }
+    if (!any) return;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double mi = Minv[i];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            const int64_t e = i * nrhs + cc[c];
+            const double xe = fma(alpha[c], p[e], x[e]);
+            const double ri = fma(-alpha[c], q[e], r[e]);
+            const double zi = mi * ri;
+            if (act[c]) {
+                x[e] = xe;
+                r[e] = ri;
+                z[e] = zi;
+            }
+            rz[c] = fma(ri, zi, rz[c]);
+            rr[c] = fma(ri, ri, rr[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        const double a0 = block_sum(rz[c], sh4), a1 = block_sum(rr[c], sh4);
+        if (threadIdx.x == 0 && act[c]) {
+            double* rc = rec + (size_t)c * 3 * kMaxVecBlocks;
+            rc[blockIdx.x] = a0;
+            rc[kMaxVecBlocks + blockIdx.x] = a1;
+            if (blockIdx.x == 0) st[c * kStateWords + kAlpha] = alpha[c];
+        }
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(kBlock) void latent_cg_direction_batch_kernel(int64_t n, int nrhs, int64_t k,
+                                                                           const double* __restrict__ rec, int n_rec,
+                                                                           const double* __restrict__ z,
+                                                                           double* __restrict__ p,
+                                                                           double* __restrict__ st) {
+    __shared__ double sh4[4];
+    const int cur = (int)(k & 1), nxt = cur ^ 1;
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    int cc[KP];
+    bool act[KP];
+    double beta[KP];
+    bool any = false, all_done = true;
+#pragma unroll
+    for (int c = 0; c < KP; ++c) {
+        cc[c] = c < nrhs ? c : nrhs - 1;
+        act[c] = false;
+        beta[c] = 0.0;
+        if (c < nrhs) {  // block-uniform
+            double* sc = st + c * kStateWords;
+            const double flag = sc[kFlag0 + cur];
+            if (flag != 0.0) {
+                if (lead) sc[kFlag0 + nxt] = flag;
+            } else if (sc[kBrk] != 0.0) {
+                if (lead) sc[kFlag0 + nxt] = sc[kStatus] = -1.0;
+            } else {
+                const double* rc = rec + (size_t)c * 3 * kMaxVecBlocks;
+                const double rz = fold_records(rc, n_rec, sh4);
+                const double rr = fold_records(rc + kMaxVecBlocks, n_rec, sh4);
+                beta[c] = rz / sc[kRz0 + cur];
+                act[c] = any = true;
+                const double done = rr <= sc[kTol2] ? 1.0 : 0.0;
+                if (done == 0.0) all_done = false;
+                if (lead) {
+                    sc[kRz0 + nxt] = rz;
+                    sc[kRr] = rr;
+                    sc[kBeta] = beta[c];
+                    sc[kIter] = (double)(k + 1);
+                    sc[kFlag0 + nxt] = sc[kStatus] = done;
+                }
+            }
+        }
+    }
+    if (lead) st[kMaxRhs * kStateWords + kAll0 + nxt] = all_done ? 1.0 : 0.0;
+    if (!any) return;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            const int64_t e = i * nrhs + cc[c];
+            const double pe = fma(beta[c], p[e], z[e]);
+            if (act[c]) p[e] = pe;
+        }
     }
 }
 
@@ -422,6 +801,171 @@ hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double
     info_host[1] = st[kStatus];
     info_host[2] = st[kRr];
     info_host[3] = st[kBb];
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- several right-hand sides: launches
+namespace {
+
+// KP: the padded column count of the instantiation that serves nrhs
+#define NNGP_LATENT_KP(nrhs, ...) \
+    do {                          \
+        if ((nrhs) <= 2) {        \
+            constexpr int KP = 2; \
+            __VA_ARGS__;          \
+        } else if ((nrhs) <= 4) { \
+            constexpr int KP = 4; \
+            __VA_ARGS__;          \
+        } else {                  \
+            constexpr int KP = 8; \
+            __VA_ARGS__;          \
+        }                         \
+    } while (0)
+
+template <int KP>
+void row_batch_launch_kp(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop,
+                         hipStream_t s) {
+    const double inv_s2 = 1.0 / g.sigma2;
+    if (g.m <= 4)
+        hipLaunchKernelGGL((latent_row_batch_kernel<4, KP>), dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+    else if (g.m <= 8)
+        hipLaunchKernelGGL((latent_row_batch_kernel<8, KP>), dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+    else
+        hipLaunchKernelGGL((latent_row_batch_kernel<16, KP>), dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0,
+                           s, g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+}
+
+void row_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop,
+                      hipStream_t s) {
+    NNGP_LATENT_KP(nrhs, row_batch_launch_kp<KP>(g, nrhs, x, t, stop, s));
+}
+
+template <bool SQRT>
+void col_batch_launch(const LatentGeom& g, int nrhs, const double* t, const double* x, double* out, double* rec,
+                      const double* stop, hipStream_t s) {
+    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_batch_kernel<SQRT, KP>), dim3(tile_blocks(g.n, kColRows)),
+                                            dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev, t, g.d, x, out, g.n,
+                                            nrhs, rec, stop));
+}
+
+// the batched CG workspace: six (n, nrhs) slots (M^-1, shared by the columns, uses n doubles of its own),
+// kMaxRhs rows of records, kMaxRhs state blocks and the block of the two "all finished" words
+struct CgBatchLayout {
+    double *t, *r, *z, *p, *q, *Minv, *rec, *pq_rec, *st;
+};
+
+constexpr size_t kBatchStateWords = (size_t)(kMaxRhs + 1) * kStateWords;
+
+CgBatchLayout cg_batch_layout(void* workspace, int64_t n, int nrhs) {
+    char* w = (char*)workspace;
+    const size_t v = align256((size_t)n * nrhs * 8);
+    CgBatchLayout L;
+    L.t = (double*)w;
+    L.r = (double*)(w + v);
+    L.z = (double*)(w + 2 * v);
+    L.p = (double*)(w + 3 * v);
+    L.q = (double*)(w + 4 * v);
+    L.Minv = (double*)(w + 5 * v);
+    w += 6 * v;
+    L.rec = (double*)w;
+    w += align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8);
+    L.pq_rec = (double*)w;
+    w += align256((size_t)kMaxRhs * kMaxTileBlocks * 8);
+    L.st = (double*)w;
+    return L;
+}
+
+}  // namespace
+
+size_t latent_apply_batch_workspace_bytes(int64_t n, int nrhs) {
+    return align256((size_t)(n > 0 ? n : 1) * nrhs * 8);
+}
+
+size_t latent_cg_batch_workspace_bytes(int64_t n, int nrhs) {
+    return 6 * align256((size_t)n * nrhs * 8) + align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8) +
+           align256((size_t)kMaxRhs * kMaxTileBlocks * 8) + align256(kBatchStateWords * 8);
+}
+
+hipError_t latent_apply_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
+                                     hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* t = (double*)workspace;
+    row_batch_launch(g, nrhs, x, t, nullptr, s);
+    col_batch_launch<false>(g, nrhs, t, x, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_sqrt_t_apply_batch_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2,
+                                            double* out, void* workspace, hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* u = (double*)workspace;
+    hipLaunchKernelGGL(latent_scale_batch_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n,
+                       nrhs, 1.0 / g.sigma2);
+    col_batch_launch<true>(g, nrhs, u, z2, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
+                              hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(latent_diag_kernel, dim3(vec_blocks(n)), dim3(kBlock), 0, s, n, d, prep.invF, prep.P,
+                       1.0 / sigma2, out);
+    return hipGetLastError();
+}
+
+hipError_t latent_cg_batch_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol,
+                               int64_t max_iter, int check_every, double* info_host, void* workspace,
+                               hipStream_t s) {
+    for (int c = 0; c < nrhs; ++c) {
+        info_host[4 * c + 0] = 0.0;
+        info_host[4 * c + 1] = 1.0;
+        info_host[4 * c + 2] = info_host[4 * c + 3] = 0.0;
+    }
+    if (g.n == 0) return hipSuccess;
+    const CgBatchLayout L = cg_batch_layout(workspace, g.n, nrhs);
+    const int nv = vec_blocks(g.n), nt = tile_blocks(g.n, kColRows);
+    const double inv_s2 = 1.0 / g.sigma2;
+    double* all = L.st + kMaxRhs * kStateWords + kAll0;
+    hipError_t e;
+    // r = b - A x0, z = M^-1 r, p = z, per column
+    row_batch_launch(g, nrhs, x, L.t, nullptr, s);
+    col_batch_launch<false>(g, nrhs, L.t, x, L.q, nullptr, nullptr, s);
+    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_init_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n, nrhs, b,
+                                            (const double*)L.q, g.d, g.prep.invF, g.prep.P, inv_s2, L.r, L.z, L.p,
+                                            L.Minv, L.rec));
+    hipLaunchKernelGGL(latent_cg_start_batch_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, nrhs, rtol,
+                       L.st);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    double st[kBatchStateWords];
+    int64_t k = 0;
+    for (;;) {
+        // one chunk: no host synchronisation inside; once every column is finished the launches are no-ops
+        for (int c = 0; c < check_every && k < max_iter; ++c, ++k) {
+            const double* stop = all + (k & 1);
+            row_batch_launch(g, nrhs, L.p, L.t, stop, s);
+            col_batch_launch<false>(g, nrhs, L.t, L.p, L.q, L.pq_rec, stop, s);
+            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_update_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0, s,
+                                                    g.n, nrhs, k, (const double*)L.pq_rec, nt, (const double*)L.p,
+                                                    (const double*)L.q, (const double*)L.Minv, x, L.r, L.z, L.rec,
+                                                    L.st));
+            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_direction_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0,
+                                                    s, g.n, nrhs, k, (const double*)L.rec, nv, (const double*)L.z,
+                                                    L.p, L.st));
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(st, L.st, sizeof st, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        if (st[kMaxRhs * kStateWords + kAll0 + (k & 1)] != 0.0 || k >= max_iter) break;
+    }
+    for (int c = 0; c < nrhs; ++c) {
+        const double* sc = st + c * kStateWords;
+        info_host[4 * c + 0] = sc[kIter];
+        info_host[4 * c + 1] = sc[kStatus];
+        info_host[4 * c + 2] = sc[kRr];
+        info_host[4 * c + 3] = sc[kBb];
+    }
     return hipSuccess;
 }
 

@@ -401,9 +401,67 @@ std::tuple<at::Tensor, at::Tensor> latent_cg(const at::Tensor& nbr, const at::Te
     return {x, info};
 }
 
+// the batched forms: x / b / x0 (n, nrhs), 1 <= nrhs <= NNGP_LATENT_MAX_RHS; column c bit-identical to the single op
+int64_t check_batch(const at::Tensor& v, const at::Tensor& nbr, const char* name) {
+    TORCH_CHECK(v.dim() == 2 && v.size(1) >= 1 && v.size(1) <= NNGP_LATENT_MAX_RHS, name,
+                " must be (n, nrhs) with 1 <= nrhs <= ", NNGP_LATENT_MAX_RHS);
+    check_f64(v, {nbr.size(0), v.size(1)}, nbr, name);
+    return v.size(1);
+}
+
+at::Tensor precision_apply_batch(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off,
+                                 const at::Tensor& rev_j, const at::Tensor& rev_k, const at::Tensor& prep,
+                                 double sigma2, const c10::optional<at::Tensor>& d, const at::Tensor& x) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(d, {n}, nbr, "d");
+    const int64_t nrhs = check_batch(x, nbr, "x");
+    auto out = at::empty_like(x);
+    auto ws = at::empty({(int64_t)nngp_precision_batch_workspace_bytes(n, (int32_t)nrhs)},
+                        nbr.options().dtype(at::kByte));
+    check_rc(nngp_precision_apply_batch(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                                        rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), n,
+                                        (int32_t)m, sigma2, ptr<double>(d), (int32_t)nrhs, x.data_ptr<double>(),
+                                        out.data_ptr<double>(), ws.data_ptr(), (size_t)ws.nbytes(), stream(nbr)),
+             "nngp_precision_apply_batch");
+    return out;
+}
+
+// (x (n, nrhs), info): info a CPU float64 (nrhs, 4), row c as latent_cg's info of column c
+std::tuple<at::Tensor, at::Tensor> latent_cg_batch(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off,
+                                                   const at::Tensor& rev_j, const at::Tensor& rev_k,
+                                                   const at::Tensor& prep, double sigma2,
+                                                   const c10::optional<at::Tensor>& d, const at::Tensor& b,
+                                                   const c10::optional<at::Tensor>& x0, double rtol, int64_t max_iter,
+                                                   int64_t check_every) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(d, {n}, nbr, "d");
+    const int64_t nrhs = check_batch(b, nbr, "b");
+    check_f64(x0, {n, nrhs}, nbr, "x0");
+    at::Tensor x = x0.has_value() ? x0->clone() : at::zeros_like(b);
+    auto info = at::empty({nrhs, 4}, at::TensorOptions().dtype(at::kDouble));
+    auto ws = at::empty({(int64_t)nngp_latent_cg_batch_workspace_bytes(n, (int32_t)nrhs)},
+                        nbr.options().dtype(at::kByte));
+    check_rc(nngp_latent_cg_batch(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                                  rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), n, (int32_t)m,
+                                  sigma2, ptr<double>(d), (int32_t)nrhs, b.data_ptr<double>(), x.data_ptr<double>(),
+                                  rtol, max_iter, (int32_t)check_every, info.data_ptr<double>(), ws.data_ptr(),
+                                  (size_t)ws.nbytes(), stream(nbr)),
+             "nngp_latent_cg_batch");
+    return {x, info};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
+    m.def("precision_apply_batch(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, "
+          "float sigma2, Tensor? d, Tensor x) -> Tensor");
+    m.def("latent_cg_batch(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
+          "Tensor? d, Tensor b, Tensor? x0=None, float rtol=1e-08, int max_iter=1000, int check_every=8) -> "
+          "(Tensor, Tensor)");
     m.def("precision_apply(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
           "Tensor? d, Tensor x) -> Tensor");
     m.def("latent_cg(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
@@ -442,4 +500,6 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("combine_partials_out", &combine_partials_out);
     m.impl("precision_apply", &precision_apply);
     m.impl("latent_cg", &latent_cg);
+    m.impl("precision_apply_batch", &precision_apply_batch);
+    m.impl("latent_cg_batch", &latent_cg_batch);
 }

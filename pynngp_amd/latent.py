@@ -30,6 +30,7 @@ from . import _lib
 from .nngp import Covariance, NNGPNumericalError, _default_device, _raise_on_bad
 
 CHECK_EVERY = 8  # CG iterations between host synchronisations
+DEFAULT_BATCH = _lib.LATENT_MAX_RHS  # right-hand sides per batched call where the caller does not say
 
 
 @dataclasses.dataclass(frozen=True)
@@ -130,6 +131,7 @@ class LatentPosterior:
         self.F = torch.empty(n, dtype=torch.float64, device=dev)
         self._prep = None
         self._ws = _lib._workspace(_lib.load().nngp_latent_cg_workspace_bytes(n), dev)
+        self._ws_batch = None  # the batched solver's workspace, made on first use for the widest chunk so far
         self.update(cov)
 
     # -- theta -----------------------------------------------------------------
@@ -190,19 +192,96 @@ class LatentPosterior:
         x, si = self._solve(self._in(rhs, "rhs"), rtol, max_iter, None if x0 is None else self._in(x0, "x0"))
         return self._out(x, rhs), si
 
+    # -- several right-hand sides at once ---------------------------------------
+    @staticmethod
+    def _batch(batch) -> int:
+        b = DEFAULT_BATCH if batch is None else int(batch)
+        if not 1 <= b <= _lib.LATENT_MAX_RHS:
+            raise ValueError(f"batch must be in [1, {_lib.LATENT_MAX_RHS}], got {batch}")
+        return b
+
+    def _batch_ws(self, nrhs):
+        need = _lib.load().nngp_latent_cg_batch_workspace_bytes(self.n, nrhs)
+        if self._ws_batch is None or self._ws_batch.numel() < need:
+            self._ws_batch = _lib._workspace(need, self.device)
+        return self._ws_batch
+
+    def _in_rows(self, v, what="rhs"):
+        """(K, N) rows in the order of ``coords`` -> (K, N) device rows in storage order."""
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != self.n:
+            raise ValueError(f"{what} must be float64 (K, {self.n}), got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device)[:, self.perm]
+
+    def _solve_cols(self, R, rtol, max_iter, X0=None):
+        """One batched solve of the storage-order columns R (n, k <= LATENT_MAX_RHS): (X, info (k, 4))."""
+        X = torch.zeros_like(R) if X0 is None else X0.clone()
+        return _lib.latent_cg_batch(*self._geom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
+                                    check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
+
+    def _report(self, info, rtol, first=0):
+        """[SolveInfo] of the (K, 4) info rows (of the right-hand sides first, first + 1, ...); raises on a
+        breakdown, warns once on non-convergence."""
+        infos = [SolveInfo(int(r[0]), bool(r[1] > 0), float(r[2]), float(r[3])) for r in info]
+        broken = [k for k, r in enumerate(info) if r[1] < 0]
+        if broken:
+            raise NNGPNumericalError(f"CG breakdown in column(s) {[first + k for k in broken]} after "
+                                     f"{[infos[k].iterations for k in broken]} iterations: p.Ap is not positive and "
+                                     "finite (NaN or inf in the factors or the right-hand side?)")
+        slow = [k for k, si in enumerate(infos) if not si.converged]
+        if slow:
+            warnings.warn(f"latent CG did not reach rtol={rtol:g} in column(s) {[first + k for k in slow]} "
+                          f"({[infos[k].iterations for k in slow]} iterations)", RuntimeWarning, stacklevel=3)
+        return infos
+
+    def _solve_rows(self, rows, rtol, max_iter, batch, x0=None):
+        """Storage-order rows (K, n) on the device -> (solutions (K, n), info (K, 4)), ``batch`` columns per
+        solve; the transposes stay on the device."""
+        if not 0.0 < rtol < 1.0:
+            raise ValueError(f"rtol must be in (0, 1), got {rtol}")
+        if max_iter is None:
+            max_iter = min(max(2 * self.n, 1000), 20000)
+        K = rows.shape[0]
+        out = torch.empty((K, self.n), dtype=torch.float64, device=self.device)
+        info = np.zeros((K, 4))
+        for k0 in range(0, K, batch):
+            k1 = min(K, k0 + batch)
+            X, info[k0:k1] = self._solve_cols(rows[k0:k1].t().contiguous(), rtol, max_iter,
+                                              None if x0 is None else x0[k0:k1].t().contiguous())
+            out[k0:k1] = X.t()
+        return out, info
+
+    def solve_many(self, rhs, rtol: float = 1e-8, max_iter: Optional[int] = None, x0=None, batch=None):
+        """Solve A x_k = rhs[k] for the K >= 0 rows of ``rhs`` (K, N): ``(x (K, N), [SolveInfo] * K)``.  The rows
+        go through the batched solver ``batch`` at a time (default ``LATENT_MAX_RHS``; every index and coefficient
+        of A is read once per chunk instead of once per row), and row k equals ``solve(rhs[k])`` bit for bit.
+        A breakdown raises :class:`NNGPNumericalError` naming the rows; rows that run out of ``max_iter`` are
+        named in one ``RuntimeWarning``."""
+        batch = self._batch(batch)
+        rows = self._in_rows(rhs, "rhs")
+        starts = None if x0 is None else self._in_rows(x0, "x0")
+        if starts is not None and starts.shape != rows.shape:
+            raise ValueError(f"x0 must have the shape of rhs {tuple(rows.shape)}, got {tuple(starts.shape)}")
+        x, info = self._solve_rows(rows, rtol, max_iter, batch, starts)
+        infos = self._report(info, rtol)
+        x = x[:, self.pos]
+        return (x if isinstance(rhs, torch.Tensor) else x.cpu().numpy()), infos
+
     # -- posterior mean --------------------------------------------------------
     def _rhs(self, beta):
         yres = self.y if self.p == 0 else self.y - self.X @ torch.as_tensor(beta, dtype=torch.float64,
                                                                            device=self.device)
         return (self.d * yres).contiguous()
 
-    def gls_beta(self, rtol: float = 1e-8, max_iter: Optional[int] = None) -> np.ndarray:
+    def gls_beta(self, rtol: float = 1e-8, max_iter: Optional[int] = None, batch=None) -> np.ndarray:
         """GLS beta under V = C~ + tau2 H^-1 (C~ the NNGP covariance): V^-1 v = H v / tau2 - H A^-1 H v / tau4,
-        one solve per column of X; rows with h = 0 drop out."""
+        one solve per column of X, ``batch`` columns per batched solve; rows with h = 0 drop out."""
         if self.p == 0:
             return np.zeros(0)
-        S = torch.stack([self._solve((self.d * self.X[:, c]).contiguous(), rtol, max_iter)[0]
-                         for c in range(self.p)], dim=1)
+        rows = (self.d[:, None] * self.X).t()
+        S, info = self._solve_rows(rows, rtol, max_iter, self._batch(batch))
+        self._report(info, rtol)
+        S = S.t().contiguous()
         W = self.d[:, None] * (self.X - S)  # V^-1 X
         G = (self.X.t() @ W).cpu().numpy()
         g = (W.t() @ self.y).cpu().numpy()
@@ -221,30 +300,80 @@ class LatentPosterior:
         return w[self.pos].cpu().numpy(), beta
 
     # -- exact draws -----------------------------------------------------------
-    def sample(self, n_draws: int, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,
-               max_iter: Optional[int] = None) -> np.ndarray:
-        """``(n_draws, N)`` exact posterior draws w = A^-1 (b + eta), eta = (I - B)^T (sigma2 F)^-1/2 z1 +
-        (h / tau2)^1/2 z2.  The normals are Philox streams keyed by ``seed`` (``nngp_gibbs_normals``; one seed
-        repeats bit for bit), or ``z = (z1, z2)``, each (n_draws, N), for testing.  ``beta``: as :meth:`mean`."""
-        n_draws = int(n_draws)
-        if n_draws < 0:
-            raise ValueError("n_draws must be >= 0")
+    def _beta_for_draws(self, beta, rtol, max_iter):
         if beta is None:
             beta = self._beta_hat if self._beta_hat is not None else self.gls_beta(rtol, max_iter)
             self._beta_hat = beta
-        b = self._rhs(np.asarray(beta, dtype=np.float64).reshape(-1))
+        return np.asarray(beta, dtype=np.float64).reshape(-1)
+
+    def _draw_chunks(self, n_draws, seed, z, b, rtol, max_iter, batch):
+        """Yields ``(k0, W)``: the draws k0 .. k0 + W.shape[1] - 1 as storage-order columns (n, k <= batch) on the
+        device.  Draw k takes the Philox streams of sweep indices 2k and 2k + 1, whatever the chunking."""
         if z is not None:
             z1, z2 = (np.asarray(a, dtype=np.float64).reshape(n_draws, self.n) for a in z)
+        zz = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        for k0 in range(0, n_draws, batch):
+            kc = min(batch, n_draws - k0)
+            Z1 = torch.empty((self.n, kc), dtype=torch.float64, device=self.device)
+            Z2 = torch.empty_like(Z1)
+            for c in range(kc):
+                if z is None:
+                    Z1[:, c] = _lib.gibbs_normals(zz, seed, 2 * (k0 + c))
+                    Z2[:, c] = _lib.gibbs_normals(zz, seed, 2 * (k0 + c) + 1)
+                else:
+                    Z1[:, c], Z2[:, c] = self._in(z1[k0 + c], "z1"), self._in(z2[k0 + c], "z2")
+            eta = _lib.precision_sqrt_t_apply_batch(*self._geom(), Z1, Z2, d=self.d, workspace=self._batch_ws(kc))
+            W, info = self._solve_rows((b[:, None] + eta).t(), rtol, max_iter, kc)
+            self._report(info, rtol, first=k0)
+            yield k0, W.t().contiguous()
+
+    def sample(self, n_draws: int, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,
+               max_iter: Optional[int] = None, batch=None) -> np.ndarray:
+        """``(n_draws, N)`` exact posterior draws w = A^-1 (b + eta), eta = (I - B)^T (sigma2 F)^-1/2 z1 +
+        (h / tau2)^1/2 z2, ``batch`` draws per batched square-root application and solve (default
+        ``LATENT_MAX_RHS``; the draws do not depend on it).  The normals are Philox streams keyed by ``seed``
+        (``nngp_gibbs_normals``; one seed repeats bit for bit), or ``z = (z1, z2)``, each (n_draws, N), for
+        testing.  ``beta``: as :meth:`mean`."""
+        n_draws = int(n_draws)
+        if n_draws < 0:
+            raise ValueError("n_draws must be >= 0")
+        batch = self._batch(batch)
+        b = self._rhs(self._beta_for_draws(beta, rtol, max_iter))
         out = np.empty((n_draws, self.n))
-        zz1 = torch.empty(self.n, dtype=torch.float64, device=self.device)
-        zz2 = torch.empty_like(zz1)
-        for k in range(n_draws):
-            if z is None:
-                _lib.gibbs_normals(zz1, seed, 2 * k)
-                _lib.gibbs_normals(zz2, seed, 2 * k + 1)
-            else:
-                zz1, zz2 = self._in(z1[k], "z1"), self._in(z2[k], "z2")
-            eta = _lib.precision_sqrt_t_apply(*self._geom(), zz1, zz2, d=self.d)
-            w, _ = self._solve(b + eta, rtol, max_iter)
-            out[k] = w[self.pos].cpu().numpy()
+        for k0, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
+            out[k0:k0 + W.shape[1]] = W[self.pos].t().cpu().numpy()
         return out
+
+    # -- posterior uncertainty ---------------------------------------------------
+    def marginal_variance(self, n_draws: int = 64, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,
+                          max_iter: Optional[int] = None, batch=None) -> np.ndarray:
+        """``(N,)`` posterior variances of w by the Rao-Blackwellised estimator over ``n_draws`` >= 2 exact draws.
+        Given the rest of a draw w, w_i is Gaussian with mean c_i = w_i - (A w - b)_i / A_ii and variance 1 / A_ii,
+        so Var(w_i | y) = 1 / A_ii + Var(c_i), estimated by
+
+            v_i = 1 / A_ii + sum_k (c_i^(k) - c_bar_i)^2 / (K - 1).
+
+        Only the second part carries Monte-Carlo error (relative standard deviation sqrt(2 / (K - 1)) of that
+        part).  A w is one batched operator application per chunk of ``batch`` draws, A_ii comes from
+        ``nngp_precision_diag``; the sums run on the device, draw by draw in draw order (shifted by the first
+        draw's c, so nothing cancels), hence the result does not depend on ``batch``.  Arguments as :meth:`sample`."""
+        n_draws = int(n_draws)
+        if n_draws < 2:
+            raise ValueError("marginal_variance needs n_draws >= 2")
+        batch = self._batch(batch)
+        b = self._rhs(self._beta_for_draws(beta, rtol, max_iter))
+        aii = _lib.precision_diag(self._prep, self.n, self.m, self.cov.sigma2, d=self.d)
+        shift = None
+        s1 = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        s2 = torch.zeros_like(s1)
+        for _, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
+            AW = _lib.precision_apply_batch(*self._geom(), W, d=self.d, workspace=self._batch_ws(W.shape[1]))
+            C = W - (AW - b[:, None]) / aii[:, None]
+            if shift is None:
+                shift = C[:, 0].clone()
+            for c in range(C.shape[1]):
+                dev = C[:, c] - shift
+                s1 += dev
+                s2 += dev * dev
+        v = 1.0 / aii + (s2 - s1 * s1 / n_draws) / (n_draws - 1)
+        return v[self.pos].cpu().numpy()

@@ -879,6 +879,14 @@ class NNGP:
         Philox normals keyed by ``seed``).  refType 'S=T' only; arguments as :meth:`latent_mean`."""
         return self._latent_posterior(cov, mean).sample(n, seed=seed)
 
+    def latent_sd(self, n_draws: int = 64, cov: Optional[Covariance] = None, seed: int = 0,
+                  mean: str = "constant") -> np.ndarray:
+        """``(N,)`` posterior standard deviations of w | y, theta at a fixed ``cov``: the square root of
+        :meth:`pynngp_amd.LatentPosterior.marginal_variance` (Rao-Blackwellised over ``n_draws`` exact draws,
+        relative standard error about sqrt(2 / (n_draws - 1)) at worst).  refType 'S=T' only; arguments as
+        :meth:`latent_mean`."""
+        return np.sqrt(self._latent_posterior(cov, mean).marginal_variance(n_draws, seed=seed))
+
     def oneSample(self, seed: int = 0, X=None, **sampler_kw):
         """One Gibbs iteration of the response model y = X beta + w + eps: the reference's
         ``update_wt`` / ``update_ws`` / ``update_y_unobserved`` (nngp.py:98-101, which do not

@@ -24,6 +24,9 @@ for tracing.
     torch.ops.nngp.precision_apply(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # latent-field precision
     torch.ops.nngp.latent_cg(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
                              check_every=8) -> (x, info)                 # Jacobi-PCG for A x = b (a solver call)
+    torch.ops.nngp.precision_apply_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # x (n, nrhs <= 8)
+    torch.ops.nngp.latent_cg_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
+                                   check_every=8) -> (x, info)           # nrhs solves in lock step, info (nrhs, 4)
 
 ``kind`` / ``algo`` are the integer codes of include/nngp.h (:func:`kind_code`, :func:`algo_code`);
 ``nu`` is the smoothness of the ``matern`` kind (0 < nu <= 50; ignored by the other kinds).
@@ -122,6 +125,15 @@ def _register_fakes() -> None:
     @fake("latent_cg")
     def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
         raise RuntimeError("latent_cg is a solver call (it synchronises once per chunk of iterations): run it eagerly")
+
+    @fake("precision_apply_batch")
+    def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x):
+        return torch.empty_like(x)
+
+    @fake("latent_cg_batch")
+    def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
+        raise RuntimeError("latent_cg_batch is a solver call (it synchronises once per chunk of iterations): run it "
+                           "eagerly")
 
 
 def kind_code(kind: str) -> int:

@@ -9,8 +9,14 @@ Measures, on one GPU and in one process:
     two sparse products plus the diagonal scalings, after the same warm-up and with the same repeat count;
   * the CG iteration count and the wall time of the posterior mean to rtol 1e-8, beside what a Gibbs estimate
     of the same iteration count would cost at --gibbs-ms per sweep.
+With --nrhs K1,K2,... it measures the batched operator instead (nngp_precision_apply_batch, vectors (n, nrhs)):
+  * ms per batched application at each nrhs beside the single operator, both timed in this process in
+    alternating rounds (--rounds of them, each `reps` applications after `warmup`), with the spread over rounds;
+  * the wall time of 8 posterior draws through the batched path (LatentPosterior.sample) beside the loop of
+    single square-root applications and single solves that served before it, and of marginal_variance(64);
+  * the gate: one application at nrhs = 8 against 8 single applications.
 Synthetic data as bench.py (uniform coordinates, standard-normal values, seed 0); prints one JSON line.
-    python tools/bench_latent.py [--n 1000000 --m 15 --reps 1000 --warmup 100]
+    python tools/bench_latent.py [--n 1000000 --m 15 --reps 1000 --warmup 100] [--nrhs 1,2,4,8 --rounds 3]
 """
 import argparse
 import json
@@ -45,6 +51,86 @@ def timed(fn, warmup, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def sample_loop_single(lp, n_draws, seed, rtol):
+    """The draws as a loop over single right-hand sides: one square-root application, one CG solve and one
+    device-to-host copy per draw (what LatentPosterior.sample did before the batched solver)."""
+    import numpy as np
+
+    b = lp._rhs(())
+    out = np.empty((n_draws, lp.n))
+    z1 = torch.empty(lp.n, dtype=torch.float64, device=lp.device)
+    z2 = torch.empty_like(z1)
+    for k in range(n_draws):
+        _lib.gibbs_normals(z1, seed, 2 * k)
+        _lib.gibbs_normals(z2, seed, 2 * k + 1)
+        eta = _lib.precision_sqrt_t_apply(*lp._geom(), z1, z2, d=lp.d)
+        w, _ = lp._solve(b + eta, rtol, None)
+        out[k] = w[lp.pos].cpu().numpy()
+    return out
+
+
+def wall_ms(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(1e3 * (time.perf_counter() - t0))
+    return out
+
+
+def bench_batch(lp, args, res):
+    """The --nrhs measurement (see the module docstring); fills res."""
+    import numpy as np
+
+    n, m, dev = lp.n, lp.m, lp.device
+    geom = lp._geom()
+    gen = torch.Generator(dev).manual_seed(1)
+    x1 = torch.randn(n, dtype=torch.float64, device=dev, generator=gen)
+    o1 = torch.empty_like(x1)
+    variants = {"single": lambda: _lib.precision_apply(*geom, x1, d=lp.d, out=o1, workspace=lp._ws)}
+    for k in args.nrhs:
+        xk = torch.randn((n, k), dtype=torch.float64, device=dev, generator=gen)
+        ok = torch.empty_like(xk)
+        ws = _lib._workspace(_lib.load().nngp_precision_batch_workspace_bytes(n, k), dev)
+        variants[f"nrhs{k}"] = (lambda xk=xk, ok=ok, ws=ws:
+                                _lib.precision_apply_batch(*geom, xk, d=lp.d, out=ok, workspace=ws))
+    rounds = {name: [] for name in variants}
+    for r in range(args.rounds):  # alternating: every variant once per round
+        for name, fn in variants.items():
+            rounds[name].append(timed(fn, args.warmup if r == 0 else 10, args.reps))
+    med = {name: statistics.median(v) for name, v in rounds.items()}
+    spread = {name: max(v) - min(v) for name, v in rounds.items()}
+    res.update(rounds=args.rounds, operator_ms_rounds=rounds, operator_ms_median=med, operator_ms_spread=spread)
+    per = {}
+    for k in args.nrhs:
+        bpc = (24 * m + 60 * k) / k  # algorithmic bytes per location and column
+        per[str(k)] = {"ms": med[f"nrhs{k}"], "ms_per_column": med[f"nrhs{k}"] / k,
+                       "speedup_per_column_vs_single": med["single"] * k / med[f"nrhs{k}"],
+                       "algorithmic_bytes_per_location_and_column": bpc,
+                       "hbm_frac": bpc * k * n / (med[f"nrhs{k}"] * 1e-3) / HBM_PEAK}
+    res["batched"] = per
+    if 8 in args.nrhs:
+        margin = 8 * med["single"] - med["nrhs8"]
+        worst = 3 * max(8 * spread["single"], spread["nrhs8"])
+        res["gate_operator"] = {"eight_single_ms": 8 * med["single"], "one_nrhs8_ms": med["nrhs8"], "margin_ms": margin,
+                                "three_times_larger_spread_ms": worst, "passed": bool(margin > worst)}
+    # draws: the loop over single right-hand sides against the batched path, alternating; the same bits
+    ref = sample_loop_single(lp, 8, 0, args.rtol)
+    got = lp.sample(8, seed=0, rtol=args.rtol)
+    res["draws_bit_identical"] = bool(np.array_equal(ref, got))
+    loop_ms, batch_ms = [], []
+    for _ in range(args.rounds):
+        loop_ms += wall_ms(lambda: sample_loop_single(lp, 8, 0, args.rtol), 1)
+        batch_ms += wall_ms(lambda: lp.sample(8, seed=0, rtol=args.rtol), 1)
+    mv_ms = wall_ms(lambda: lp.marginal_variance(64, seed=0, rtol=args.rtol), 2)
+    res.update(sample8_single_loop_ms=loop_ms, sample8_batched_ms=batch_ms,
+               sample8_speedup=statistics.median(loop_ms) / statistics.median(batch_ms),
+               marginal_variance64_ms=mv_ms,
+               gate_sample={"passed": bool(statistics.median(batch_ms) <= statistics.median(loop_ms))})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -58,6 +144,9 @@ def main():
     ap.add_argument("--solves", type=int, default=5)
     ap.add_argument("--gibbs-ms", type=float, default=0.80, help="ms per Gibbs iteration to compare against")
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--nrhs", type=lambda v: [int(t) for t in v.split(",")], default=None,
+                    help="comma-separated column counts: measure the batched operator and the batched draws instead")
+    ap.add_argument("--rounds", type=int, default=3, help="alternating rounds per variant (--nrhs)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_latent needs a ROCm GPU (a timing without one says nothing)")
@@ -69,6 +158,14 @@ def main():
     lp = LatentPosterior(coords, y, Covariance("exponential", args.sigma2, args.phi, args.tau2), m=m, device=dev)
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t0
+
+    if args.nrhs:
+        res = {"workload": f"latent posterior, batched operator, N={n}, m={m}, exponential, sigma2={args.sigma2}, "
+                           f"phi={args.phi}, tau2={args.tau2}",
+               "setup_s": setup_s, "reps": args.reps, "warmup": args.warmup, "hbm_peak_GBps": HBM_PEAK / 1e9}
+        bench_batch(lp, args, res)
+        print(json.dumps(res))
+        return
 
     geom = lp._geom()
     x = torch.randn(n, dtype=torch.float64, device=dev, generator=torch.Generator(dev).manual_seed(1))
