@@ -524,6 +524,9 @@ int nngp_gibbs_stats(int64_t n, const double *r, const double *Ft, const double 
  *   p.Ap not above 0 or not finite, e.g. NaN in B), |r|^2, |b|^2 -- numerical outcomes are data, the
  *   return code stays NNGP_OK.  0 < rtol < 1, max_iter >= 0, check_every >= 1; workspace:
  *   nngp_latent_cg_workspace_bytes(n) bytes (0 for n < 0), 256-B aligned, no initialisation needed.
+ * These three calls are the _batch calls below at nrhs = 1, and their workspace sizes are the one-column
+ * batched sizes (nngp_precision_batch_workspace_bytes(n, 1), nngp_latent_cg_batch_workspace_bytes(n, 1)):
+ * query them, do not compute them.
  * ------------------------------------------------------------------------- */
 size_t nngp_precision_workspace_bytes(int64_t n);
 int nngp_precision_apply(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
@@ -543,8 +546,8 @@ int nngp_latent_cg(const int32_t *nbr, const double *B, const int32_t *off, cons
  * index and coefficient is read once for all columns and a gather fetches nrhs contiguous doubles.  Geometry,
  * prep, sigma2, d and the argument checks are those of the calls above (nrhs outside its range: NNGP_EINVAL).
  * THE CONTRACT: column c of every result is bit-identical to the single call on that column alone, for every
- * nrhs and whatever the other columns hold (the lane groups, tiles, grids and each column's expression
- * sequence are the single call's).
+ * nrhs and whatever the other columns hold (one kernel family serves every nrhs; the lane groups, tiles,
+ * grids and each column's expression sequence do not depend on it).
  * nngp_precision_apply_batch / nngp_precision_sqrt_t_apply_batch: out = A x / the square-root operator, per
  *   column; workspace: nngp_precision_batch_workspace_bytes(n, nrhs) bytes (0 for n < 0 or a bad nrhs); x
  *   (z1 / z2) and out must not alias.

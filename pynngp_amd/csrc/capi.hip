@@ -788,20 +788,67 @@ static int latent_common(const int32_t* nbr, const double* B, const int32_t* off
     return NNGP_OK;
 }
 
-size_t nngp_precision_workspace_bytes(int64_t n) { return n < 0 ? 0 : nngp::latent_apply_workspace_bytes(n); }
+// Each operation is written once, for vectors (n, nrhs); the single-vector entry points are its nrhs = 1.
+// `what` names the public call in the launch-failure message.
+static bool bad_nrhs(int32_t nrhs) { return nrhs < 1 || nrhs > NNGP_LATENT_MAX_RHS; }
+static int fail_nrhs(int32_t nrhs) {
+    return fail(NNGP_EINVAL, "nrhs=%d outside [1, %d]", nrhs, NNGP_LATENT_MAX_RHS);
+}
 
+size_t nngp_precision_batch_workspace_bytes(int64_t n, int32_t nrhs) {
+    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_apply_workspace_bytes(n, nrhs);
+}
+
+size_t nngp_precision_workspace_bytes(int64_t n) { return nngp_precision_batch_workspace_bytes(n, 1); }
+
+static int precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                           const void* prep, int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs,
+                           const double* x, double* out, void* workspace, size_t workspace_bytes, void* stream,
+                           const char* what) {
+    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    nngp::LatentGeom g;
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
+                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_apply_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return NNGP_OK;
+}
+
+// rev_k is unused by the latent calls: prep holds B in reverse-list order already
 int nngp_precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
                          const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
                          const double* x, double* out, void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;  // prep holds B in reverse-list order already
-    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
-    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    (void)rev_k;
+    return precision_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, x, out, workspace, workspace_bytes, stream,
+                           "precision_apply launch");
+}
+
+int nngp_precision_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                               const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                               const double* d, int32_t nrhs, const double* x, double* out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return precision_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, x, out, workspace, workspace_bytes,
+                           stream, "precision_apply_batch launch");
+}
+
+static int precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                  const void* prep, int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs,
+                                  const double* z1, const double* z2, double* out, void* workspace,
+                                  size_t workspace_bytes, void* stream, const char* what) {
+    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
+        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
+    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
     nngp::LatentGeom g;
     const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_workspace_bytes(n), &g);
+                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
     if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_apply_launch(g, x, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_apply launch");
+    hipError_t e = nngp::latent_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, what);
     return NNGP_OK;
 }
 
@@ -810,67 +857,8 @@ int nngp_precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32
                                 const double* d, const double* z1, const double* z2, double* out, void* workspace,
                                 size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
-        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
-    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_workspace_bytes(n), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_sqrt_t_apply_launch(g, z1, z2, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_sqrt_t_apply launch");
-    return NNGP_OK;
-}
-
-size_t nngp_latent_cg_workspace_bytes(int64_t n) { return n < 0 ? 0 : nngp::latent_cg_workspace_bytes(n); }
-
-int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                   const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
-                   const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every, double* info_host,
-                   void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    if (b == nullptr || x == nullptr || info_host == nullptr)
-        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
-    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
-    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
-    if (max_iter < 0 || check_every < 1)
-        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
-                    check_every);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_latent_cg_workspace_bytes(n), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_cg_run(g, b, x, rtol, max_iter, check_every, info_host, workspace,
-                                       (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "latent_cg");
-    return NNGP_OK;
-}
-
-// several right-hand sides: the single calls' checks, plus nrhs
-static bool bad_nrhs(int32_t nrhs) { return nrhs < 1 || nrhs > NNGP_LATENT_MAX_RHS; }
-static int fail_nrhs(int32_t nrhs) {
-    return fail(NNGP_EINVAL, "nrhs=%d outside [1, %d]", nrhs, NNGP_LATENT_MAX_RHS);
-}
-
-size_t nngp_precision_batch_workspace_bytes(int64_t n, int32_t nrhs) {
-    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_apply_batch_workspace_bytes(n, nrhs);
-}
-
-int nngp_precision_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                               const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
-                               const double* d, int32_t nrhs, const double* x, double* out, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
-    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_apply_batch_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_apply_batch launch");
-    return NNGP_OK;
+    return precision_sqrt_t_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, z1, z2, out, workspace,
+                                  workspace_bytes, stream, "precision_sqrt_t_apply launch");
 }
 
 int nngp_precision_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -878,28 +866,20 @@ int nngp_precision_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const
                                       const double* d, int32_t nrhs, const double* z1, const double* z2, double* out,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
-        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
-    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_sqrt_t_apply_batch_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_sqrt_t_apply_batch launch");
-    return NNGP_OK;
+    return precision_sqrt_t_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, z1, z2, out, workspace,
+                                  workspace_bytes, stream, "precision_sqrt_t_apply_batch launch");
 }
 
 size_t nngp_latent_cg_batch_workspace_bytes(int64_t n, int32_t nrhs) {
-    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_cg_batch_workspace_bytes(n, nrhs);
+    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_cg_workspace_bytes(n, nrhs);
 }
 
-int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
-                         int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every,
-                         double* info_host, void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;
+size_t nngp_latent_cg_workspace_bytes(int64_t n) { return nngp_latent_cg_batch_workspace_bytes(n, 1); }
+
+static int latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j, const void* prep,
+                     int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs, const double* b, double* x,
+                     double rtol, int64_t max_iter, int32_t check_every, double* info_host, void* workspace,
+                     size_t workspace_bytes, void* stream, const char* what) {
     if (b == nullptr || x == nullptr || info_host == nullptr)
         return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
     if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
@@ -912,10 +892,28 @@ int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off
     const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
                                  nngp_latent_cg_batch_workspace_bytes(n, nrhs), &g);
     if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_cg_batch_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
-                                             (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "latent_cg_batch");
+    hipError_t e = nngp::latent_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
+                                       (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, what);
     return NNGP_OK;
+}
+
+int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                   const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                   const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every, double* info_host,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return latent_cg(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, b, x, rtol, max_iter, check_every, info_host,
+                     workspace, workspace_bytes, stream, "latent_cg");
+}
+
+int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                         int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every,
+                         double* info_host, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return latent_cg(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, b, x, rtol, max_iter, check_every, info_host,
+                     workspace, workspace_bytes, stream, "latent_cg_batch");
 }
 
 int nngp_precision_diag(const void* prep, int64_t n, int32_t m, double sigma2, const double* d, double* out,

@@ -28,31 +28,23 @@ struct LatentGeom {
     const double* d;  // (n,) diagonal term, or null
 };
 
-size_t latent_apply_workspace_bytes(int64_t n);
-size_t latent_cg_workspace_bytes(int64_t n);
-// out = A x (workspace: latent_apply_workspace_bytes(n))
-hipError_t latent_apply_launch(const LatentGeom& g, const double* x, double* out, void* workspace, hipStream_t s);
-// out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2
-hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, const double* z1, const double* z2, double* out,
-                                      void* workspace, hipStream_t s);
-// Jacobi-PCG for A x = b from the start in x; info_host: iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2.
-// Synchronises the stream once per chunk of check_every iterations.
-hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s);
-
-// Several right-hand sides at once: vectors are (n, nrhs) row-major, 1 <= nrhs <= NNGP_LATENT_MAX_RHS.  Column c
-// of every result is bit-identical to the call above on that column alone, whatever the other columns hold.
-size_t latent_apply_batch_workspace_bytes(int64_t n, int nrhs);
-size_t latent_cg_batch_workspace_bytes(int64_t n, int nrhs);
-hipError_t latent_apply_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
-                                     hipStream_t s);
-hipError_t latent_sqrt_t_apply_batch_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2,
-                                            double* out, void* workspace, hipStream_t s);
-// nrhs Jacobi-PCG recurrences in lock step, each with its own scalars and stopping; info_host: (nrhs, 4) rows
-// as latent_cg_run's.  A finished column is frozen; the launches are no-ops once every column is finished.
-hipError_t latent_cg_batch_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol,
-                               int64_t max_iter, int check_every, double* info_host, void* workspace,
+// Vectors are (n, nrhs) row-major, 1 <= nrhs <= NNGP_LATENT_MAX_RHS; a single right-hand side is nrhs = 1.
+// Column c of every result depends on column c of the inputs alone, bit for bit, whatever nrhs is and whatever
+// the other columns hold.
+size_t latent_apply_workspace_bytes(int64_t n, int nrhs);
+size_t latent_cg_workspace_bytes(int64_t n, int nrhs);
+// out = A x (workspace: latent_apply_workspace_bytes(n, nrhs))
+hipError_t latent_apply_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
                                hipStream_t s);
+// out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2
+hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s);
+// nrhs Jacobi-PCG recurrences for A x = b in lock step from the start in x, each with its own scalars and
+// stopping; info_host: (nrhs, 4) rows of iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2.  A finished
+// column is frozen; the launches are no-ops once every column is finished.  Synchronises the stream once per
+// chunk of check_every iterations.
+hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s);
 // out_i = diag(A)_i = d_i + (invF_i + P_i) / sigma2 (d null: 0), the CG's preconditioner before its reciprocal
 hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
                               hipStream_t s);

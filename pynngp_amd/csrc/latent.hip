@@ -17,6 +17,15 @@
 //
 // The CG keeps alpha and beta on the device.  Its dots go through per-block records folded in a fixed
 // order by every block that needs the scalar (the same bits in each), so a solve is bit-reproducible.
+//
+// One kernel family serves every call.  Vectors are (n, nrhs) row-major, 1 <= nrhs <= kMaxRhs, a single
+// right-hand side being nrhs = 1: an index or coefficient is loaded once for all columns and a gather
+// fetches nrhs contiguous doubles.  The kernels are templates on KP, the padded column count (1, 2, 4, 8:
+// the smallest that holds nrhs): register arrays are indexed by compile-time constants only; a padding
+// column c >= nrhs re-reads column nrhs - 1 (a valid address, no branch around the load) and is never stored.
+// A column's bits depend neither on KP nor on the other columns: the lane groups, tiles, grids, thread ->
+// location and tile -> block mappings are the same for every KP, no arithmetic crosses columns, and each
+// column's expression sequence is one text (every multiply-add is an explicit fma or cannot fuse).
 #include "latent.h"
 
 #include <math.h>
@@ -34,6 +43,7 @@ constexpr int kColRows = kBlock / kColLanes;     // locations per tile
 constexpr int kLongList = 32 * kColLanes;        // a lane group's budget; longer lists go to the block
 constexpr int kMaxTileBlocks = 2048;             // persistent grid of the operator phases (= p.q records)
 constexpr int kMaxVecBlocks = 1024;              // grid of the CG's vector kernels (= records per dot)
+constexpr int kMaxRhs = NNGP_LATENT_MAX_RHS;
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -69,273 +79,40 @@ __device__ __forceinline__ void tile_range(int64_t n_tiles, int64_t* lo, int64_t
     *hi = (lb + 1) * n_tiles / nb;
 }
 
-// CG state words (doubles) at the end of the workspace
+// The column count as a KP instantiation sees it: the launch's nrhs, except that KP = 1 serves nrhs = 1 only
+// and knows it at compile time.  There the row stride is the constant 1 and the padding clamp and the store
+// guards fold away, which keeps the one-column kernels at the cost of kernels written for one vector.
+template <int KP>
+__device__ __forceinline__ int columns(int nrhs) {
+    return KP == 1 ? 1 : nrhs;
+}
+
+// the column that register slot c reads: its own, or column nrhs - 1 for a padding slot
+__device__ __forceinline__ int column_of(int c, int nrhs) { return c < nrhs ? c : nrhs - 1; }
+
+// CG state words (doubles) of one column; kMaxRhs such blocks end the workspace, followed by the two "every
+// column is finished" words for the even and the odd iterations (the operator launches' stop word)
 enum { kRz0 = 0, kRz1 = 1, kRr = 2, kBb = 3, kTol2 = 4, kAlpha = 5, kBeta = 6, kIter = 7, kStatus = 8, kFlag0 = 9,
        kFlag1 = 10, kBrk = 11, kStateWords = 32 };
+enum { kAll0 = kMaxRhs * kStateWords, kAll1 = kAll0 + 1 };
 
 // ---------------------------------------------------------------- row phase
 // G lanes per location (G = 4, 8 or 16 by m alone); lane l takes slots l, l + G, ...: the nbr and B rows are
 // read coalesced.  stop: null, or a device word that makes the launch a no-op when non-zero (a finished CG).
-template <int G>
+template <int G, int KP>
 __global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __restrict__ nbr,
                                                             const double* __restrict__ B,
                                                             const double* __restrict__ invF,
                                                             const double* __restrict__ x, double* __restrict__ t,
-                                                            int64_t n, int m, double inv_s2,
+                                                            int64_t n, int m, int nrhs, double inv_s2,
                                                             const double* __restrict__ stop) {
     if (stop != nullptr && *stop != 0.0) return;
-    constexpr int kRows = kBlock / G;
-    const int g = threadIdx.x / G, l = threadIdx.x % G;
-    int64_t lo, hi;
-    tile_range((n + kRows - 1) / kRows, &lo, &hi);
-    for (int64_t tile = lo; tile < hi; ++tile) {
-        const int64_t i = tile * kRows + g;
-        double acc = 0.0;
-        if (i < n) {
-            const int32_t* nb = nbr + i * m;
-            const double* bb = B + i * m;
-            for (int s = l; s < m; s += G) {
-                const int32_t j = nb[s];
-                if (j >= 0 && (int64_t)j < n) acc = fma(bb[s], x[j], acc);  // a slot without a point: exactly 0
-            }
-        }
-        acc = lane_group_sum<G>(acc);
-        if (i < n && l == 0) t[i] = (x[i] - acc) * (invF[i] * inv_s2);
-    }
-}
-
-// u_i = z1_i sqrt(invF_i / sigma2): the column phase's input for the square-root operator
-__global__ __launch_bounds__(kBlock) void latent_scale_kernel(const double* __restrict__ invF,
-                                                              const double* __restrict__ z1, double* __restrict__ u,
-                                                              int64_t n, double inv_s2) {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        u[i] = z1[i] * sqrt(invF[i] * inv_s2);
-}
-
-// ---------------------------------------------------------------- column phase
-// out_i = t_i - sum_e Brev[e] t[rev_j[e]] + dd_i x_i, dd = d (SQRT: sqrt(d)); d null: no diagonal term.
-// rec: null, or the block's record of sum_i x_i out_i (the CG's p.q) at rec[blockIdx.x].
-template <bool SQRT>
-__global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __restrict__ off,
-                                                            const int32_t* __restrict__ rev_j,
-                                                            const double* __restrict__ Brev,
-                                                            const double* __restrict__ t,
-                                                            const double* __restrict__ d,
-                                                            const double* __restrict__ x, double* __restrict__ out,
-                                                            int64_t n, double* __restrict__ rec,
-                                                            const double* __restrict__ stop) {
-    __shared__ int32_t sh_e0[kColRows], sh_e1[kColRows];
-    __shared__ double sh4[4];
-    if (stop != nullptr && *stop != 0.0) return;
-    const int g = threadIdx.x / kColLanes, l = threadIdx.x % kColLanes;
-    int64_t lo, hi;
-    tile_range((n + kColRows - 1) / kColRows, &lo, &hi);
-    double dot = 0.0;
-    for (int64_t tile = lo; tile < hi; ++tile) {
-        const int64_t i = tile * kColRows + g;
-        const bool live = i < n;
-        const int32_t e0 = live ? off[i] : 0, e1 = live ? off[i + 1] : 0;
-        const bool is_long = e1 - e0 > kLongList;
-        double acc = 0.0;
-        if (!is_long) {
-            for (int32_t e = e0 + l; e < e1; e += kColLanes) {
-                const int32_t j = rev_j[e];
-                if ((uint32_t)j < (uint64_t)n) acc = fma(Brev[e], t[j], acc);
-            }
-        }
-        acc = lane_group_sum<kColLanes>(acc);
-        if (__syncthreads_or(is_long)) {  // block-uniform; rare (hubs)
-            if (l == 0) {
-                sh_e0[g] = e0;
-                sh_e1[g] = is_long ? e1 : e0;
-            }
-            __syncthreads();
-            for (int k = 0; k < kColRows; ++k) {
-                const int32_t a0 = sh_e0[k], a1 = sh_e1[k];
-                if (a1 <= a0) continue;  // block-uniform
-                double s = 0.0;
-                for (int32_t e = a0 + (int32_t)threadIdx.x; e < a1; e += kBlock) {
-                    const int32_t j = rev_j[e];
-                    if ((uint32_t)j < (uint64_t)n) s = fma(Brev[e], t[j], s);
-                }
-                s = block_sum(s, sh4);
-                if (g == k) acc = s;
-            }
-            __syncthreads();
-        }
-        if (live && l == 0) {
-            double o = t[i] - acc;
-            const double xi = (d != nullptr || rec != nullptr) && x != nullptr ? x[i] : 0.0;
-            if (d != nullptr) o = fma(SQRT ? sqrt(d[i]) : d[i], xi, o);
-            out[i] = o;
-            dot = fma(xi, o, dot);
-        }
-    }
-    if (rec != nullptr) {
-        dot = block_sum(dot, sh4);
-        if (threadIdx.x == 0) rec[blockIdx.x] = dot;
-    }
-}
-
-// ---------------------------------------------------------------- CG vector kernels
-// diag(A)_i = d_i + (invF_i + P_i) / sigma2, the Jacobi preconditioner's and nngp_precision_diag's.  One fused
-// multiply-add, written out: it is what the compiler contracted the plain expression to, and every kernel that
-// needs the diagonal must get these bits whatever its surroundings.
-__device__ __forceinline__ double latent_diag(const double* __restrict__ d, const double* __restrict__ invF,
-                                              const double* __restrict__ P, double inv_s2, int64_t i) {
-    return fma(invF[i] + P[i], inv_s2, d != nullptr ? d[i] : 0.0);
-}
-
-// start: M^-1 = 1 / (d + (invF + P) / sigma2), r = b - A x0 (q holds A x0), z = M^-1 r, p = z; records of
-// r.z, r.r and b.b
-__global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(int64_t n, const double* __restrict__ b,
-                                                                const double* __restrict__ q,
-                                                                const double* __restrict__ d,
-                                                                const double* __restrict__ invF,
-                                                                const double* __restrict__ P, double inv_s2,
-                                                                double* __restrict__ r, double* __restrict__ z,
-                                                                double* __restrict__ p, double* __restrict__ Minv,
-                                                                double* __restrict__ rec) {
-    __shared__ double sh4[4];
-    double rz = 0.0, rr = 0.0, bb = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double mi = 1.0 / latent_diag(d, invF, P, inv_s2, i);
-        const double bi = b[i], ri = bi - q[i], zi = mi * ri;
-        Minv[i] = mi;
-        r[i] = ri;
-        z[i] = zi;
-        p[i] = zi;
-        rz = fma(ri, zi, rz);
-        rr = fma(ri, ri, rr);
-        bb = fma(bi, bi, bb);
-    }
-    rz = block_sum(rz, sh4);
-    rr = block_sum(rr, sh4);
-    bb = block_sum(bb, sh4);
-    if (threadIdx.x == 0) {
-        rec[blockIdx.x] = rz;
-        rec[kMaxVecBlocks + blockIdx.x] = rr;
-        rec[2 * kMaxVecBlocks + blockIdx.x] = bb;
-    }
-}
-
-// one block: fold the start's records into the state
-__global__ __launch_bounds__(kBlock) void latent_cg_start_kernel(const double* __restrict__ rec, int n_rec,
-                                                                 double rtol, double* __restrict__ st) {
-    __shared__ double sh4[4];
-    const double rz = fold_records(rec, n_rec, sh4);
-    const double rr = fold_records(rec + kMaxVecBlocks, n_rec, sh4);
-    const double bb = fold_records(rec + 2 * kMaxVecBlocks, n_rec, sh4);
-    if (threadIdx.x == 0) {
-        const double tol2 = rtol * rtol * bb;
-        const double done = rr <= tol2 ? 1.0 : 0.0;
-        st[kRz0] = rz;
-        st[kRz1] = 0.0;
-        st[kRr] = rr;
-        st[kBb] = bb;
-        st[kTol2] = tol2;
-        st[kAlpha] = st[kBeta] = 0.0;
-        st[kIter] = 0.0;
-        st[kStatus] = done;
-        st[kFlag0] = done;
-        st[kFlag1] = 0.0;
-        st[kBrk] = 0.0;
-    }
-}
-
-// iteration k, after q = A p and the p.q records: alpha = r.z / p.q (a breakdown -- p.q not above 0 or not
-// finite -- is flagged and nothing moves), x += alpha p, r -= alpha q, z = M^-1 r; records of r.z and r.r
-__global__ __launch_bounds__(kBlock) void latent_cg_update_kernel(int64_t n, int64_t k, const double* __restrict__ pq_rec,
-                                                                  int n_pq, const double* __restrict__ p,
-                                                                  const double* __restrict__ q,
-                                                                  const double* __restrict__ Minv,
-                                                                  double* __restrict__ x, double* __restrict__ r,
-                                                                  double* __restrict__ z, double* __restrict__ rec,
-                                                                  double* __restrict__ st) {
-    __shared__ double sh4[4];
-    if (st[kFlag0 + (k & 1)] != 0.0) return;
-    const double pq = fold_records(pq_rec, n_pq, sh4);
-    if (!(pq > 0.0) || pq > 1.7976931348623157e308) {  // not above 0, NaN or +inf
-        if (blockIdx.x == 0 && threadIdx.x == 0) st[kBrk] = 1.0;
-        return;
-    }
-    const double alpha = st[kRz0 + (k & 1)] / pq;
-    double rz = 0.0, rr = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        x[i] = fma(alpha, p[i], x[i]);
-        const double ri = fma(-alpha, q[i], r[i]);
-        const double zi = Minv[i] * ri;
-        r[i] = ri;
-        z[i] = zi;
-        rz = fma(ri, zi, rz);
-        rr = fma(ri, ri, rr);
-    }
-    rz = block_sum(rz, sh4);
-    rr = block_sum(rr, sh4);
-    if (threadIdx.x == 0) {
-        rec[blockIdx.x] = rz;
-        rec[kMaxVecBlocks + blockIdx.x] = rr;
-        if (blockIdx.x == 0) st[kAlpha] = alpha;
-    }
-}
-
-// iteration k, last launch: beta = r.z' / r.z, p = z + beta p; block 0 moves the state on (the scalars of
-// iteration k + 1 live in the other slot, so no block reads a word this launch writes)
-__global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, int64_t k, const double* __restrict__ rec,
-                                                                     int n_rec, const double* __restrict__ z,
-                                                                     double* __restrict__ p, double* __restrict__ st) {
-    __shared__ double sh4[4];
-    const int cur = (int)(k & 1), nxt = cur ^ 1;
-    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    const double flag = st[kFlag0 + cur];
-    if (flag != 0.0) {
-        if (lead) st[kFlag0 + nxt] = flag;
-        return;
-    }
-    if (st[kBrk] != 0.0) {
-        if (lead) st[kFlag0 + nxt] = st[kStatus] = -1.0;
-        return;
-    }
-    const double rz = fold_records(rec, n_rec, sh4);
-    const double rr = fold_records(rec + kMaxVecBlocks, n_rec, sh4);
-    const double beta = rz / st[kRz0 + cur];
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        p[i] = fma(beta, p[i], z[i]);
-    if (lead) {
-        const double done = rr <= st[kTol2] ? 1.0 : 0.0;
-        st[kRz0 + nxt] = rz;
-        st[kRr] = rr;
-        st[kBeta] = beta;
-        st[kIter] = (double)(k + 1);
-        st[kFlag0 + nxt] = st[kStatus] = done;
-    }
-}
-
-// ================================================================ several right-hand sides at once
-// Vectors are (n, nrhs) row-major, 1 <= nrhs <= kMaxRhs: an index or coefficient is loaded once for all
-// columns and a gather fetches nrhs contiguous doubles.  Column c of every kernel below is bit-identical to
-// the single-RHS kernel above run on that column alone: the lane groups, tiles, grids, thread -> location and
-// tile -> block mappings are the same, and so is each column's expression sequence (every multiply-add is an
-// explicit fma or cannot fuse).  KP is the padded column count (2, 4, 8): register arrays are indexed by
-// compile-time constants only; a padding column c >= nrhs re-reads column nrhs - 1 (a valid address, no
-// branch around the load) and is never stored.
-constexpr int kMaxRhs = NNGP_LATENT_MAX_RHS;
-enum { kAll0 = 0, kAll1 = 1 };  // the "every column finished" words, after the kMaxRhs per-column state blocks
-
-template <int G, int KP>
-__global__ __launch_bounds__(kBlock) void latent_row_batch_kernel(const int32_t* __restrict__ nbr,
-                                                                  const double* __restrict__ B,
-                                                                  const double* __restrict__ invF,
-                                                                  const double* __restrict__ x,
-                                                                  double* __restrict__ t, int64_t n, int m,
-                                                                  int nrhs, double inv_s2,
-                                                                  const double* __restrict__ stop) {
-    if (stop != nullptr && *stop != 0.0) return;
+    nrhs = columns<KP>(nrhs);
     constexpr int kRows = kBlock / G;
     const int g = threadIdx.x / G, l = threadIdx.x % G;
     int cc[KP];
 #pragma unroll
-    for (int c = 0; c < KP; ++c) cc[c] = c < nrhs ? c : nrhs - 1;
+    for (int c = 0; c < KP; ++c) cc[c] = column_of(c, nrhs);
     int64_t lo, hi;
     tile_range((n + kRows - 1) / kRows, &lo, &hi);
     for (int64_t tile = lo; tile < hi; ++tile) {
@@ -369,35 +146,36 @@ __global__ __launch_bounds__(kBlock) void latent_row_batch_kernel(const int32_t*
     }
 }
 
-// u[i, c] = z1[i, c] sqrt(invF_i / sigma2)
-__global__ __launch_bounds__(kBlock) void latent_scale_batch_kernel(const double* __restrict__ invF,
-                                                                    const double* __restrict__ z1,
-                                                                    double* __restrict__ u, int64_t n, int nrhs,
-                                                                    double inv_s2) {
+// u[i, c] = z1[i, c] sqrt(invF_i / sigma2): the column phase's input for the square-root operator
+__global__ __launch_bounds__(kBlock) void latent_scale_kernel(const double* __restrict__ invF,
+                                                              const double* __restrict__ z1, double* __restrict__ u,
+                                                              int64_t n, int nrhs, double inv_s2) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const double sc = sqrt(invF[i] * inv_s2);
         for (int c = 0; c < nrhs; ++c) u[i * nrhs + c] = z1[i * nrhs + c] * sc;
     }
 }
 
-// rec: null, or column c's record of the block at rec[c * kMaxTileBlocks + blockIdx.x]
+// ---------------------------------------------------------------- column phase
+// out_i = t_i - sum_e Brev[e] t[rev_j[e]] + dd_i x_i, dd = d (SQRT: sqrt(d)); d null: no diagonal term.
+// rec: null, or column c's record of sum_i x_i out_i (the CG's p.q) at rec[c * kMaxTileBlocks + blockIdx.x].
 template <bool SQRT, int KP>
-__global__ __launch_bounds__(kBlock) void latent_col_batch_kernel(const int32_t* __restrict__ off,
-                                                                  const int32_t* __restrict__ rev_j,
-                                                                  const double* __restrict__ Brev,
-                                                                  const double* __restrict__ t,
-                                                                  const double* __restrict__ d,
-                                                                  const double* __restrict__ x,
-                                                                  double* __restrict__ out, int64_t n, int nrhs,
-                                                                  double* __restrict__ rec,
-                                                                  const double* __restrict__ stop) {
+__global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __restrict__ off,
+                                                            const int32_t* __restrict__ rev_j,
+                                                            const double* __restrict__ Brev,
+                                                            const double* __restrict__ t,
+                                                            const double* __restrict__ d,
+                                                            const double* __restrict__ x, double* __restrict__ out,
+                                                            int64_t n, int nrhs, double* __restrict__ rec,
+                                                            const double* __restrict__ stop) {
     __shared__ int32_t sh_e0[kColRows], sh_e1[kColRows];
     __shared__ double sh4[4];
     if (stop != nullptr && *stop != 0.0) return;
+    nrhs = columns<KP>(nrhs);
     const int g = threadIdx.x / kColLanes, l = threadIdx.x % kColLanes;
     int cc[KP];
 #pragma unroll
-    for (int c = 0; c < KP; ++c) cc[c] = c < nrhs ? c : nrhs - 1;
+    for (int c = 0; c < KP; ++c) cc[c] = column_of(c, nrhs);
     int64_t lo, hi;
     tile_range((n + kColRows - 1) / kColRows, &lo, &hi);
     double dot[KP];
@@ -476,6 +254,15 @@ __global__ __launch_bounds__(kBlock) void latent_col_batch_kernel(const int32_t*
     }
 }
 
+// ---------------------------------------------------------------- the diagonal
+// diag(A)_i = d_i + (invF_i + P_i) / sigma2, the Jacobi preconditioner's and nngp_precision_diag's.  One fused
+// multiply-add, written out: it is what the compiler contracted the plain expression to, and every kernel that
+// needs the diagonal must get these bits whatever its surroundings.
+__device__ __forceinline__ double latent_diag(const double* __restrict__ d, const double* __restrict__ invF,
+                                              const double* __restrict__ P, double inv_s2, int64_t i) {
+    return fma(invF[i] + P[i], inv_s2, d != nullptr ? d[i] : 0.0);
+}
+
 // out_i = diag(A)_i
 __global__ __launch_bounds__(kBlock) void latent_diag_kernel(int64_t n, const double* __restrict__ d,
                                                              const double* __restrict__ invF,
@@ -485,22 +272,25 @@ __global__ __launch_bounds__(kBlock) void latent_diag_kernel(int64_t n, const do
         out[i] = latent_diag(d, invF, P, inv_s2, i);
 }
 
-// ---------------------------------------------------------------- batched CG: nrhs recurrences in lock step
-// Column c owns the state block st + c * kStateWords and the record rows rec + c * 3 * kMaxVecBlocks and
-// pq_rec + c * kMaxTileBlocks; the two words after the kMaxRhs state blocks say "every column is finished" for
-// the even and the odd iterations (the operator launches' stop word).  A finished column (converged or broken
-// down) is frozen: from then on none of its x, r, z, p or state is written.  M^-1 does not depend on the column.
+// ---------------------------------------------------------------- CG vector kernels
+// nrhs recurrences in lock step.  Column c owns the state block st + c * kStateWords and the record rows
+// rec + c * 3 * kMaxVecBlocks and pq_rec + c * kMaxTileBlocks.  A finished column (converged or broken down) is
+// frozen: from then on none of its x, r, z, p or state is written.  M^-1 does not depend on the column.
+//
+// start: M^-1 = 1 / (d + (invF + P) / sigma2), r = b - A x0 (q holds A x0), z = M^-1 r, p = z; records of
+// r.z, r.r and b.b
 template <int KP>
-__global__ __launch_bounds__(kBlock) void latent_cg_init_batch_kernel(
+__global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(
     int64_t n, int nrhs, const double* __restrict__ b, const double* __restrict__ q, const double* __restrict__ d,
     const double* __restrict__ invF, const double* __restrict__ P, double inv_s2, double* __restrict__ r,
     double* __restrict__ z, double* __restrict__ p, double* __restrict__ Minv, double* __restrict__ rec) {
     __shared__ double sh4[4];
+    nrhs = columns<KP>(nrhs);
     int cc[KP];
     double rz[KP], rr[KP], bb[KP];
 #pragma unroll
     for (int c = 0; c < KP; ++c) {
-        cc[c] = c < nrhs ? c : nrhs - 1;
+        cc[c] = column_of(c, nrhs);
         rz[c] = rr[c] = bb[c] = 0.0;
     }
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
@@ -533,9 +323,8 @@ __global__ __launch_bounds__(kBlock) void latent_cg_init_batch_kernel(
 }
 
 // one block: fold each column's start records into its state
-__global__ __launch_bounds__(kBlock) void latent_cg_start_batch_kernel(const double* __restrict__ rec, int n_rec,
-                                                                       int nrhs, double rtol,
-                                                                       double* __restrict__ st) {
+__global__ __launch_bounds__(kBlock) void latent_cg_start_kernel(const double* __restrict__ rec, int n_rec, int nrhs,
+                                                                 double rtol, double* __restrict__ st) {
     __shared__ double sh4[4];
     double all = 1.0;
     for (int c = 0; c < nrhs; ++c) {
@@ -562,26 +351,29 @@ __global__ __launch_bounds__(kBlock) void latent_cg_start_batch_kernel(const dou
         }
     }
     if (threadIdx.x == 0) {
-        st[kMaxRhs * kStateWords + kAll0] = all;
-        st[kMaxRhs * kStateWords + kAll1] = 0.0;
+        st[kAll0] = all;
+        st[kAll1] = 0.0;
     }
 }
 
+// iteration k, after q = A p and the p.q records: per column alpha = r.z / p.q (a breakdown -- p.q not above 0
+// or not finite -- is flagged in that column and nothing of it moves), x += alpha p, r -= alpha q, z = M^-1 r;
+// records of r.z and r.r
 template <int KP>
-__global__ __launch_bounds__(kBlock) void latent_cg_update_batch_kernel(
+__global__ __launch_bounds__(kBlock) void latent_cg_update_kernel(
     int64_t n, int nrhs, int64_t k, const double* __restrict__ pq_rec, int n_pq, const double* __restrict__ p,
     const double* __restrict__ q, const double* __restrict__ Minv, double* __restrict__ x, double* __restrict__ r,
     double* __restrict__ z, double* __restrict__ rec, double* __restrict__ st) {
     __shared__ double sh4[4];
     const int cur = (int)(k & 1);
-    if (st[kMaxRhs * kStateWords + kAll0 + cur] != 0.0) return;
+    nrhs = columns<KP>(nrhs);
     int cc[KP];
     bool act[KP];
     double alpha[KP], rz[KP], rr[KP];
     bool any = false;
 #pragma unroll
     for (int c = 0; c < KP; ++c) {
-        cc[c] = c < nrhs ? c : nrhs - 1;
+        cc[c] = column_of(c, nrhs);
         act[c] = false;
         alpha[c] = rz[c] = rr[c] = 0.0;
         if (c < nrhs) {  // block-uniform, as is everything read from the state
@@ -627,13 +419,15 @@ __global__ __launch_bounds__(kBlock) void latent_cg_update_batch_kernel(
     }
 }
 
+// iteration k, last launch: per column beta = r.z' / r.z, p = z + beta p; block 0 moves the states on (the
+// scalars of iteration k + 1 live in the other slot, so no block reads a word this launch writes)
 template <int KP>
-__global__ __launch_bounds__(kBlock) void latent_cg_direction_batch_kernel(int64_t n, int nrhs, int64_t k,
-                                                                           const double* __restrict__ rec, int n_rec,
-                                                                           const double* __restrict__ z,
-                                                                           double* __restrict__ p,
-                                                                           double* __restrict__ st) {
+__global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, int nrhs, int64_t k,
+                                                                     const double* __restrict__ rec, int n_rec,
+                                                                     const double* __restrict__ z,
+                                                                     double* __restrict__ p, double* __restrict__ st) {
     __shared__ double sh4[4];
+    nrhs = columns<KP>(nrhs);
     const int cur = (int)(k & 1), nxt = cur ^ 1;
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
     int cc[KP];
@@ -642,7 +436,7 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_batch_kernel(int64
     bool any = false, all_done = true;
 #pragma unroll
     for (int c = 0; c < KP; ++c) {
-        cc[c] = c < nrhs ? c : nrhs - 1;
+        cc[c] = column_of(c, nrhs);
         act[c] = false;
         beta[c] = 0.0;
         if (c < nrhs) {  // block-uniform
@@ -658,19 +452,19 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_batch_kernel(int64
                 const double rr = fold_records(rc + kMaxVecBlocks, n_rec, sh4);
                 beta[c] = rz / sc[kRz0 + cur];
                 act[c] = any = true;
-                const double done = rr <= sc[kTol2] ? 1.0 : 0.0;
-                if (done == 0.0) all_done = false;
+                const bool done = rr <= sc[kTol2];
+                if (!done) all_done = false;
                 if (lead) {
                     sc[kRz0 + nxt] = rz;
                     sc[kRr] = rr;
                     sc[kBeta] = beta[c];
                     sc[kIter] = (double)(k + 1);
-                    sc[kFlag0 + nxt] = sc[kStatus] = done;
+                    sc[kFlag0 + nxt] = sc[kStatus] = done ? 1.0 : 0.0;
                 }
             }
         }
     }
-    if (lead) st[kMaxRhs * kStateWords + kAll0 + nxt] = all_done ? 1.0 : 0.0;
+    if (lead) st[kAll0 + nxt] = all_done ? 1.0 : 0.0;
     if (!any) return;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
 #pragma unroll
@@ -682,6 +476,7 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_batch_kernel(int64
     }
 }
 
+// ---------------------------------------------------------------- launches
 int tile_blocks(int64_t n, int rows_per_tile) {
     const int64_t tiles = (n + rows_per_tile - 1) / rows_per_tile;
     return (int)(tiles < kMaxTileBlocks ? tiles : kMaxTileBlocks);
@@ -692,125 +487,13 @@ int vec_blocks(int64_t n) {
     return (int)(b < kMaxVecBlocks ? b : kMaxVecBlocks);
 }
 
-void row_launch(const LatentGeom& g, const double* x, double* t, const double* stop, hipStream_t s) {
-    const double inv_s2 = 1.0 / g.sigma2;
-    // lanes per location from m alone (part of the fixed summation order)
-    if (g.m <= 4)
-        hipLaunchKernelGGL(latent_row_kernel<4>, dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s, g.nbr, g.B,
-                           g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
-    else if (g.m <= 8)
-        hipLaunchKernelGGL(latent_row_kernel<8>, dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s, g.nbr, g.B,
-                           g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
-    else
-        hipLaunchKernelGGL(latent_row_kernel<16>, dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0, s, g.nbr,
-                           g.B, g.prep.invF, x, t, g.n, g.m, inv_s2, stop);
-}
-
-// the CG workspace: six vectors, the records, the state
-struct CgLayout {
-    double *t, *r, *z, *p, *q, *Minv, *rec, *pq_rec, *st;
-};
-
-CgLayout cg_layout(void* workspace, int64_t n) {
-    char* w = (char*)workspace;
-    const size_t v = align256((size_t)n * 8);
-    CgLayout L;
-    L.t = (double*)w;
-    L.r = (double*)(w + v);
-    L.z = (double*)(w + 2 * v);
-    L.p = (double*)(w + 3 * v);
-    L.q = (double*)(w + 4 * v);
-    L.Minv = (double*)(w + 5 * v);
-    w += 6 * v;
-    L.rec = (double*)w;
-    w += align256((size_t)3 * kMaxVecBlocks * 8);
-    L.pq_rec = (double*)w;
-    w += align256((size_t)kMaxTileBlocks * 8);
-    L.st = (double*)w;
-    return L;
-}
-
-}  // namespace
-
-size_t latent_apply_workspace_bytes(int64_t n) { return align256((size_t)(n > 0 ? n : 1) * 8); }
-
-size_t latent_cg_workspace_bytes(int64_t n) {
-    return 6 * align256((size_t)n * 8) + align256((size_t)3 * kMaxVecBlocks * 8) +
-           align256((size_t)kMaxTileBlocks * 8) + align256((size_t)kStateWords * 8);
-}
-
-hipError_t latent_apply_launch(const LatentGeom& g, const double* x, double* out, void* workspace, hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* t = (double*)workspace;
-    row_launch(g, x, t, nullptr, s);
-    hipLaunchKernelGGL(latent_col_kernel<false>, dim3(tile_blocks(g.n, kColRows)), dim3(kBlock), 0, s, g.off, g.rev_j,
-                       g.prep.Brev, t, g.d, x, out, g.n, (double*)nullptr, (const double*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, const double* z1, const double* z2, double* out,
-                                      void* workspace, hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* u = (double*)workspace;
-    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n,
-                       1.0 / g.sigma2);
-    hipLaunchKernelGGL(latent_col_kernel<true>, dim3(tile_blocks(g.n, kColRows)), dim3(kBlock), 0, s, g.off, g.rev_j,
-                       g.prep.Brev, u, g.d, z2, out, g.n, (double*)nullptr, (const double*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t latent_cg_run(const LatentGeom& g, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s) {
-    info_host[0] = 0.0;
-    info_host[1] = 1.0;
-    info_host[2] = info_host[3] = 0.0;
-    if (g.n == 0) return hipSuccess;
-    const CgLayout L = cg_layout(workspace, g.n);
-    const int nv = vec_blocks(g.n), nt = tile_blocks(g.n, kColRows);
-    const double inv_s2 = 1.0 / g.sigma2;
-    hipError_t e;
-    // r = b - A x0, z = M^-1 r, p = z
-    row_launch(g, x, L.t, nullptr, s);
-    hipLaunchKernelGGL(latent_col_kernel<false>, dim3(nt), dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev, L.t, g.d,
-                       (const double*)x, L.q, g.n, (double*)nullptr, (const double*)nullptr);
-    hipLaunchKernelGGL(latent_cg_init_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, b, (const double*)L.q, g.d,
-                       g.prep.invF, g.prep.P, inv_s2, L.r, L.z, L.p, L.Minv, L.rec);
-    hipLaunchKernelGGL(latent_cg_start_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, rtol, L.st);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    double st[kStateWords];
-    int64_t k = 0;
-    for (;;) {
-        // one chunk: no host synchronisation inside; a finished solve turns the remaining launches into no-ops
-        for (int c = 0; c < check_every && k < max_iter; ++c, ++k) {
-            const double* stop = L.st + kFlag0 + (k & 1);
-            row_launch(g, L.p, L.t, stop, s);
-            hipLaunchKernelGGL(latent_col_kernel<false>, dim3(nt), dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev,
-                               (const double*)L.t, g.d, (const double*)L.p, L.q, g.n, L.pq_rec, stop);
-            hipLaunchKernelGGL(latent_cg_update_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, k,
-                               (const double*)L.pq_rec, nt, (const double*)L.p, (const double*)L.q,
-                               (const double*)L.Minv, x, L.r, L.z, L.rec, L.st);
-            hipLaunchKernelGGL(latent_cg_direction_kernel, dim3(nv), dim3(kBlock), 0, s, g.n, k,
-                               (const double*)L.rec, nv, (const double*)L.z, L.p, L.st);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(st, L.st, sizeof st, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        if (st[kStatus] != 0.0 || k >= max_iter) break;
-    }
-    info_host[0] = st[kIter];
-    info_host[1] = st[kStatus];
-    info_host[2] = st[kRr];
-    info_host[3] = st[kBb];
-    return hipSuccess;
-}
-
-// ---------------------------------------------------------------- several right-hand sides: launches
-namespace {
-
 // KP: the padded column count of the instantiation that serves nrhs
 #define NNGP_LATENT_KP(nrhs, ...) \
     do {                          \
-        if ((nrhs) <= 2) {        \
+        if ((nrhs) == 1) {        \
+            constexpr int KP = 1; \
+            __VA_ARGS__;          \
+        } else if ((nrhs) <= 2) { \
             constexpr int KP = 2; \
             __VA_ARGS__;          \
         } else if ((nrhs) <= 4) { \
@@ -823,45 +506,44 @@ namespace {
     } while (0)
 
 template <int KP>
-void row_batch_launch_kp(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop,
-                         hipStream_t s) {
+void row_launch_kp(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop, hipStream_t s) {
     const double inv_s2 = 1.0 / g.sigma2;
+    // lanes per location from m alone (part of the fixed summation order)
     if (g.m <= 4)
-        hipLaunchKernelGGL((latent_row_batch_kernel<4, KP>), dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s,
-                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<4, KP>), dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s, g.nbr,
+                           g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
     else if (g.m <= 8)
-        hipLaunchKernelGGL((latent_row_batch_kernel<8, KP>), dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s,
-                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<8, KP>), dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s, g.nbr,
+                           g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
     else
-        hipLaunchKernelGGL((latent_row_batch_kernel<16, KP>), dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0,
-                           s, g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<16, KP>), dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
 }
 
-void row_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop,
-                      hipStream_t s) {
-    NNGP_LATENT_KP(nrhs, row_batch_launch_kp<KP>(g, nrhs, x, t, stop, s));
+void row_launch(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop, hipStream_t s) {
+    NNGP_LATENT_KP(nrhs, row_launch_kp<KP>(g, nrhs, x, t, stop, s));
 }
 
 template <bool SQRT>
-void col_batch_launch(const LatentGeom& g, int nrhs, const double* t, const double* x, double* out, double* rec,
-                      const double* stop, hipStream_t s) {
-    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_batch_kernel<SQRT, KP>), dim3(tile_blocks(g.n, kColRows)),
+void col_launch(const LatentGeom& g, int nrhs, const double* t, const double* x, double* out, double* rec,
+                const double* stop, hipStream_t s) {
+    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_kernel<SQRT, KP>), dim3(tile_blocks(g.n, kColRows)),
                                             dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev, t, g.d, x, out, g.n,
                                             nrhs, rec, stop));
 }
 
-// the batched CG workspace: six (n, nrhs) slots (M^-1, shared by the columns, uses n doubles of its own),
-// kMaxRhs rows of records, kMaxRhs state blocks and the block of the two "all finished" words
-struct CgBatchLayout {
+// the CG workspace: six (n, nrhs) slots (M^-1, shared by the columns, uses n doubles of its own), kMaxRhs rows
+// of records, kMaxRhs state blocks and the block of the two "all finished" words
+struct CgLayout {
     double *t, *r, *z, *p, *q, *Minv, *rec, *pq_rec, *st;
 };
 
-constexpr size_t kBatchStateWords = (size_t)(kMaxRhs + 1) * kStateWords;
+constexpr size_t kCgStateWords = (size_t)(kMaxRhs + 1) * kStateWords;
 
-CgBatchLayout cg_batch_layout(void* workspace, int64_t n, int nrhs) {
+CgLayout cg_layout(void* workspace, int64_t n, int nrhs) {
     char* w = (char*)workspace;
     const size_t v = align256((size_t)n * nrhs * 8);
-    CgBatchLayout L;
+    CgLayout L;
     L.t = (double*)w;
     L.r = (double*)(w + v);
     L.z = (double*)(w + 2 * v);
@@ -879,31 +561,29 @@ CgBatchLayout cg_batch_layout(void* workspace, int64_t n, int nrhs) {
 
 }  // namespace
 
-size_t latent_apply_batch_workspace_bytes(int64_t n, int nrhs) {
-    return align256((size_t)(n > 0 ? n : 1) * nrhs * 8);
-}
+size_t latent_apply_workspace_bytes(int64_t n, int nrhs) { return align256((size_t)(n > 0 ? n : 1) * nrhs * 8); }
 
-size_t latent_cg_batch_workspace_bytes(int64_t n, int nrhs) {
+size_t latent_cg_workspace_bytes(int64_t n, int nrhs) {
     return 6 * align256((size_t)n * nrhs * 8) + align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8) +
-           align256((size_t)kMaxRhs * kMaxTileBlocks * 8) + align256(kBatchStateWords * 8);
+           align256((size_t)kMaxRhs * kMaxTileBlocks * 8) + align256(kCgStateWords * 8);
 }
 
-hipError_t latent_apply_batch_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
-                                     hipStream_t s) {
+hipError_t latent_apply_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
+                               hipStream_t s) {
     if (g.n == 0) return hipSuccess;
     double* t = (double*)workspace;
-    row_batch_launch(g, nrhs, x, t, nullptr, s);
-    col_batch_launch<false>(g, nrhs, t, x, out, nullptr, nullptr, s);
+    row_launch(g, nrhs, x, t, nullptr, s);
+    col_launch<false>(g, nrhs, t, x, out, nullptr, nullptr, s);
     return hipGetLastError();
 }
 
-hipError_t latent_sqrt_t_apply_batch_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2,
-                                            double* out, void* workspace, hipStream_t s) {
+hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s) {
     if (g.n == 0) return hipSuccess;
     double* u = (double*)workspace;
-    hipLaunchKernelGGL(latent_scale_batch_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n,
-                       nrhs, 1.0 / g.sigma2);
-    col_batch_launch<true>(g, nrhs, u, z2, out, nullptr, nullptr, s);
+    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n, nrhs,
+                       1.0 / g.sigma2);
+    col_launch<true>(g, nrhs, u, z2, out, nullptr, nullptr, s);
     return hipGetLastError();
 }
 
@@ -915,49 +595,47 @@ hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, 
     return hipGetLastError();
 }
 
-hipError_t latent_cg_batch_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol,
-                               int64_t max_iter, int check_every, double* info_host, void* workspace,
-                               hipStream_t s) {
+hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s) {
     for (int c = 0; c < nrhs; ++c) {
         info_host[4 * c + 0] = 0.0;
         info_host[4 * c + 1] = 1.0;
         info_host[4 * c + 2] = info_host[4 * c + 3] = 0.0;
     }
     if (g.n == 0) return hipSuccess;
-    const CgBatchLayout L = cg_batch_layout(workspace, g.n, nrhs);
+    const CgLayout L = cg_layout(workspace, g.n, nrhs);
     const int nv = vec_blocks(g.n), nt = tile_blocks(g.n, kColRows);
     const double inv_s2 = 1.0 / g.sigma2;
-    double* all = L.st + kMaxRhs * kStateWords + kAll0;
     hipError_t e;
     // r = b - A x0, z = M^-1 r, p = z, per column
-    row_batch_launch(g, nrhs, x, L.t, nullptr, s);
-    col_batch_launch<false>(g, nrhs, L.t, x, L.q, nullptr, nullptr, s);
-    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_init_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n, nrhs, b,
+    row_launch(g, nrhs, x, L.t, nullptr, s);
+    col_launch<false>(g, nrhs, L.t, x, L.q, nullptr, nullptr, s);
+    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_init_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n, nrhs, b,
                                             (const double*)L.q, g.d, g.prep.invF, g.prep.P, inv_s2, L.r, L.z, L.p,
                                             L.Minv, L.rec));
-    hipLaunchKernelGGL(latent_cg_start_batch_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, nrhs, rtol,
+    hipLaunchKernelGGL(latent_cg_start_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, nrhs, rtol,
                        L.st);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    double st[kBatchStateWords];
+    double st[kCgStateWords];
     int64_t k = 0;
     for (;;) {
         // one chunk: no host synchronisation inside; once every column is finished the launches are no-ops
         for (int c = 0; c < check_every && k < max_iter; ++c, ++k) {
-            const double* stop = all + (k & 1);
-            row_batch_launch(g, nrhs, L.p, L.t, stop, s);
-            col_batch_launch<false>(g, nrhs, L.t, L.p, L.q, L.pq_rec, stop, s);
-            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_update_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0, s,
-                                                    g.n, nrhs, k, (const double*)L.pq_rec, nt, (const double*)L.p,
+            const double* stop = L.st + kAll0 + (k & 1);
+            row_launch(g, nrhs, L.p, L.t, stop, s);
+            col_launch<false>(g, nrhs, L.t, L.p, L.q, L.pq_rec, stop, s);
+            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_update_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n,
+                                                    nrhs, k, (const double*)L.pq_rec, nt, (const double*)L.p,
                                                     (const double*)L.q, (const double*)L.Minv, x, L.r, L.z, L.rec,
                                                     L.st));
-            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_direction_batch_kernel<KP>, dim3(nv), dim3(kBlock), 0,
-                                                    s, g.n, nrhs, k, (const double*)L.rec, nv, (const double*)L.z,
-                                                    L.p, L.st));
+            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_direction_kernel<KP>, dim3(nv), dim3(kBlock), 0, s,
+                                                    g.n, nrhs, k, (const double*)L.rec, nv, (const double*)L.z, L.p,
+                                                    L.st));
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = hipMemcpyAsync(st, L.st, sizeof st, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        if (st[kMaxRhs * kStateWords + kAll0 + (k & 1)] != 0.0 || k >= max_iter) break;
+        if (st[kAll0 + (k & 1)] != 0.0 || k >= max_iter) break;
     }
     for (int c = 0; c < nrhs; ++c) {
         const double* sc = st + c * kStateWords;

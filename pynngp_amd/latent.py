@@ -130,8 +130,7 @@ class LatentPosterior:
         self.B = torch.empty((n, self.m), dtype=torch.float64, device=dev)
         self.F = torch.empty(n, dtype=torch.float64, device=dev)
         self._prep = None
-        self._ws = _lib._workspace(_lib.load().nngp_latent_cg_workspace_bytes(n), dev)
-        self._ws_batch = None  # the batched solver's workspace, made on first use for the widest chunk so far
+        self._ws_batch = None  # the operator's and solver's workspace, made on first use for the widest chunk so far
         self.update(cov)
 
     # -- theta -----------------------------------------------------------------
@@ -164,7 +163,8 @@ class LatentPosterior:
     # -- the operator and the solver -------------------------------------------
     def matvec(self, x):
         """A x (two gathers, bit-reproducible)."""
-        return self._out(_lib.precision_apply(*self._geom(), self._in(x, "x"), d=self.d, workspace=self._ws), x)
+        return self._out(_lib.precision_apply(*self._geom(), self._in(x, "x"), d=self.d, workspace=self._batch_ws(1)),
+                         x)
 
     def _solve(self, rhs, rtol, max_iter, x0=None):
         """Storage-order solve: (x, SolveInfo); raises on a breakdown, warns on non-convergence."""
@@ -174,7 +174,7 @@ class LatentPosterior:
             max_iter = min(max(2 * self.n, 1000), 20000)
         x = torch.zeros_like(rhs) if x0 is None else x0.clone()
         _, info = _lib.latent_cg(*self._geom(), rhs, x, d=self.d, rtol=rtol, max_iter=int(max_iter),
-                                 check_every=CHECK_EVERY, workspace=self._ws)
+                                 check_every=CHECK_EVERY, workspace=self._batch_ws(1))
         if info[1] < 0:
             raise NNGPNumericalError(f"CG breakdown after {int(info[0])} iterations: p.Ap is not positive and finite "
                                      "(NaN or inf in the factors or the right-hand side?)")

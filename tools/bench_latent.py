@@ -89,7 +89,8 @@ def bench_batch(lp, args, res):
     gen = torch.Generator(dev).manual_seed(1)
     x1 = torch.randn(n, dtype=torch.float64, device=dev, generator=gen)
     o1 = torch.empty_like(x1)
-    variants = {"single": lambda: _lib.precision_apply(*geom, x1, d=lp.d, out=o1, workspace=lp._ws)}
+    ws1 = lp._batch_ws(1)
+    variants = {"single": lambda: _lib.precision_apply(*geom, x1, d=lp.d, out=o1, workspace=ws1)}
     for k in args.nrhs:
         xk = torch.randn((n, k), dtype=torch.float64, device=dev, generator=gen)
         ok = torch.empty_like(xk)
@@ -170,7 +171,8 @@ def main():
     geom = lp._geom()
     x = torch.randn(n, dtype=torch.float64, device=dev, generator=torch.Generator(dev).manual_seed(1))
     out = torch.empty_like(x)
-    op_ms = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws), args.warmup, args.reps)
+    ws1 = lp._batch_ws(1)
+    op_ms = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=ws1), args.warmup, args.reps)
     bpl = bytes_per_location(m)
     res = {"workload": f"latent posterior, N={n}, m={m}, exponential, sigma2={args.sigma2}, phi={args.phi}, "
                        f"tau2={args.tau2}",
@@ -198,11 +200,11 @@ def main():
             return o.addcmul_(lp.d[:, None], x2)
 
         ref = stock()[:, 0]  # (a torch build without sparse CSR products on the GPU fails here, loudly)
-        _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws)
+        _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=ws1)
         res["baseline_max_rel_diff"] = float(((out - ref).abs().max() / ref.abs().max()).item())
         base_ms = timed(stock, args.warmup, args.reps)
         # alternate once more, to see the spread of both on a shared machine
-        op_ms2 = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=lp._ws), 10, args.reps)
+        op_ms2 = timed(lambda: _lib.precision_apply(*geom, x, d=lp.d, out=out, workspace=ws1), 10, args.reps)
         base_ms2 = timed(stock, 10, args.reps)
         res.update(baseline="torch.sparse_csr_tensor fp64: (I - B) x, scale, (I - B)^T t, + d x",
                    baseline_ms=base_ms, operator_ms_repeat=op_ms2, baseline_ms_repeat=base_ms2,
