@@ -578,6 +578,70 @@ int nngp_latent_cg_batch(const int32_t *nbr, const double *B, const int32_t *off
 int nngp_precision_diag(const void *prep, int64_t n, int32_t m, double sigma2, const double *d, double *out,
                         void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Latent-field posterior on a reference set (S != T), the leaves integrated out.  The reference's refType
+ * ('subset', nRef) / ('random', nRef, bounds) puts the field on n_s reference points; a data location outside
+ * S is a leaf whose parents are all reference points.  Nodes 0 .. n_s - 1 are the reference points, n_s ..
+ * n - 1 the leaves; every entry of nbr (n, m) indexes a reference point or is -1 (an index >= n_s is treated
+ * as -1 on the device).  B, F, off / rev_j / rev_k and prep are those of the n-node DAG, built by
+ * nngp_bf_sweep / nngp_bf_cross, nngp_reverse_neighbors and nngp_gibbs_prepare as they stand; d (n,) or NULL
+ * holds h / tau2 per node, 0 on a node without an observation.  With f_r = invF_r / sigma2, v the centred
+ * response and, per leaf j, g_j = f_j d_j / (f_j + d_j) (exactly 0 where d_j = 0), the leaves drop out in
+ * closed form and
+ *   A_S = (I - B_S)^T diag(f_S) (I - B_S) + diag(d_S) + B_L^T diag(g) B_L,   b_S = d_S v_S + B_L^T (g v_L),
+ *   w_S | y ~ N(A_S^-1 b_S, A_S^-1),   w_j | w_S, y ~ N((f_j B_j w_S + d_j v_j) / (f_j + d_j), 1 / (f_j + d_j)),
+ * the S-marginal of the posterior over all n nodes.  Vectors on S are (n_s, nrhs) row-major, vectors on all
+ * nodes (n, nrhs), vectors on the leaves (n - n_s, nrhs); 1 <= nrhs <= NNGP_LATENT_MAX_RHS, nrhs = 1 being the
+ * single call.  Checks as the calls above, and 0 <= n_s <= n.  The same kernel family serves these calls (the
+ * row scale is f on a reference row and g on a leaf row, a leaf row has no self term, the reverse-list phase
+ * runs over the first n_s nodes): sums keep a fixed order that depends on (m, the list's length, n, n_s) only,
+ * no atomics, and column c of every result is bit-identical to the one-column call.
+ * THE CONTRACT: with n_s = n every call below equals its _batch counterpart above bit for bit.
+ * nngp_precision_ref_apply_batch: out = A_S x.  workspace: nngp_precision_ref_batch_workspace_bytes(n, n_s,
+ *   nrhs) bytes (0 for bad arguments), 256-B aligned; it serves the next three calls too.
+ * nngp_precision_ref_sqrt_t_apply_batch: out = (I - B_S)^T f_S^1/2 z1_S + B_L^T g^1/2 z1_L + d_S^1/2 z2 with z1
+ *   (n, nrhs) and z2 (n_s, nrhs) (NULL allowed when d is): Cov(out) = A_S for standard normals.
+ * nngp_precision_ref_fold_batch: out = d_S v_S + B_L^T (g v_L) for v (n, nrhs): b_S of the centred response.
+ * nngp_precision_ref_diag: out (n_s,) = diag(A_S)_i = d_i + f_i + sum over children c of B_ci^2 s_c (s = f for a
+ *   reference child, g for a leaf), summed in the reverse-list phase's order; workspace as at nrhs = 1.
+ * nngp_latent_ref_cg_batch: nngp_latent_cg_batch on A_S x = b, preconditioned by that diagonal: the same four
+ *   launches per iteration, per-column state, freezing, check_every and info_host (HOST, nrhs x 4).  workspace:
+ *   nngp_latent_ref_cg_batch_workspace_bytes(n, n_s, nrhs) bytes: one (n, nrhs) and four (n_s, nrhs) vectors
+ *   where the n-node system needs six (n, nrhs).
+ * nngp_latent_ref_leaves_batch: the leaves given x (n_s, nrhs) on S: out = (f a + d v) / (f + d) [+ z /
+ *   sqrt(f + d)], a = B_L x summed as the row phase sums; v, z: (n - n_s, nrhs) or NULL (v NULL: 0; z NULL: the
+ *   conditional mean, else a conditional draw for standard normal z).  d NULL: out = a [+ z / sqrt(f)], kriging
+ *   of nrhs fields to unobserved leaves -- prediction points are such leaves.  One launch, no workspace; off,
+ *   rev_j and rev_k are not read.
+ * ------------------------------------------------------------------------- */
+size_t nngp_precision_ref_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs);
+int nngp_precision_ref_apply_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                   const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
+                                   double sigma2, const double *d, int32_t nrhs, const double *x, double *out,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int nngp_precision_ref_sqrt_t_apply_batch(const int32_t *nbr, const double *B, const int32_t *off,
+                                          const int32_t *rev_j, const int32_t *rev_k, const void *prep, int64_t n,
+                                          int64_t n_s, int32_t m, double sigma2, const double *d, int32_t nrhs,
+                                          const double *z1, const double *z2, double *out, void *workspace,
+                                          size_t workspace_bytes, void *stream);
+int nngp_precision_ref_fold_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                  const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
+                                  double sigma2, const double *d, int32_t nrhs, const double *v, double *out,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int nngp_precision_ref_diag(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                            const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
+                            const double *d, double *out, void *workspace, size_t workspace_bytes, void *stream);
+size_t nngp_latent_ref_cg_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs);
+int nngp_latent_ref_cg_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                             const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
+                             const double *d, int32_t nrhs, const double *b, double *x, double rtol, int64_t max_iter,
+                             int32_t check_every, double *info_host, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int nngp_latent_ref_leaves_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                 const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
+                                 double sigma2, const double *d, int32_t nrhs, const double *x, const double *v,
+                                 const double *z, double *out, void *stream);
+
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident
  * partials of a finished sweep, returns NNGP_OK, NNGP_ENOTPD with *first_bad_row = the

@@ -81,6 +81,14 @@ SYMBOLS = (
     "nngp_latent_cg_batch_workspace_bytes",
     "nngp_latent_cg_batch",
     "nngp_precision_diag",
+    "nngp_precision_ref_batch_workspace_bytes",
+    "nngp_precision_ref_apply_batch",
+    "nngp_precision_ref_sqrt_t_apply_batch",
+    "nngp_precision_ref_fold_batch",
+    "nngp_precision_ref_diag",
+    "nngp_latent_ref_cg_batch_workspace_bytes",
+    "nngp_latent_ref_cg_batch",
+    "nngp_latent_ref_leaves_batch",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -241,6 +249,24 @@ def load() -> ctypes.CDLL:
     lib.nngp_latent_cg_batch.restype = ctypes.c_int
     lib.nngp_precision_diag.argtypes = [P, I64, I32, D, P, P, P]
     lib.nngp_precision_diag.restype = ctypes.c_int
+    lib.nngp_precision_ref_batch_workspace_bytes.argtypes = [I64, I64, I32]
+    lib.nngp_precision_ref_batch_workspace_bytes.restype = SZ
+    lib.nngp_precision_ref_apply_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, SZ, P]
+    lib.nngp_precision_ref_apply_batch.restype = ctypes.c_int
+    lib.nngp_precision_ref_sqrt_t_apply_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, P, SZ,
+                                                          P]
+    lib.nngp_precision_ref_sqrt_t_apply_batch.restype = ctypes.c_int
+    lib.nngp_precision_ref_fold_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, SZ, P]
+    lib.nngp_precision_ref_fold_batch.restype = ctypes.c_int
+    lib.nngp_precision_ref_diag.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, P, P, SZ, P]
+    lib.nngp_precision_ref_diag.restype = ctypes.c_int
+    lib.nngp_latent_ref_cg_batch_workspace_bytes.argtypes = [I64, I64, I32]
+    lib.nngp_latent_ref_cg_batch_workspace_bytes.restype = SZ
+    lib.nngp_latent_ref_cg_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, D, I64, I32, P, P, SZ,
+                                             P]
+    lib.nngp_latent_ref_cg_batch.restype = ctypes.c_int
+    lib.nngp_latent_ref_leaves_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, P, P]
+    lib.nngp_latent_ref_leaves_batch.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1328,4 +1354,145 @@ def precision_diag(prep: torch.Tensor, n: int, m: int, sigma2: float, d: Optiona
     out = torch.empty(n, dtype=torch.float64, device=dev) if out is None else out
     _check(lib.nngp_precision_diag(_ptr(prep), n, m, float(sigma2), _ptr(d), _ptr(out), _stream(dev)),
            "nngp_precision_diag")
+    return out
+
+
+# ---- a reference set with the leaves integrated out (include/nngp.h: "Latent-field posterior on a reference set")
+def _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, **vectors):
+    """Checks of the reference-set calls.  ``vectors``: name -> (tensor or None, rows), rows one of "s" (n_s),
+    "n" (all nodes) or "l" (the leaves); the first one given fixes nrhs.  Returns (device, n, n_s, m, nrhs)."""
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    n, n_s = nbr.shape[0], int(n_s)
+    if not 0 <= n_s <= n:
+        raise ValueError(f"need 0 <= n_s <= n = {n}, got n_s={n_s}")
+    rows = {"s": n_s, "n": n, "l": n - n_s}
+    nrhs = None
+    for name, (t, kind) in vectors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != rows[kind] or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous float64 ({rows[kind]}, nrhs), got {t.dtype} {tuple(t.shape)}")
+        if nrhs is None:
+            nrhs = t.shape[1]
+            if not 1 <= nrhs <= LATENT_MAX_RHS:
+                raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
+        elif t.shape[1] != nrhs:
+            raise ValueError(f"{name} must have nrhs={nrhs} columns, got {t.shape[1]}")
+    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, d)
+    _require_gpu(nbr, *[t for t, _ in vectors.values()])
+    return dev, n, n_s, m, nrhs
+
+
+def _ref_ws(lib, dev, n, n_s, nrhs, workspace, cg=False):
+    need = (lib.nngp_latent_ref_cg_batch_workspace_bytes if cg else lib.nngp_precision_ref_batch_workspace_bytes)(
+        n, n_s, nrhs)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    return workspace
+
+
+def precision_ref_apply_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, x: torch.Tensor,
+                              d: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = A_S x for ``x`` (n_s, nrhs) on the n-node DAG whose first ``n_s`` nodes are the reference set
+    (nngp_precision_ref_apply_batch): A_S = (I - B_S)^T f_S (I - B_S) + d_S + B_L^T g B_L, the leaves integrated
+    out.  ``d`` (n,) or None.  With n_s = n it equals :func:`precision_apply_batch` bit for bit."""
+    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, x=(x, "s"), out=(out, "s"))
+    lib = load()
+    out = torch.empty_like(x) if out is None else out
+    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
+    _check(lib.nngp_precision_ref_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
+                                              n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(out),
+                                              _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_precision_ref_apply_batch")
+    return out
+
+
+def precision_ref_sqrt_t_apply_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, z1: torch.Tensor,
+                                     z2: Optional[torch.Tensor] = None, d: Optional[torch.Tensor] = None,
+                                     out: Optional[torch.Tensor] = None,
+                                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (n_s, nrhs) = (I - B_S)^T f_S^1/2 z1_S + B_L^T g^1/2 z1_L + d_S^1/2 z2 for ``z1`` (n, nrhs) and ``z2``
+    (n_s, nrhs) (nngp_precision_ref_sqrt_t_apply_batch): Cov(out) = A_S for standard normals."""
+    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, z1=(z1, "n"), z2=(z2, "s"),
+                                       out=(out, "s"))
+    if d is not None and z2 is None:
+        raise ValueError("z2 is needed when d is given")
+    lib = load()
+    out = torch.empty((n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
+    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
+    _check(lib.nngp_precision_ref_sqrt_t_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k),
+                                                     _ptr(prep), n, n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(z1),
+                                                     _ptr(z2), _ptr(out), _ptr(workspace), workspace.numel(),
+                                                     _stream(dev)), "nngp_precision_ref_sqrt_t_apply_batch")
+    return out
+
+
+def precision_ref_fold_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, v: torch.Tensor,
+                             d: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                             workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (n_s, nrhs) = d_S v_S + B_L^T (g v_L) for ``v`` (n, nrhs) on all nodes (nngp_precision_ref_fold_batch):
+    the right-hand side b_S of the mean when v is the centred response."""
+    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, v=(v, "n"), out=(out, "s"))
+    lib = load()
+    out = torch.empty((n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
+    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
+    _check(lib.nngp_precision_ref_fold_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
+                                             n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(v), _ptr(out),
+                                             _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_precision_ref_fold_batch")
+    return out
+
+
+def precision_ref_diag(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, d: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """diag(A_S) (n_s,) (nngp_precision_ref_diag): d_i + f_i + sum over children of B^2 s, the expression whose
+    reciprocal preconditions :func:`latent_ref_cg_batch`."""
+    if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != (int(n_s),) or not out.is_contiguous()):
+        raise ValueError(f"out must be contiguous float64 ({int(n_s)},)")
+    dev, n, n_s, m, _ = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d)
+    _require_gpu(nbr, out)
+    lib = load()
+    out = torch.empty(n_s, dtype=torch.float64, device=dev) if out is None else out
+    workspace = _ref_ws(lib, dev, n, n_s, 1, workspace)
+    _check(lib.nngp_precision_ref_diag(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, n_s, m,
+                                       float(sigma2), _ptr(d), _ptr(out), _ptr(workspace), workspace.numel(),
+                                       _stream(dev)), "nngp_precision_ref_diag")
+    return out
+
+
+def latent_ref_cg_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, b: torch.Tensor, x: torch.Tensor,
+                        d: Optional[torch.Tensor] = None, rtol: float = 1e-8, max_iter: int = 1000,
+                        check_every: int = 8, workspace: Optional[torch.Tensor] = None):
+    """nrhs Jacobi-PCG solves of A_S x = b in lock step, in place on ``x`` (n_s, nrhs) (nngp_latent_ref_cg_batch);
+    ``(x, info)`` as :func:`latent_cg_batch`."""
+    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, b=(b, "s"), x=(x, "s"))
+    if b is None or x is None:
+        raise ValueError("b and x are needed")
+    lib = load()
+    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace, cg=True)
+    info = np.zeros((nrhs, 4), dtype=np.float64)
+    _check(lib.nngp_latent_ref_cg_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, n_s,
+                                        m, float(sigma2), _ptr(d), nrhs, _ptr(b), _ptr(x), float(rtol), int(max_iter),
+                                        int(check_every), info.ctypes.data_as(ctypes.c_void_p), _ptr(workspace),
+                                        workspace.numel(), _stream(dev)), "nngp_latent_ref_cg_batch")
+    return x, info
+
+
+def latent_ref_leaves_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, x: torch.Tensor,
+                            v: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None,
+                            d: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The leaves given ``x`` (n_s, nrhs) on the reference set (nngp_latent_ref_leaves_batch): out (n - n_s, nrhs) =
+    (f a + d v) / (f + d) [+ z / sqrt(f + d)], a = B_L x; ``v``, ``z`` (n - n_s, nrhs) or None.  ``d`` None: out =
+    a [+ z / sqrt(f)], kriging of the nrhs fields to unobserved leaves."""
+    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, x=(x, "s"), v=(v, "l"), z=(z, "l"),
+                                       out=(out, "l"))
+    if x is None:
+        raise ValueError("x is needed")
+    lib = load()
+    out = torch.empty((n - n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
+    _check(lib.nngp_latent_ref_leaves_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
+                                            n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(v), _ptr(z),
+                                            _ptr(out), _stream(dev)), "nngp_latent_ref_leaves_batch")
     return out

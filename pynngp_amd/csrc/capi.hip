@@ -931,6 +931,143 @@ int nngp_precision_diag(const void* prep, int64_t n, int32_t m, double sigma2, c
     return NNGP_OK;
 }
 
+// ---- a reference set with the leaves integrated out: latent_common's checks plus 0 <= n_s <= n
+static int latent_ref_common(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                             const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2, const double* d,
+                             int32_t nrhs, void* workspace, size_t workspace_bytes, size_t need,
+                             nngp::LatentGeom* g) {
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    if (n < 0 || n_s < 0 || n_s > n)
+        return fail(NNGP_EINVAL, "need 0 <= n_s <= n (got n_s=%lld, n=%lld)", (long long)n_s, (long long)n);
+    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes, need, g);
+    if (rc != NNGP_OK) return rc;
+    g->n_s = n_s;
+    g->s = nullptr;
+    return NNGP_OK;
+}
+
+static bool bad_ref(int64_t n, int64_t n_s, int32_t nrhs) { return n < 0 || n_s < 0 || n_s > n || bad_nrhs(nrhs); }
+
+size_t nngp_precision_ref_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
+    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_apply_workspace_bytes(n, n_s, nrhs);
+}
+
+size_t nngp_latent_ref_cg_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
+    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_cg_workspace_bytes(n, n_s, nrhs);
+}
+
+int nngp_precision_ref_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                   const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m,
+                                   double sigma2, const double* d, int32_t nrhs, const double* x, double* out,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_ref_apply_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_ref_apply_batch launch");
+    return NNGP_OK;
+}
+
+int nngp_precision_ref_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off,
+                                          const int32_t* rev_j, const int32_t* rev_k, const void* prep, int64_t n,
+                                          int64_t n_s, int32_t m, double sigma2, const double* d, int32_t nrhs,
+                                          const double* z1, const double* z2, double* out, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
+        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
+    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_ref_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_ref_sqrt_t_apply_batch launch");
+    return NNGP_OK;
+}
+
+int nngp_precision_ref_fold_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                  const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m,
+                                  double sigma2, const double* d, int32_t nrhs, const double* v, double* out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (v == nullptr || out == nullptr) return fail(NNGP_EINVAL, "v and out must be non-null");
+    if (v == out) return fail(NNGP_EINVAL, "v and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_ref_fold_launch(g, nrhs, v, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_ref_fold_batch launch");
+    return NNGP_OK;
+}
+
+int nngp_precision_ref_diag(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                            const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
+                            const double* d, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    if (out == nullptr) return fail(NNGP_EINVAL, "out must be non-null");
+    nngp::LatentGeom g;
+    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, 1, workspace, workspace_bytes,
+                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, 1), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_ref_diag_launch(g, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "precision_ref_diag launch");
+    return NNGP_OK;
+}
+
+int nngp_latent_ref_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                             const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
+                             const double* d, int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                             int32_t check_every, double* info_host, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    (void)rev_k;
+    if (b == nullptr || x == nullptr || info_host == nullptr)
+        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
+    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
+    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
+    if (max_iter < 0 || check_every < 1)
+        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
+                    check_every);
+    nngp::LatentGeom g;
+    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                     nngp_latent_ref_cg_batch_workspace_bytes(n, n_s, nrhs), &g);
+    if (rc != NNGP_OK) return rc;
+    hipError_t e = nngp::latent_ref_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "latent_ref_cg_batch");
+    return NNGP_OK;
+}
+
+int nngp_latent_ref_leaves_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                 const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m,
+                                 double sigma2, const double* d, int32_t nrhs, const double* x, const double* v,
+                                 const double* z, double* out, void* stream) {
+    (void)off;
+    (void)rev_j;
+    (void)rev_k;
+    if (nbr == nullptr || B == nullptr || prep == nullptr) return fail(NNGP_EINVAL, "nbr, B and prep must be non-null");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    if (n < 0 || n_s < 0 || n_s > n)
+        return fail(NNGP_EINVAL, "need 0 <= n_s <= n (got n_s=%lld, n=%lld)", (long long)n_s, (long long)n);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
+        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
+    if (((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
+    if (n > n_s && (out == nullptr || (n_s > 0 && x == nullptr)))
+        return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (out != nullptr && (out == x || out == v || out == z)) return fail(NNGP_EINVAL, "out must not alias an input");
+    nngp::LatentGeom g{nbr, B, off, rev_j, nngp::latent_prep_view(prep, n, m), n, m, sigma2, d, n_s, nullptr};
+    hipError_t e = nngp::latent_ref_leaves_launch(g, nrhs, x, v, z, out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "latent_ref_leaves_batch launch");
+    return NNGP_OK;
+}
+
 size_t nngp_row_order_workspace_bytes(int64_t n_rows) { return nngp::row_order_workspace_bytes(n_rows); }
 
 int nngp_row_order(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, int32_t m, int64_t i0,

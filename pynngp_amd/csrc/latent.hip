@@ -26,6 +26,16 @@
 // A column's bits depend neither on KP nor on the other columns: the lane groups, tiles, grids, thread ->
 // location and tile -> block mappings are the same for every KP, no arithmetic crosses columns, and each
 // column's expression sequence is one text (every multiply-add is an explicit fma or cannot fuse).
+//
+// A reference set (S != T): nodes 0 .. n_s - 1 are reference points, n_s .. n - 1 leaves whose parents are all
+// reference points.  A leaf is conditionally independent of everything else given S and is integrated out, which
+// leaves the posterior of w_S alone, with L the stacked [(I - B_S); -B_L] and s the row scale (f_r = invF_r /
+// sigma2 on a reference row, g_r = f_r d_r / (f_r + d_r) on a leaf row):
+//   A_S = L^T diag(s) L + diag(d_S),   b_S = d_S v_S + B_L^T (g v_L)
+// This is the same two-phase operator written over the n-node structure: the REF instantiations of the row and
+// column kernels take the row scale from the vector s, give a leaf row no self term (its x is implicitly 0) and
+// run the column phase over the first n_s nodes only, whose reverse lists hold both kinds of children.  The
+// S = T instantiations (REF = false) are the text they were.
 #include "latent.h"
 
 #include <math.h>
@@ -99,14 +109,17 @@ enum { kAll0 = kMaxRhs * kStateWords, kAll1 = kAll0 + 1 };
 // ---------------------------------------------------------------- row phase
 // G lanes per location (G = 4, 8 or 16 by m alone); lane l takes slots l, l + G, ...: the nbr and B rows are
 // read coalesced.  stop: null, or a device word that makes the launch a no-op when non-zero (a finished CG).
-template <int G, int KP>
+// REF: x has n_s rows, t all n; `invF` is the row scale s itself (inv_s2 unused); a slot naming a node >= n_s
+// counts as -1; a leaf row i >= n_s has no self term: t_i = -s_i sum_s B[i,s] x[nbr[i,s]].
+template <int G, int KP, bool REF>
 __global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __restrict__ nbr,
                                                             const double* __restrict__ B,
                                                             const double* __restrict__ invF,
                                                             const double* __restrict__ x, double* __restrict__ t,
                                                             int64_t n, int m, int nrhs, double inv_s2,
-                                                            const double* __restrict__ stop) {
+                                                            const double* __restrict__ stop, int64_t n_s) {
     if (stop != nullptr && *stop != 0.0) return;
+    const int64_t nx = REF ? n_s : n;  // rows of x
     nrhs = columns<KP>(nrhs);
     constexpr int kRows = kBlock / G;
     const int g = threadIdx.x / G, l = threadIdx.x % G;
@@ -125,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __res
             const double* bb = B + i * m;
             for (int s = l; s < m; s += G) {
                 const int32_t j = nb[s];
-                if (j >= 0 && (int64_t)j < n) {  // a slot without a point: exactly 0 in every column
+                if (j >= 0 && (int64_t)j < nx) {  // a slot without a point: exactly 0 in every column
                     const double b = bb[s];
                     const double* xj = x + (int64_t)j * nrhs;
 #pragma unroll
@@ -136,12 +149,13 @@ __global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __res
 #pragma unroll
         for (int c = 0; c < KP; ++c) acc[c] = lane_group_sum<G>(acc[c]);
         if (i < n && l == 0) {
-            const double sc = invF[i] * inv_s2;
-            const double* xi = x + i * nrhs;
+            const double sc = REF ? invF[i] : invF[i] * inv_s2;
+            const bool self = !REF || i < nx;
+            const double* xi = x + (self ? i : 0) * nrhs;
             double* ti = t + i * nrhs;
 #pragma unroll
             for (int c = 0; c < KP; ++c)
-                if (c < nrhs) ti[c] = (xi[c] - acc[c]) * sc;
+                if (c < nrhs) ti[c] = ((self ? xi[c] : 0.0) - acc[c]) * sc;
         }
     }
 }
@@ -156,10 +170,47 @@ __global__ __launch_bounds__(kBlock) void latent_scale_kernel(const double* __re
     }
 }
 
+// The row scale of a reference-set system: s_i = invF_i / sigma2 on a reference row, g_i = f_i d_i / (f_i + d_i)
+// on a leaf row (exactly 0 where d_i = 0 or d is null: a leaf without data drops out)
+__global__ __launch_bounds__(kBlock) void latent_ref_s_kernel(const double* __restrict__ invF,
+                                                              const double* __restrict__ d, double* __restrict__ s,
+                                                              int64_t n, int64_t n_s, double inv_s2) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double f = invF[i] * inv_s2;
+        double v = f;
+        if (i >= n_s) {
+            const double di = d != nullptr ? d[i] : 0.0;
+            v = di == 0.0 ? 0.0 : f * di / (f + di);
+        }
+        s[i] = v;
+    }
+}
+
+// The column phase's input over all n nodes for the two maps that start from a given vector z (n, nrhs):
+//   FOLD   u = 0 on a reference row, -s z on a leaf row:        the column phase gives d_S z_S + B_L^T (g z_L)
+//   !FOLD  u = sqrt(s) z on a reference row, -sqrt(s) z on a leaf row:  ... (I - B_S)^T f^1/2 z_S + B_L^T g^1/2 z_L
+template <bool FOLD>
+__global__ __launch_bounds__(kBlock) void latent_ref_scale_kernel(const double* __restrict__ s,
+                                                                  const double* __restrict__ z,
+                                                                  double* __restrict__ u, int64_t n, int64_t n_s,
+                                                                  int nrhs) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const bool leaf = i >= n_s;
+        const double a = FOLD ? s[i] : sqrt(s[i]);
+        const double sc = leaf ? -a : (FOLD ? 0.0 : a);
+        for (int c = 0; c < nrhs; ++c) u[i * nrhs + c] = z[i * nrhs + c] * sc;
+    }
+}
+
 // ---------------------------------------------------------------- column phase
-// out_i = t_i - sum_e Brev[e] t[rev_j[e]] + dd_i x_i, dd = d (SQRT: sqrt(d)); d null: no diagonal term.
+// out_i = t_i - sum_e Brev[e] t[rev_j[e]] + dd_i x_i, dd = d (kColSqrt: sqrt(d)); d null: no diagonal term.
 // rec: null, or column c's record of sum_i x_i out_i (the CG's p.q) at rec[c * kMaxTileBlocks + blockIdx.x].
-template <bool SQRT, int KP>
+// REF: the nodes are the first n of the n_t that t covers (S = T: n_t is not read).
+// kColDiag (one column, t = the row scale s): out_i = (s_i + sum_e Brev[e]^2 s[rev_j[e]]) + d_i, the diagonal of
+// A_S, its sum in this phase's order.
+enum { kColApply = 0, kColSqrt = 1, kColDiag = 2 };
+
+template <int MODE, int KP, bool REF>
 __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __restrict__ off,
                                                             const int32_t* __restrict__ rev_j,
                                                             const double* __restrict__ Brev,
@@ -167,11 +218,13 @@ __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __res
                                                             const double* __restrict__ d,
                                                             const double* __restrict__ x, double* __restrict__ out,
                                                             int64_t n, int nrhs, double* __restrict__ rec,
-                                                            const double* __restrict__ stop) {
+                                                            const double* __restrict__ stop, int64_t n_t) {
     __shared__ int32_t sh_e0[kColRows], sh_e1[kColRows];
     __shared__ double sh4[4];
+    constexpr bool SQRT = MODE == kColSqrt;
     if (stop != nullptr && *stop != 0.0) return;
     nrhs = columns<KP>(nrhs);
+    const int64_t nt = REF ? n_t : n;  // rows of t
     const int g = threadIdx.x / kColLanes, l = threadIdx.x % kColLanes;
     int cc[KP];
 #pragma unroll
@@ -192,8 +245,8 @@ __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __res
         if (!is_long) {
             for (int32_t e = e0 + l; e < e1; e += kColLanes) {
                 const int32_t j = rev_j[e];
-                if ((uint32_t)j < (uint64_t)n) {
-                    const double b = Brev[e];
+                if ((uint32_t)j < (uint64_t)nt) {
+                    const double b = MODE == kColDiag ? Brev[e] * Brev[e] : Brev[e];
                     const double* tj = t + (int64_t)j * nrhs;
 #pragma unroll
                     for (int c = 0; c < KP; ++c) acc[c] = fma(b, tj[cc[c]], acc[c]);
@@ -216,8 +269,8 @@ __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __res
                 for (int c = 0; c < KP; ++c) s[c] = 0.0;
                 for (int32_t e = a0 + (int32_t)threadIdx.x; e < a1; e += kBlock) {
                     const int32_t j = rev_j[e];
-                    if ((uint32_t)j < (uint64_t)n) {
-                        const double b = Brev[e];
+                    if ((uint32_t)j < (uint64_t)nt) {
+                        const double b = MODE == kColDiag ? Brev[e] * Brev[e] : Brev[e];
                         const double* tj = t + (int64_t)j * nrhs;
 #pragma unroll
                         for (int c = 0; c < KP; ++c) s[c] = fma(b, tj[cc[c]], s[c]);
@@ -237,6 +290,10 @@ __global__ __launch_bounds__(kBlock) void latent_col_kernel(const int32_t* __res
             if (d != nullptr) dd = SQRT ? sqrt(d[i]) : d[i];
 #pragma unroll
             for (int c = 0; c < KP; ++c) {
+                if (MODE == kColDiag) {
+                    out[i] = (t[i] + acc[c]) + dd;
+                    continue;
+                }
                 double o = t[i * nrhs + cc[c]] - acc[c];
                 const double xi = want_x ? x[i * nrhs + cc[c]] : 0.0;
                 if (d != nullptr) o = fma(dd, xi, o);
@@ -278,8 +335,8 @@ __global__ __launch_bounds__(kBlock) void latent_diag_kernel(int64_t n, const do
 // frozen: from then on none of its x, r, z, p or state is written.  M^-1 does not depend on the column.
 //
 // start: M^-1 = 1 / (d + (invF + P) / sigma2), r = b - A x0 (q holds A x0), z = M^-1 r, p = z; records of
-// r.z, r.r and b.b
-template <int KP>
+// r.z, r.r and b.b.  REF: `P` is the diagonal of A_S itself (latent_col_kernel<kColDiag>), d and invF unread.
+template <int KP, bool REF>
 __global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(
     int64_t n, int nrhs, const double* __restrict__ b, const double* __restrict__ q, const double* __restrict__ d,
     const double* __restrict__ invF, const double* __restrict__ P, double inv_s2, double* __restrict__ r,
@@ -294,7 +351,7 @@ __global__ __launch_bounds__(kBlock) void latent_cg_init_kernel(
         rz[c] = rr[c] = bb[c] = 0.0;
     }
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double mi = 1.0 / latent_diag(d, invF, P, inv_s2, i);
+        const double mi = 1.0 / (REF ? P[i] : latent_diag(d, invF, P, inv_s2, i));
         Minv[i] = mi;
 #pragma unroll
         for (int c = 0; c < KP; ++c) {
@@ -476,6 +533,67 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, 
     }
 }
 
+// ---------------------------------------------------------------- the leaves given w_S
+// Leaf j = n_s + r, r in [0, n_l): w_j | w_S, y ~ N((f_j a_j + d_j v_j) / (f_j + d_j), 1 / (f_j + d_j)), a_j =
+// sum_s B[j,s] x[nbr[j,s]] in the row phase's lane groups and order, f_j = invF_j / sigma2.
+//   out[r, c] = (f_j a_j + d_j v[r, c]) / (f_j + d_j)  [+ z[r, c] / sqrt(f_j + d_j)]
+// v, z: (n_l, nrhs) or null (v null: 0).  d null: no data on any leaf, out = a_j as it stands (kriging of the
+// nrhs fields x) [+ z / sqrt(f_j)].
+template <int G, int KP>
+__global__ __launch_bounds__(kBlock) void latent_leaf_kernel(const int32_t* __restrict__ nbr,
+                                                             const double* __restrict__ B,
+                                                             const double* __restrict__ invF,
+                                                             const double* __restrict__ d,
+                                                             const double* __restrict__ x,
+                                                             const double* __restrict__ v,
+                                                             const double* __restrict__ z, double* __restrict__ out,
+                                                             int64_t n, int64_t n_s, int m, int nrhs, double inv_s2) {
+    nrhs = columns<KP>(nrhs);
+    constexpr int kRows = kBlock / G;
+    const int g = threadIdx.x / G, l = threadIdx.x % G;
+    const int64_t n_l = n - n_s;
+    int cc[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) cc[c] = column_of(c, nrhs);
+    int64_t lo, hi;
+    tile_range((n_l + kRows - 1) / kRows, &lo, &hi);
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t r = tile * kRows + g, i = n_s + r;
+        double acc[KP];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = 0.0;
+        if (r < n_l) {
+            const int32_t* nb = nbr + i * m;
+            const double* bb = B + i * m;
+            for (int s = l; s < m; s += G) {
+                const int32_t j = nb[s];
+                if (j >= 0 && (int64_t)j < n_s) {
+                    const double b = bb[s];
+                    const double* xj = x + (int64_t)j * nrhs;
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) acc[c] = fma(b, xj[cc[c]], acc[c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c) acc[c] = lane_group_sum<G>(acc[c]);
+        if (r < n_l && l == 0) {
+            const double f = invF[i] * inv_s2;
+            const double di = d != nullptr ? d[i] : 0.0;
+            const double prec = f + di;
+            const double sd = z != nullptr ? 1.0 / sqrt(prec) : 0.0;
+#pragma unroll
+            for (int c = 0; c < KP; ++c) {
+                const int64_t e = r * nrhs + cc[c];
+                double o = acc[c];
+                if (d != nullptr) o = fma(f, acc[c], di * (v != nullptr ? v[e] : 0.0)) / prec;
+                if (z != nullptr) o = fma(z[e], sd, o);
+                if (c < nrhs) out[r * nrhs + c] = o;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launches
 int tile_blocks(int64_t n, int rows_per_tile) {
     const int64_t tiles = (n + rows_per_tile - 1) / rows_per_tile;
@@ -505,40 +623,76 @@ int vec_blocks(int64_t n) {
         }                         \
     } while (0)
 
-template <int KP>
+// g.s != null: a reference-set system (the REF instantiations; vectors have g.n_s rows, t has g.n)
+template <int KP, bool REF>
 void row_launch_kp(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop, hipStream_t s) {
     const double inv_s2 = 1.0 / g.sigma2;
+    const double* scale = REF ? g.s : g.prep.invF;
     // lanes per location from m alone (part of the fixed summation order)
     if (g.m <= 4)
-        hipLaunchKernelGGL((latent_row_kernel<4, KP>), dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s, g.nbr,
-                           g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<4, KP, REF>), dim3(tile_blocks(g.n, kBlock / 4)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, scale, x, t, g.n, g.m, nrhs, inv_s2, stop, g.n_s);
     else if (g.m <= 8)
-        hipLaunchKernelGGL((latent_row_kernel<8, KP>), dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s, g.nbr,
-                           g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<8, KP, REF>), dim3(tile_blocks(g.n, kBlock / 8)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, scale, x, t, g.n, g.m, nrhs, inv_s2, stop, g.n_s);
     else
-        hipLaunchKernelGGL((latent_row_kernel<16, KP>), dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0, s,
-                           g.nbr, g.B, g.prep.invF, x, t, g.n, g.m, nrhs, inv_s2, stop);
+        hipLaunchKernelGGL((latent_row_kernel<16, KP, REF>), dim3(tile_blocks(g.n, kBlock / 16)), dim3(kBlock), 0, s,
+                           g.nbr, g.B, scale, x, t, g.n, g.m, nrhs, inv_s2, stop, g.n_s);
 }
 
 void row_launch(const LatentGeom& g, int nrhs, const double* x, double* t, const double* stop, hipStream_t s) {
-    NNGP_LATENT_KP(nrhs, row_launch_kp<KP>(g, nrhs, x, t, stop, s));
+    if (g.s != nullptr)
+        NNGP_LATENT_KP(nrhs, row_launch_kp<KP, true>(g, nrhs, x, t, stop, s));
+    else
+        NNGP_LATENT_KP(nrhs, row_launch_kp<KP, false>(g, nrhs, x, t, stop, s));
 }
 
-template <bool SQRT>
+// the vectors' row count: the nodes the column phase and the CG's vector kernels run over
+int64_t vec_rows(const LatentGeom& g) { return g.s != nullptr ? g.n_s : g.n; }
+
+template <int MODE>
 void col_launch(const LatentGeom& g, int nrhs, const double* t, const double* x, double* out, double* rec,
                 const double* stop, hipStream_t s) {
-    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_kernel<SQRT, KP>), dim3(tile_blocks(g.n, kColRows)),
-                                            dim3(kBlock), 0, s, g.off, g.rev_j, g.prep.Brev, t, g.d, x, out, g.n,
-                                            nrhs, rec, stop));
+    if (g.s != nullptr)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_kernel<MODE, KP, true>),
+                                                dim3(tile_blocks(g.n_s, kColRows)), dim3(kBlock), 0, s, g.off,
+                                                g.rev_j, g.prep.Brev, t, g.d, x, out, g.n_s, nrhs, rec, stop, g.n));
+    else
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_col_kernel<MODE, KP, false>),
+                                                dim3(tile_blocks(g.n, kColRows)), dim3(kBlock), 0, s, g.off, g.rev_j,
+                                                g.prep.Brev, t, g.d, x, out, g.n, nrhs, rec, stop, g.n));
+}
+
+// reference-set systems: s for (theta, d), and diag(A_S) from it by the column phase
+void ref_s_launch(const LatentGeom& g, double* sv, hipStream_t s) {
+    hipLaunchKernelGGL(latent_ref_s_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, g.d, sv, g.n,
+                       g.n_s, 1.0 / g.sigma2);
+}
+
+void ref_diag_launch(const LatentGeom& g, double* out, hipStream_t s) {
+    hipLaunchKernelGGL((latent_col_kernel<kColDiag, 1, true>), dim3(tile_blocks(g.n_s, kColRows)), dim3(kBlock), 0,
+                       s, g.off, g.rev_j, g.prep.Brev, g.s, g.d, (const double*)nullptr, out, g.n_s, 1,
+                       (double*)nullptr, (const double*)nullptr, g.n);
 }
 
 // the CG workspace: six (n, nrhs) slots (M^-1, shared by the columns, uses n doubles of its own), kMaxRhs rows
 // of records, kMaxRhs state blocks and the block of the two "all finished" words
 struct CgLayout {
     double *t, *r, *z, *p, *q, *Minv, *rec, *pq_rec, *st;
+    double *s, *diag;  // reference-set systems only
 };
 
 constexpr size_t kCgStateWords = (size_t)(kMaxRhs + 1) * kStateWords;
+const size_t kCgTailBytes = align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8) +
+                            align256((size_t)kMaxRhs * kMaxTileBlocks * 8) + align256(kCgStateWords * 8);
+
+void cg_layout_tail(CgLayout* L, char* w) {
+    L->rec = (double*)w;
+    w += align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8);
+    L->pq_rec = (double*)w;
+    w += align256((size_t)kMaxRhs * kMaxTileBlocks * 8);
+    L->st = (double*)w;
+}
 
 CgLayout cg_layout(void* workspace, int64_t n, int nrhs) {
     char* w = (char*)workspace;
@@ -550,69 +704,57 @@ CgLayout cg_layout(void* workspace, int64_t n, int nrhs) {
     L.p = (double*)(w + 3 * v);
     L.q = (double*)(w + 4 * v);
     L.Minv = (double*)(w + 5 * v);
-    w += 6 * v;
-    L.rec = (double*)w;
-    w += align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8);
-    L.pq_rec = (double*)w;
-    w += align256((size_t)kMaxRhs * kMaxTileBlocks * 8);
-    L.st = (double*)w;
+    L.s = L.diag = nullptr;
+    cg_layout_tail(&L, w + 6 * v);
     return L;
 }
 
-}  // namespace
-
-size_t latent_apply_workspace_bytes(int64_t n, int nrhs) { return align256((size_t)(n > 0 ? n : 1) * nrhs * 8); }
-
-size_t latent_cg_workspace_bytes(int64_t n, int nrhs) {
-    return 6 * align256((size_t)n * nrhs * 8) + align256((size_t)kMaxRhs * 3 * kMaxVecBlocks * 8) +
-           align256((size_t)kMaxRhs * kMaxTileBlocks * 8) + align256(kCgStateWords * 8);
+// a reference-set system's: t (n, nrhs); r, z, p, q (n_s, nrhs); M^-1 and diag(A_S) (n_s,); s (n,); the tail
+size_t ref_cg_head_bytes(int64_t n, int64_t n_s, int nrhs) {
+    return align256((size_t)n * nrhs * 8) + 4 * align256((size_t)n_s * nrhs * 8) + 2 * align256((size_t)n_s * 8) +
+           align256((size_t)n * 8);
 }
 
-hipError_t latent_apply_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
-                               hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* t = (double*)workspace;
-    row_launch(g, nrhs, x, t, nullptr, s);
-    col_launch<false>(g, nrhs, t, x, out, nullptr, nullptr, s);
-    return hipGetLastError();
+CgLayout ref_cg_layout(void* workspace, int64_t n, int64_t n_s, int nrhs) {
+    char* w = (char*)workspace;
+    const size_t vt = align256((size_t)n * nrhs * 8), v = align256((size_t)n_s * nrhs * 8),
+                 v1 = align256((size_t)n_s * 8);
+    CgLayout L;
+    L.t = (double*)w;
+    w += vt;
+    L.r = (double*)w;
+    L.z = (double*)(w + v);
+    L.p = (double*)(w + 2 * v);
+    L.q = (double*)(w + 3 * v);
+    w += 4 * v;
+    L.Minv = (double*)w;
+    L.diag = (double*)(w + v1);
+    w += 2 * v1;
+    L.s = (double*)w;
+    w += align256((size_t)n * 8);
+    cg_layout_tail(&L, w);
+    return L;
 }
 
-hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2, double* out,
-                                      void* workspace, hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* u = (double*)workspace;
-    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n, nrhs,
-                       1.0 / g.sigma2);
-    col_launch<true>(g, nrhs, u, z2, out, nullptr, nullptr, s);
-    return hipGetLastError();
-}
-
-hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
-                              hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(latent_diag_kernel, dim3(vec_blocks(n)), dim3(kBlock), 0, s, n, d, prep.invF, prep.P,
-                       1.0 / sigma2, out);
-    return hipGetLastError();
-}
-
-hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s) {
-    for (int c = 0; c < nrhs; ++c) {
-        info_host[4 * c + 0] = 0.0;
-        info_host[4 * c + 1] = 1.0;
-        info_host[4 * c + 2] = info_host[4 * c + 3] = 0.0;
-    }
-    if (g.n == 0) return hipSuccess;
-    const CgLayout L = cg_layout(workspace, g.n, nrhs);
-    const int nv = vec_blocks(g.n), nt = tile_blocks(g.n, kColRows);
+// the recurrences on a geometry whose workspace is laid out (and, for a reference-set system, whose s and
+// diag(A_S) are in place); vectors have vec_rows(g) rows
+hipError_t cg_iterate(const LatentGeom& g, const CgLayout& L, int nrhs, const double* b, double* x, double rtol,
+                      int64_t max_iter, int check_every, double* info_host, hipStream_t s) {
+    const int64_t nr = vec_rows(g);
+    const int nv = vec_blocks(nr), nt = tile_blocks(nr, kColRows);
     const double inv_s2 = 1.0 / g.sigma2;
     hipError_t e;
     // r = b - A x0, z = M^-1 r, p = z, per column
     row_launch(g, nrhs, x, L.t, nullptr, s);
-    col_launch<false>(g, nrhs, L.t, x, L.q, nullptr, nullptr, s);
-    NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_init_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n, nrhs, b,
-                                            (const double*)L.q, g.d, g.prep.invF, g.prep.P, inv_s2, L.r, L.z, L.p,
-                                            L.Minv, L.rec));
+    col_launch<kColApply>(g, nrhs, L.t, x, L.q, nullptr, nullptr, s);
+    if (g.s != nullptr)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_cg_init_kernel<KP, true>), dim3(nv), dim3(kBlock), 0, s, nr,
+                                                nrhs, b, (const double*)L.q, g.d, g.prep.invF,
+                                                (const double*)L.diag, inv_s2, L.r, L.z, L.p, L.Minv, L.rec));
+    else
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_cg_init_kernel<KP, false>), dim3(nv), dim3(kBlock), 0, s, nr,
+                                                nrhs, b, (const double*)L.q, g.d, g.prep.invF, g.prep.P, inv_s2, L.r,
+                                                L.z, L.p, L.Minv, L.rec));
     hipLaunchKernelGGL(latent_cg_start_kernel, dim3(1), dim3(kBlock), 0, s, (const double*)L.rec, nv, nrhs, rtol,
                        L.st);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -623,13 +765,13 @@ hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double*
         for (int c = 0; c < check_every && k < max_iter; ++c, ++k) {
             const double* stop = L.st + kAll0 + (k & 1);
             row_launch(g, nrhs, L.p, L.t, stop, s);
-            col_launch<false>(g, nrhs, L.t, L.p, L.q, L.pq_rec, stop, s);
-            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_update_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, g.n,
+            col_launch<kColApply>(g, nrhs, L.t, L.p, L.q, L.pq_rec, stop, s);
+            NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_update_kernel<KP>, dim3(nv), dim3(kBlock), 0, s, nr,
                                                     nrhs, k, (const double*)L.pq_rec, nt, (const double*)L.p,
                                                     (const double*)L.q, (const double*)L.Minv, x, L.r, L.z, L.rec,
                                                     L.st));
             NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_direction_kernel<KP>, dim3(nv), dim3(kBlock), 0, s,
-                                                    g.n, nrhs, k, (const double*)L.rec, nv, (const double*)L.z, L.p,
+                                                    nr, nrhs, k, (const double*)L.rec, nv, (const double*)L.z, L.p,
                                                     L.st));
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -645,6 +787,153 @@ hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double*
         info_host[4 * c + 3] = sc[kBb];
     }
     return hipSuccess;
+}
+
+void cg_info_clear(int nrhs, double* info_host) {
+    for (int c = 0; c < nrhs; ++c) {
+        info_host[4 * c + 0] = 0.0;
+        info_host[4 * c + 1] = 1.0;
+        info_host[4 * c + 2] = info_host[4 * c + 3] = 0.0;
+    }
+}
+
+size_t max_size(size_t a, size_t b) { return a > b ? a : b; }
+
+}  // namespace
+
+size_t latent_apply_workspace_bytes(int64_t n, int nrhs) { return align256((size_t)(n > 0 ? n : 1) * nrhs * 8); }
+
+size_t latent_cg_workspace_bytes(int64_t n, int nrhs) {
+    return 6 * align256((size_t)n * nrhs * 8) + kCgTailBytes;
+}
+
+hipError_t latent_apply_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
+                               hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* t = (double*)workspace;
+    row_launch(g, nrhs, x, t, nullptr, s);
+    col_launch<kColApply>(g, nrhs, t, x, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s) {
+    if (g.n == 0) return hipSuccess;
+    double* u = (double*)workspace;
+    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n, nrhs,
+                       1.0 / g.sigma2);
+    col_launch<kColSqrt>(g, nrhs, u, z2, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
+                              hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(latent_diag_kernel, dim3(vec_blocks(n)), dim3(kBlock), 0, s, n, d, prep.invF, prep.P,
+                       1.0 / sigma2, out);
+    return hipGetLastError();
+}
+
+hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s) {
+    cg_info_clear(nrhs, info_host);
+    if (g.n == 0) return hipSuccess;
+    return cg_iterate(g, cg_layout(workspace, g.n, nrhs), nrhs, b, x, rtol, max_iter, check_every, info_host, s);
+}
+
+// ---------------------------------------------------------------- reference-set systems
+// g.n_s == g.n: there is no leaf and the S = T launches serve the call, so the bits are theirs.  Otherwise the
+// workspace starts with t (n, nrhs) and s (n,) (the CG's: ref_cg_layout).
+size_t latent_ref_apply_workspace_bytes(int64_t n, int64_t n_s, int nrhs) {
+    const size_t w = align256((size_t)(n > 0 ? n : 1) * nrhs * 8) + align256((size_t)(n > 0 ? n : 1) * 8);
+    return n_s == n ? max_size(w, latent_apply_workspace_bytes(n, nrhs)) : w;
+}
+
+size_t latent_ref_cg_workspace_bytes(int64_t n, int64_t n_s, int nrhs) {
+    const size_t w = ref_cg_head_bytes(n, n_s, nrhs) + kCgTailBytes;
+    return n_s == n ? max_size(w, latent_cg_workspace_bytes(n, nrhs)) : w;
+}
+
+namespace {
+// t and s of an operator workspace; s is computed and g made a reference-set geometry
+double* ref_begin(LatentGeom* g, int nrhs, void* workspace, hipStream_t s) {
+    char* w = (char*)workspace;
+    double* sv = (double*)(w + align256((size_t)g->n * nrhs * 8));
+    ref_s_launch(*g, sv, s);
+    g->s = sv;
+    return (double*)w;
+}
+}  // namespace
+
+hipError_t latent_ref_apply_launch(LatentGeom g, int nrhs, const double* x, double* out, void* workspace,
+                                   hipStream_t s) {
+    if (g.n_s == g.n) return latent_apply_launch(g, nrhs, x, out, workspace, s);
+    if (g.n_s == 0) return hipSuccess;
+    double* t = ref_begin(&g, nrhs, workspace, s);
+    row_launch(g, nrhs, x, t, nullptr, s);
+    col_launch<kColApply>(g, nrhs, t, x, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_ref_sqrt_t_apply_launch(LatentGeom g, int nrhs, const double* z1, const double* z2, double* out,
+                                          void* workspace, hipStream_t s) {
+    if (g.n_s == g.n) return latent_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, s);
+    if (g.n_s == 0) return hipSuccess;
+    double* u = ref_begin(&g, nrhs, workspace, s);
+    hipLaunchKernelGGL(latent_ref_scale_kernel<false>, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.s, z1, u, g.n,
+                       g.n_s, nrhs);
+    col_launch<kColSqrt>(g, nrhs, u, z2, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_ref_fold_launch(LatentGeom g, int nrhs, const double* v, double* out, void* workspace,
+                                  hipStream_t s) {
+    if (g.n_s == 0) return hipSuccess;
+    double* u = ref_begin(&g, nrhs, workspace, s);
+    hipLaunchKernelGGL(latent_ref_scale_kernel<true>, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.s, v, u, g.n,
+                       g.n_s, nrhs);
+    col_launch<kColApply>(g, nrhs, u, v, out, nullptr, nullptr, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_ref_diag_launch(LatentGeom g, double* out, void* workspace, hipStream_t s) {
+    if (g.n_s == g.n) return latent_diag_launch(g.prep, g.n, g.sigma2, g.d, out, s);
+    if (g.n_s == 0) return hipSuccess;
+    ref_begin(&g, 1, workspace, s);
+    ref_diag_launch(g, out, s);
+    return hipGetLastError();
+}
+
+hipError_t latent_ref_cg_run(LatentGeom g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                             int check_every, double* info_host, void* workspace, hipStream_t s) {
+    if (g.n_s == g.n) return latent_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace, s);
+    cg_info_clear(nrhs, info_host);
+    if (g.n_s == 0) return hipSuccess;
+    const CgLayout L = ref_cg_layout(workspace, g.n, g.n_s, nrhs);
+    ref_s_launch(g, L.s, s);
+    g.s = L.s;
+    ref_diag_launch(g, L.diag, s);
+    return cg_iterate(g, L, nrhs, b, x, rtol, max_iter, check_every, info_host, s);
+}
+
+hipError_t latent_ref_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,
+                                    double* out, hipStream_t s) {
+    const int64_t n_l = g.n - g.n_s;
+    if (n_l == 0) return hipSuccess;
+    const double inv_s2 = 1.0 / g.sigma2;
+    if (g.m <= 4)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_leaf_kernel<4, KP>), dim3(tile_blocks(n_l, kBlock / 4)),
+                                                dim3(kBlock), 0, s, g.nbr, g.B, g.prep.invF, g.d, x, v, z, out, g.n,
+                                                g.n_s, g.m, nrhs, inv_s2));
+    else if (g.m <= 8)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_leaf_kernel<8, KP>), dim3(tile_blocks(n_l, kBlock / 8)),
+                                                dim3(kBlock), 0, s, g.nbr, g.B, g.prep.invF, g.d, x, v, z, out, g.n,
+                                                g.n_s, g.m, nrhs, inv_s2));
+    else
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_leaf_kernel<16, KP>), dim3(tile_blocks(n_l, kBlock / 16)),
+                                                dim3(kBlock), 0, s, g.nbr, g.B, g.prep.invF, g.d, x, v, z, out, g.n,
+                                                g.n_s, g.m, nrhs, inv_s2));
+    return hipGetLastError();
 }
 
 }  // namespace nngp

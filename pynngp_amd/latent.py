@@ -13,8 +13,19 @@ the mean is a Jacobi-preconditioned conjugate-gradient solve (``nngp_latent_cg``
 applications instead of thousands of Gibbs sweeps), and exact draws come from the same solver by perturbation:
 w = A^-1 (b + eta), eta = (I - B)^T (sigma2 F)^-1/2 z1 + (h / tau2)^1/2 z2 has covariance A.
 
-The latent mean at new locations is kriging of w_hat without a nugget:
-``NNGP.predict(values=w_hat, cov=cov.replace(tau2=0), query=...)``.
+A reference set (``ref=``; the reference's refType ('subset', nRef) / ('random', nRef, bounds)): the field
+lives on the n_S points of S, and a data location outside S is a leaf whose parents are its m nearest points of S
+(``SeqNNGP``'s node DAG).  A leaf is conditionally independent of everything else given w_S, so it is integrated
+out in closed form instead of being carried through the solver: with f = 1 / (sigma2 F), d = h / tau2, v the
+centred response and g_j = f_j d_j / (f_j + d_j) per leaf,
+
+    A_S = (I - B_S)^T f_S (I - B_S) + d_S + B_L^T g B_L,   b_S = d_S v_S + B_L^T (g v_L)
+    w_S | y ~ N(A_S^-1 b_S, A_S^-1),   w_j | w_S, y ~ N((f_j B_j w_S + d_j v_j) / (f_j + d_j), 1 / (f_j + d_j))
+
+Every CG vector has n_S entries however many data locations hang off S (``nngp_precision_ref_*``,
+``nngp_latent_ref_cg_batch``, ``nngp_latent_ref_leaves_batch``).  A prediction point is an unobserved leaf of the
+same kind: :meth:`LatentPosterior.predict` gives the latent mean, its variance and draws at new locations for
+both S = T and S != T.
 """
 from __future__ import annotations
 
@@ -67,9 +78,21 @@ class LatentPosterior:
     buffer once.  Internally every per-location array is kept in Z-order storage (as ``SeqNNGP``), so that the
     operator's gathers stay in cache; vectors go in and come out in the order of ``coords``.  Methods take and
     return numpy arrays, or device tensors when given device tensors.
+
+    ``ref`` (n_S, d): the reference set S the field lives on (default None: S = T, the data locations).  The nodes
+    are ``SeqNNGP``'s: the points of ``ref``, then the data locations outside it as leaves linked to their m
+    nearest points of S (-1 padded when n_S < m); a data location that coincides with a reference point carries
+    its observation on that node (``node_of_t`` maps data rows to nodes).  Storage holds the reference nodes in
+    Z-order, then the leaves in Z-order.  The leaves are integrated out (module docstring): the vectors of
+    :meth:`matvec` / :meth:`solve` / :meth:`solve_many` have n_S entries in the order of ``ref``, and field-valued
+    results take ``where="data"`` (one value per row of ``coords``, the default) or ``where="ref"``.  ``X_ref``
+    (n_S, p): covariates at S, accepted as ``SeqNNGP`` does; a node without an observation has no weight in any
+    estimate here, so they change nothing.  ``nbr`` is for S = T only.
     """
 
-    def __init__(self, coords, y, cov, m: int = 15, X=None, eps=None, device=None, nbr=None):
+    _ref = False  # S = T unless __init__ builds a reference set
+
+    def __init__(self, coords, y, cov, m: int = 15, X=None, eps=None, device=None, nbr=None, ref=None, X_ref=None):
         cov = _check_cov(cov)
         self.m = int(m)
         if not 1 <= self.m <= _lib.MAX_M:
@@ -111,9 +134,35 @@ class LatentPosterior:
                                 or tuple(nbr.shape) != (n, self.m)):
             raise ValueError(f"nbr must be an int32 ({n}, {self.m}) device tensor")
 
+        s_host = None
+        if ref is not None:
+            if nbr is not None:
+                raise ValueError("nbr (prior neighbour sets of the data locations) is for S = T; with ref the "
+                                 "neighbour sets are built on the reference set")
+            s_host = np.ascontiguousarray(ref.detach().cpu().numpy() if isinstance(ref, torch.Tensor) else ref,
+                                          dtype=np.float64)
+            if s_host.ndim == 1:
+                s_host = s_host[:, None]
+            if s_host.ndim != 2 or s_host.shape[0] < 1 or not np.all(np.isfinite(s_host)):
+                raise ValueError(f"ref must be finite (n_S >= 1, d), got {s_host.shape}")
+            if s_host.shape[1] != c_host.shape[1]:
+                raise ValueError(f"reference set has dimension {s_host.shape[1]}, locations {c_host.shape[1]}")
+            if X_ref is not None:
+                xr = np.asarray(X_ref, dtype=np.float64)
+                xr = xr[:, None] if xr.ndim == 1 else xr
+                if xr.shape != (s_host.shape[0], X_host.shape[1]) or not np.all(np.isfinite(xr)):
+                    raise ValueError(f"X_ref must be finite ({s_host.shape[0]}, {X_host.shape[1]}), got {xr.shape}")
+        elif X_ref is not None:
+            raise ValueError("X_ref needs ref")
+
         self.device = dev = _default_device(device)
         self.n, self.p = n, X_host.shape[1]
         to = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731
+        if s_host is not None:
+            self._init_ref(to, c_host, s_host, y_host, observed, h_host, X_host)
+            self.update(cov)
+            return
+        self.n_nodes = self.n_s = n
         coords0 = to(c_host)
         nbr0 = _lib.knn_prior(coords0, self.m) if nbr is None else nbr.to(dev)
         # Z-order storage: slot s holds location perm[s]; neighbour sets relabelled into storage labels
@@ -133,6 +182,67 @@ class LatentPosterior:
         self._ws_batch = None  # the operator's and solver's workspace, made on first use for the widest chunk so far
         self.update(cov)
 
+    def _init_ref(self, to, c_host, s_host, y_host, observed, h_host, X_host):
+        """The node DAG of a reference set, as ``SeqNNGP`` builds it (gibbs.py), in the storage order [S in
+        Z-order; leaves in Z-order]."""
+        dev, n_t, n_s = self.device, c_host.shape[0], s_host.shape[0]
+        t_dev, s_dev = to(c_host), to(s_host)
+        nbr_s = _lib.knn_prior(s_dev, self.m)
+        if n_s > 1:  # a repeated reference point makes C_N singular
+            j1 = nbr_s[1:, 0].long()
+            dup = torch.nonzero((s_dev[1:] == s_dev[j1]).all(dim=1)).flatten()
+            if dup.numel() > 0:
+                k = int(dup[0]) + 1
+                raise ValueError(f"reference set point {k} repeats point {int(j1[k - 1])} (C_N would be singular; "
+                                 "e.g. ('subset', nRef) draws with replacement)")
+        # data locations that coincide with a reference point carry their data on that node
+        j0 = _lib.knn_query(s_dev, t_dev, 1)[:, 0].long()
+        hit = (t_dev == s_dev[j0]).all(dim=1).cpu().numpy()
+        j0h = j0.cpu().numpy()
+        if np.unique(j0h[hit]).size != int(hit.sum()):
+            raise ValueError("two data locations coincide with the same reference point")
+        out_idx = np.nonzero(~hit)[0]
+        node_of_t = np.where(hit, j0h, 0)
+        node_of_t[out_idx] = n_s + np.arange(out_idx.size)
+        k = min(self.m, n_s)
+        t_out = t_dev[torch.from_numpy(out_idx).to(dev)]
+        nbr_t = (_lib.knn_query(s_dev, t_out, k) if out_idx.size
+                 else torch.empty((0, k), dtype=torch.int32, device=dev))
+        if k < self.m:
+            nbr_t = torch.cat([nbr_t, torch.full((nbr_t.shape[0], self.m - k), -1, dtype=torch.int32, device=dev)],
+                              dim=1)
+        nbr0 = torch.cat([nbr_s, nbr_t]).contiguous()
+        coords0 = torch.cat([s_dev, t_out]).contiguous()
+        n = coords0.shape[0]
+        self._ref = True
+        self.n_nodes, self.n_s = n, n_s
+        self.node_of_t = node_of_t.astype(np.int64)  # model node (reference points, then leaves) of each data row
+        h_n, y_n, X_n = np.zeros(n), np.zeros(n), np.zeros((n, self.p))
+        h_n[node_of_t[observed]] = h_host[observed]
+        y_n[node_of_t[observed]] = y_host[observed]
+        X_n[node_of_t] = X_host
+        # storage: slot s holds model node perm[s]; reference nodes keep the first n_s slots
+        parts = [_lib.row_order(s_dev)[0].long()]
+        if n > n_s:
+            parts.append(_lib.row_order(t_out)[0].long() + n_s)
+        self.perm = torch.cat(parts)
+        self.pos = torch.empty_like(self.perm)
+        self.pos[self.perm] = torch.arange(n, device=dev)
+        self.perm_s = self.perm[:n_s].contiguous()  # reference point held by storage slot s < n_s
+        self.slot_of_ref = self.pos[:n_s].contiguous()
+        self.slot_of_t = self.pos[torch.from_numpy(self.node_of_t).to(dev)]
+        self.coords = coords0[self.perm].contiguous()
+        nb = nbr0[self.perm].long()
+        self.nbr = torch.where(nb >= 0, self.pos[nb.clamp(min=0)], -1).to(torch.int32).contiguous()
+        self.off, self.rev_j, self.rev_k = _lib.reverse_neighbors(self.nbr)
+        self.h = to(h_n)[self.perm].contiguous()
+        self.y = to(y_n)[self.perm].contiguous()
+        self.X = to(X_n)[self.perm].contiguous()
+        self.B = torch.empty((n, self.m), dtype=torch.float64, device=dev)
+        self.F = torch.empty(n, dtype=torch.float64, device=dev)
+        self._prep = None
+        self._ws_batch = None
+
     # -- theta -----------------------------------------------------------------
     def update(self, cov) -> "LatentPosterior":
         """A new theta on the same neighbour sets: one B / F sweep and one ``prepare``."""
@@ -147,22 +257,73 @@ class LatentPosterior:
         return self
 
     # -- vectors in / out ------------------------------------------------------
+    # the solver's vectors: one entry per data location (S = T) or per reference point, in the caller's order
+    @property
+    def _vn(self):
+        return self.n_s if self._ref else self.n
+
+    @property
+    def _vperm(self):
+        return self.perm_s if self._ref else self.perm
+
+    @property
+    def _vpos(self):
+        return self.slot_of_ref if self._ref else self.pos
+
     def _in(self, v, what="vector"):
         t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
-        if t.dtype != torch.float64 or tuple(t.shape) != (self.n,):
-            raise ValueError(f"{what} must be float64 ({self.n},), got {t.dtype} {tuple(t.shape)}")
-        return t.to(self.device)[self.perm].contiguous()
+        if t.dtype != torch.float64 or tuple(t.shape) != (self._vn,):
+            raise ValueError(f"{what} must be float64 ({self._vn},), got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device)[self._vperm].contiguous()
 
     def _out(self, t, like):
-        o = t[self.pos]
+        o = t[self._vpos]
         return o if isinstance(like, torch.Tensor) else o.cpu().numpy()
 
     def _geom(self):
         return (self.nbr, self.B, self.off, self.rev_j, self.rev_k, self._prep, self.cov.sigma2)
 
+    def _rgeom(self):
+        return (self.nbr, self.B, self.off, self.rev_j, self.rev_k, self._prep, self.n_s, self.cov.sigma2)
+
+    @staticmethod
+    def _check_where(where):
+        if where not in ("data", "ref"):
+            raise ValueError(f"where must be 'data' or 'ref', got {where!r}")
+
+    def _rows_of(self, where):
+        """Storage slots of the rows a field-valued result reports."""
+        if not self._ref:
+            return self.pos  # S = T: the reference set is the data locations
+        return self.slot_of_t if where == "data" else self.slot_of_ref
+
+    def _apply_cols(self, X):
+        """A X (S = T) or A_S X for storage-order columns."""
+        if self._ref:
+            return _lib.precision_ref_apply_batch(*self._rgeom(), X, d=self.d, workspace=self._batch_ws(X.shape[1]))
+        return _lib.precision_apply_batch(*self._geom(), X, d=self.d, workspace=self._batch_ws(X.shape[1]))
+
+    def _leaf_cols(self, XS, V=None, Z=None):
+        """The leaves given the storage-order columns XS on S: conditional means (+ noise for normals Z)."""
+        return _lib.latent_ref_leaves_batch(*self._rgeom(), XS, v=V, z=Z, d=self.d)
+
+    def _node_cols(self, XS, V=None, Z=None):
+        """(n_nodes, k) columns over all storage slots from the columns on S."""
+        return torch.cat([XS, self._leaf_cols(XS, V, Z)]) if self._ref and self.n_nodes > self.n_s else XS
+
+    def _yres(self, beta):
+        return self.y if self.p == 0 else self.y - self.X @ torch.as_tensor(beta, dtype=torch.float64,
+                                                                           device=self.device)
+
+    def _leaf_v(self, beta, k):
+        """The centred response on the leaves as k equal columns (the leaves kernel's v)."""
+        return self._yres(beta)[self.n_s:, None].expand(-1, k).contiguous()
+
     # -- the operator and the solver -------------------------------------------
     def matvec(self, x):
-        """A x (two gathers, bit-reproducible)."""
+        """A x (two gathers, bit-reproducible); with a reference set A_S x, x in the order of ``ref``."""
+        if self._ref:
+            return self._out(self._apply_cols(self._in(x, "x")[:, None].contiguous())[:, 0], x)
         return self._out(_lib.precision_apply(*self._geom(), self._in(x, "x"), d=self.d, workspace=self._batch_ws(1)),
                          x)
 
@@ -171,10 +332,15 @@ class LatentPosterior:
         if not 0.0 < rtol < 1.0:
             raise ValueError(f"rtol must be in (0, 1), got {rtol}")
         if max_iter is None:
-            max_iter = min(max(2 * self.n, 1000), 20000)
-        x = torch.zeros_like(rhs) if x0 is None else x0.clone()
-        _, info = _lib.latent_cg(*self._geom(), rhs, x, d=self.d, rtol=rtol, max_iter=int(max_iter),
-                                 check_every=CHECK_EVERY, workspace=self._batch_ws(1))
+            max_iter = min(max(2 * self._vn, 1000), 20000)
+        if self._ref:
+            X, info = self._solve_cols(rhs[:, None].contiguous(), rtol, max_iter,
+                                       None if x0 is None else x0[:, None].contiguous())
+            x, info = X[:, 0].contiguous(), [float(v) for v in info[0]]
+        else:
+            x = torch.zeros_like(rhs) if x0 is None else x0.clone()
+            _, info = _lib.latent_cg(*self._geom(), rhs, x, d=self.d, rtol=rtol, max_iter=int(max_iter),
+                                     check_every=CHECK_EVERY, workspace=self._batch_ws(1))
         if info[1] < 0:
             raise NNGPNumericalError(f"CG breakdown after {int(info[0])} iterations: p.Ap is not positive and finite "
                                      "(NaN or inf in the factors or the right-hand side?)")
@@ -201,7 +367,10 @@ class LatentPosterior:
         return b
 
     def _batch_ws(self, nrhs):
-        need = _lib.load().nngp_latent_cg_batch_workspace_bytes(self.n, nrhs)
+        if self._ref:
+            need = _lib.load().nngp_latent_ref_cg_batch_workspace_bytes(self.n_nodes, self.n_s, nrhs)
+        else:
+            need = _lib.load().nngp_latent_cg_batch_workspace_bytes(self.n, nrhs)
         if self._ws_batch is None or self._ws_batch.numel() < need:
             self._ws_batch = _lib._workspace(need, self.device)
         return self._ws_batch
@@ -209,13 +378,16 @@ class LatentPosterior:
     def _in_rows(self, v, what="rhs"):
         """(K, N) rows in the order of ``coords`` -> (K, N) device rows in storage order."""
         t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
-        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != self.n:
-            raise ValueError(f"{what} must be float64 (K, {self.n}), got {t.dtype} {tuple(t.shape)}")
-        return t.to(self.device)[:, self.perm]
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != self._vn:
+            raise ValueError(f"{what} must be float64 (K, {self._vn}), got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device)[:, self._vperm]
 
     def _solve_cols(self, R, rtol, max_iter, X0=None):
         """One batched solve of the storage-order columns R (n, k <= LATENT_MAX_RHS): (X, info (k, 4))."""
         X = torch.zeros_like(R) if X0 is None else X0.clone()
+        if self._ref:
+            return _lib.latent_ref_cg_batch(*self._rgeom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
+                                            check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
         return _lib.latent_cg_batch(*self._geom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
                                     check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
 
@@ -240,9 +412,9 @@ class LatentPosterior:
         if not 0.0 < rtol < 1.0:
             raise ValueError(f"rtol must be in (0, 1), got {rtol}")
         if max_iter is None:
-            max_iter = min(max(2 * self.n, 1000), 20000)
+            max_iter = min(max(2 * self._vn, 1000), 20000)
         K = rows.shape[0]
-        out = torch.empty((K, self.n), dtype=torch.float64, device=self.device)
+        out = torch.empty((K, self._vn), dtype=torch.float64, device=self.device)
         info = np.zeros((K, 4))
         for k0 in range(0, K, batch):
             k1 = min(K, k0 + batch)
@@ -264,40 +436,62 @@ class LatentPosterior:
             raise ValueError(f"x0 must have the shape of rhs {tuple(rows.shape)}, got {tuple(starts.shape)}")
         x, info = self._solve_rows(rows, rtol, max_iter, batch, starts)
         infos = self._report(info, rtol)
-        x = x[:, self.pos]
+        x = x[:, self._vpos]
         return (x if isinstance(rhs, torch.Tensor) else x.cpu().numpy()), infos
 
     # -- posterior mean --------------------------------------------------------
     def _rhs(self, beta):
         yres = self.y if self.p == 0 else self.y - self.X @ torch.as_tensor(beta, dtype=torch.float64,
                                                                            device=self.device)
+        if self._ref:  # b_S = d_S v_S + B_L^T (g v_L)
+            return self._fold_cols(yres[:, None].contiguous())[:, 0].contiguous()
         return (self.d * yres).contiguous()
+
+    def _fold_cols(self, V):
+        return _lib.precision_ref_fold_batch(*self._rgeom(), V, d=self.d, workspace=self._batch_ws(V.shape[1]))
 
     def gls_beta(self, rtol: float = 1e-8, max_iter: Optional[int] = None, batch=None) -> np.ndarray:
         """GLS beta under V = C~ + tau2 H^-1 (C~ the NNGP covariance): V^-1 v = H v / tau2 - H A^-1 H v / tau4,
         one solve per column of X, ``batch`` columns per batched solve; rows with h = 0 drop out."""
         if self.p == 0:
             return np.zeros(0)
-        rows = (self.d[:, None] * self.X).t()
-        S, info = self._solve_rows(rows, rtol, max_iter, self._batch(batch))
-        self._report(info, rtol)
-        S = S.t().contiguous()
+        if self._ref:
+            # A_aug^-1 (D v) = [x_S; leaf mean(x_S, v)] with x_S = A_S^-1 fold(v), per column v of X
+            batch = self._batch(batch)
+            if not 0.0 < rtol < 1.0:
+                raise ValueError(f"rtol must be in (0, 1), got {rtol}")
+            mi = min(max(2 * self.n_s, 1000), 20000) if max_iter is None else max_iter
+            S = torch.empty_like(self.X)
+            for k0 in range(0, self.p, batch):
+                V = self.X[:, k0:k0 + batch].contiguous()
+                XS, info = self._solve_cols(self._fold_cols(V), rtol, mi)
+                self._report(info, rtol, first=k0)
+                S[:, k0:k0 + batch] = self._node_cols(XS, V[self.n_s:].contiguous())
+        else:
+            rows = (self.d[:, None] * self.X).t()
+            S, info = self._solve_rows(rows, rtol, max_iter, self._batch(batch))
+            self._report(info, rtol)
+            S = S.t().contiguous()
         W = self.d[:, None] * (self.X - S)  # V^-1 X
         G = (self.X.t() @ W).cpu().numpy()
         g = (W.t() @ self.y).cpu().numpy()
         return np.linalg.solve(0.5 * (G + G.T), g)
 
-    def mean(self, beta=None, rtol: float = 1e-8, max_iter: Optional[int] = None):
+    def mean(self, beta=None, rtol: float = 1e-8, max_iter: Optional[int] = None, where: str = "data"):
         """Posterior mean ``(w_hat, beta_hat)``: w_hat = A^-1 h (y - X beta) / tau2 as a numpy array.  With ``X``
         and no ``beta``, beta_hat is the GLS estimate (:meth:`gls_beta`; p + 1 solves in all); without ``X`` it
-        is empty.  The latent mean at new locations: ``NNGP.predict(values=w_hat, cov=cov.replace(tau2=0))``."""
+        is empty.  With a reference set, ``where="data"`` gives the mean at every row of ``coords`` (a leaf's is its
+        conditional mean given w_hat on S) and ``where="ref"`` the mean on S.  At new locations: :meth:`predict`."""
+        self._check_where(where)
         if beta is None:
             beta = self._beta_hat = self.gls_beta(rtol, max_iter)
         beta = np.asarray(beta, dtype=np.float64).reshape(-1)
         if beta.shape != (self.p,):
             raise ValueError(f"beta must hold {self.p} coefficients")
         w, _ = self._solve(self._rhs(beta), rtol, max_iter)
-        return w[self.pos].cpu().numpy(), beta
+        if self._ref:
+            w = self._node_cols(w[:, None].contiguous(), self._leaf_v(beta, 1))[:, 0]
+        return w[self._rows_of(where)].cpu().numpy(), beta
 
     # -- exact draws -----------------------------------------------------------
     def _beta_for_draws(self, beta, rtol, max_iter):
@@ -309,8 +503,11 @@ class LatentPosterior:
     def _draw_chunks(self, n_draws, seed, z, b, rtol, max_iter, batch):
         """Yields ``(k0, W)``: the draws k0 .. k0 + W.shape[1] - 1 as storage-order columns (n, k <= batch) on the
         device.  Draw k takes the Philox streams of sweep indices 2k and 2k + 1, whatever the chunking."""
+        if self._ref:
+            yield from self._draw_chunks_ref(n_draws, seed, z, b, rtol, max_iter, batch)
+            return
         if z is not None:
-            z1, z2 = (np.asarray(a, dtype=np.float64).reshape(n_draws, self.n) for a in z)
+            z1, z2 = (np.asarray(a, dtype=np.float64).reshape(n_draws, self.n) for a in z[:2])
         zz = torch.empty(self.n, dtype=torch.float64, device=self.device)
         for k0 in range(0, n_draws, batch):
             kc = min(batch, n_draws - k0)
@@ -327,26 +524,84 @@ class LatentPosterior:
             self._report(info, rtol, first=k0)
             yield k0, W.t().contiguous()
 
+    LEAF_STREAM = 1 << 40   # sweep index of draw k's third Philox stream (the leaves' conditional noise)
+    QUERY_STREAM = 1 << 41  # ... of predict's conditional noise
+    RESPONSE_STREAM = 3 << 40  # ... of predict's response noise (every stream is keyed by the draw's k alone)
+
+    def _nodes_in(self, a, n_draws, part):
+        """Given test normals (n_draws, len) in model order -> storage-order device rows; part: "n" all nodes
+        (reference points, then the data locations outside S in their order), "s" S, "l" the leaves."""
+        size = {"n": self.n_nodes, "s": self.n_s, "l": self.n_nodes - self.n_s}[part]
+        t = torch.from_numpy(np.asarray(a, dtype=np.float64).reshape(n_draws, size)).to(self.device)
+        idx = {"n": self.perm, "s": self.perm_s, "l": self.perm[self.n_s:] - self.n_s}[part]
+        return t[:, idx]
+
+    def _draw_chunks_ref(self, n_draws, seed, z, b, rtol, max_iter, batch):
+        """:meth:`_draw_chunks` on a reference set: W holds draws of w_S, storage-order columns (n_s, k).  z1 has
+        one normal per node, z2 one per reference point."""
+        n, n_s = self.n_nodes, self.n_s
+        if z is not None:
+            z1, z2 = self._nodes_in(z[0], n_draws, "n"), self._nodes_in(z[1], n_draws, "s")
+        zz1 = torch.empty(n, dtype=torch.float64, device=self.device)
+        zz2 = torch.empty(n_s, dtype=torch.float64, device=self.device)
+        for k0 in range(0, n_draws, batch):
+            kc = min(batch, n_draws - k0)
+            Z1 = torch.empty((n, kc), dtype=torch.float64, device=self.device)
+            Z2 = torch.empty((n_s, kc), dtype=torch.float64, device=self.device)
+            for c in range(kc):
+                if z is None:
+                    Z1[:, c] = _lib.gibbs_normals(zz1, seed, 2 * (k0 + c))
+                    Z2[:, c] = _lib.gibbs_normals(zz2, seed, 2 * (k0 + c) + 1)
+                else:
+                    Z1[:, c], Z2[:, c] = z1[k0 + c], z2[k0 + c]
+            eta = _lib.precision_ref_sqrt_t_apply_batch(*self._rgeom(), Z1, Z2, d=self.d,
+                                                        workspace=self._batch_ws(kc))
+            W, info = self._solve_rows((b[:, None] + eta).t(), rtol, max_iter, kc)
+            self._report(info, rtol, first=k0)
+            yield k0, W.t().contiguous()
+
+    def _leaf_normals(self, k0, kc, n_draws, seed, z3, stream, size=None):
+        """(size, kc) standard normals of draws k0 .. k0 + kc - 1: given rows, or Philox stream ``stream + k``."""
+        size = self.n_nodes - self.n_s if size is None else size
+        Z = torch.empty((size, kc), dtype=torch.float64, device=self.device)
+        zz = torch.empty(size, dtype=torch.float64, device=self.device)
+        for c in range(kc):
+            Z[:, c] = z3[k0 + c] if z3 is not None else _lib.gibbs_normals(zz, seed, stream + k0 + c)
+        return Z
+
     def sample(self, n_draws: int, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,
-               max_iter: Optional[int] = None, batch=None) -> np.ndarray:
+               max_iter: Optional[int] = None, batch=None, where: str = "data") -> np.ndarray:
         """``(n_draws, N)`` exact posterior draws w = A^-1 (b + eta), eta = (I - B)^T (sigma2 F)^-1/2 z1 +
         (h / tau2)^1/2 z2, ``batch`` draws per batched square-root application and solve (default
         ``LATENT_MAX_RHS``; the draws do not depend on it).  The normals are Philox streams keyed by ``seed``
         (``nngp_gibbs_normals``; one seed repeats bit for bit), or ``z = (z1, z2)``, each (n_draws, N), for
-        testing.  ``beta``: as :meth:`mean`."""
+        testing.  ``beta``: as :meth:`mean`.
+
+        With a reference set the draws are of w_S (eta = (I - B_S)^T f_S^1/2 z1_S + B_L^T g^1/2 z1_L + d_S^1/2 z2),
+        and every leaf adds its conditional noise from a third Philox stream per draw (streams 2k and 2k + 1 are
+        those of S = T); ``where`` as :meth:`mean`; ``z = (z1 (n_draws, n_nodes), z2 (n_draws, n_S), z3 (n_draws,
+        n_nodes - n_S))`` in node order (the points of ``ref``, then the data locations outside it)."""
         n_draws = int(n_draws)
         if n_draws < 0:
             raise ValueError("n_draws must be >= 0")
         batch = self._batch(batch)
-        b = self._rhs(self._beta_for_draws(beta, rtol, max_iter))
-        out = np.empty((n_draws, self.n))
+        self._check_where(where)
+        beta = self._beta_for_draws(beta, rtol, max_iter)
+        b = self._rhs(beta)
+        rows = self._rows_of(where)
+        out = np.empty((n_draws, rows.shape[0]))
+        z3 = None if z is None or not self._ref else self._nodes_in(z[2], n_draws, "l")
         for k0, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
-            out[k0:k0 + W.shape[1]] = W[self.pos].t().cpu().numpy()
+            if self._ref and where == "data" and self.n_nodes > self.n_s:
+                kc = W.shape[1]
+                W = self._node_cols(W, self._leaf_v(beta, kc),
+                                    self._leaf_normals(k0, kc, n_draws, seed, z3, self.LEAF_STREAM))
+            out[k0:k0 + W.shape[1]] = W[rows].t().cpu().numpy()
         return out
 
     # -- posterior uncertainty ---------------------------------------------------
     def marginal_variance(self, n_draws: int = 64, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,
-                          max_iter: Optional[int] = None, batch=None) -> np.ndarray:
+                          max_iter: Optional[int] = None, batch=None, where: str = "data") -> np.ndarray:
         """``(N,)`` posterior variances of w by the Rao-Blackwellised estimator over ``n_draws`` >= 2 exact draws.
         Given the rest of a draw w, w_i is Gaussian with mean c_i = w_i - (A w - b)_i / A_ii and variance 1 / A_ii,
         so Var(w_i | y) = 1 / A_ii + Var(c_i), estimated by
@@ -356,24 +611,118 @@ class LatentPosterior:
         Only the second part carries Monte-Carlo error (relative standard deviation sqrt(2 / (K - 1)) of that
         part).  A w is one batched operator application per chunk of ``batch`` draws, A_ii comes from
         ``nngp_precision_diag``; the sums run on the device, draw by draw in draw order (shifted by the first
-        draw's c, so nothing cancels), hence the result does not depend on ``batch``.  Arguments as :meth:`sample`."""
+        draw's c, so nothing cancels), hence the result does not depend on ``batch``.  Arguments as :meth:`sample`.
+
+        With a reference set the estimator above runs on A_S for the reference nodes; a leaf j, Gaussian given w_S
+        with variance 1 / (f_j + d_j), gets v_j = 1 / (f_j + d_j) + the sample variance of its conditional mean
+        over the draws of w_S (``z = (z1, z2)``: no leaf noise is drawn)."""
         n_draws = int(n_draws)
         if n_draws < 2:
             raise ValueError("marginal_variance needs n_draws >= 2")
         batch = self._batch(batch)
-        b = self._rhs(self._beta_for_draws(beta, rtol, max_iter))
-        aii = _lib.precision_diag(self._prep, self.n, self.m, self.cov.sigma2, d=self.d)
+        self._check_where(where)
+        beta = self._beta_for_draws(beta, rtol, max_iter)
+        b = self._rhs(beta)
+        if self._ref:
+            aii = _lib.precision_ref_diag(*self._rgeom(), d=self.d, workspace=self._batch_ws(1))
+            base = torch.cat([aii, self.d[self.n_s:] + 1.0 / (self.cov.sigma2 * self.F[self.n_s:])])
+        else:
+            base = aii = _lib.precision_diag(self._prep, self.n, self.m, self.cov.sigma2, d=self.d)
         shift = None
-        s1 = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        s1 = torch.zeros(self.n_nodes, dtype=torch.float64, device=self.device)
         s2 = torch.zeros_like(s1)
         for _, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
-            AW = _lib.precision_apply_batch(*self._geom(), W, d=self.d, workspace=self._batch_ws(W.shape[1]))
+            AW = self._apply_cols(W)
             C = W - (AW - b[:, None]) / aii[:, None]
+            if self._ref and self.n_nodes > self.n_s:  # a leaf's conditional mean given this draw of w_S
+                C = torch.cat([C, self._leaf_cols(W, self._leaf_v(beta, W.shape[1]))])
             if shift is None:
                 shift = C[:, 0].clone()
             for c in range(C.shape[1]):
                 dev = C[:, c] - shift
                 s1 += dev
                 s2 += dev * dev
-        v = 1.0 / aii + (s2 - s1 * s1 / n_draws) / (n_draws - 1)
-        return v[self.pos].cpu().numpy()
+        v = 1.0 / base + (s2 - s1 * s1 / n_draws) / (n_draws - 1)
+        return v[self._rows_of(where)].cpu().numpy()
+
+    # -- new locations -----------------------------------------------------------
+    def predict(self, query, n_draws: int = 0, seed: int = 0, response: bool = False, beta=None, rtol: float = 1e-8,
+                max_iter: Optional[int] = None, batch=None, z=None, zq=None):
+        """The latent field at the points ``query`` (Q, d): ``(mean, var, draws)``.  A query point is an unobserved
+        leaf of the reference set (S = T: of the data locations): its parents are its m nearest reference points
+        (``nngp_knn_query``), its B_q / F_q the unit-variance factors without a nugget (``nngp_bf_cross``),
+        factorised once per call, and all columns go through ``nngp_latent_ref_leaves_batch``, ``batch`` at a time.
+
+        mean = B_q w_hat_S.  var = sigma2 F_q + the sample variance over the draws of B_q w_S^(k) (the law of total
+        variance; None when n_draws < 2).  draws (n_draws, Q): B_q w_S^(k) + (sigma2 F_q)^1/2 z_k, exact draws of
+        the latent field at the query points; ``response=True`` adds the noise of a new observation, tau2.  The
+        draws of w_S are those of :meth:`sample` for this ``seed``; ``z`` as there, ``zq`` (n_draws, Q): given
+        normals for the conditional noise (testing).  No covariate term is added: the mean is of w alone."""
+        n_draws = int(n_draws)
+        if n_draws < 0:
+            raise ValueError("n_draws must be >= 0")
+        batch = self._batch(batch)
+        q_host = np.ascontiguousarray(query.detach().cpu().numpy() if isinstance(query, torch.Tensor) else query,
+                                      dtype=np.float64)
+        if q_host.ndim == 1:
+            q_host = q_host[:, None]
+        if q_host.ndim != 2 or q_host.shape[1] != self.coords.shape[1] or not np.all(np.isfinite(q_host)):
+            raise ValueError(f"query must be finite (Q, {self.coords.shape[1]}), got {q_host.shape}")
+        Q, n_s, dev, cov = q_host.shape[0], self.n_s, self.device, self.cov
+        if zq is not None:
+            zq = torch.from_numpy(np.asarray(zq, dtype=np.float64).reshape(n_draws, Q)).to(dev)
+        beta = self._beta_for_draws(beta, rtol, max_iter)
+        b = self._rhs(beta)
+        w_hat, _ = self._solve(b, rtol, max_iter)
+        if Q == 0:
+            return np.zeros(0), (np.zeros(0) if n_draws >= 2 else None), np.zeros((n_draws, 0))
+        # the prediction DAG: the query points as leaves of the reference points they name
+        q = torch.from_numpy(q_host).to(dev)
+        s_coords = self.coords[:n_s].contiguous()
+        k = min(self.m, n_s)
+        nbr_q = _lib.knn_query(s_coords, q, k)
+        B_q, F_q, p = _lib.bf_cross(s_coords, q, nbr_q, cov.kind, 1.0, cov.phi, 0.0, nu=cov.nu_arg)
+        _raise_on_bad(p.cpu().numpy())
+        if k < self.m:
+            nbr_q = torch.cat([nbr_q, torch.full((Q, self.m - k), -1, dtype=torch.int32, device=dev)], dim=1)
+            B_q = torch.cat([B_q, torch.zeros((Q, self.m - k), dtype=torch.float64, device=dev)], dim=1)
+        # The leaves call reads a leaf row's nbr / B / invF and x at its parents, nothing of the reference rows: the
+        # DAG handed to it keeps only the u <= Q m distinct parents, as parentless nodes, and x is gathered to them.
+        # Its size, and that of its reverse lists and prep, does not depend on n_S; a row's slots, hence its sum,
+        # are what they would be over all of S.
+        valid = nbr_q >= 0
+        parents, inv = torch.unique(nbr_q[valid].long(), return_inverse=True)
+        n_u = parents.numel()
+        nbr_c = torch.full_like(nbr_q, -1)
+        nbr_c[valid] = inv.to(torch.int32)
+        nbr_a = torch.cat([torch.full((n_u, self.m), -1, dtype=torch.int32, device=dev), nbr_c]).contiguous()
+        B_a = torch.cat([torch.zeros((n_u, self.m), dtype=torch.float64, device=dev), B_q]).contiguous()
+        F_a = torch.cat([torch.ones(n_u, dtype=torch.float64, device=dev), F_q]).contiguous()
+        off, rev_j, rev_k = _lib.reverse_neighbors(nbr_a)
+        prep = _lib.gibbs_prepare(B_a, F_a, off, rev_j, rev_k)
+        geom = (nbr_a, B_a, off, rev_j, rev_k, prep, n_u, cov.sigma2)
+        mean = _lib.latent_ref_leaves_batch(*geom, w_hat[parents][:, None].contiguous())[:, 0].cpu().numpy()
+        draws = np.empty((n_draws, Q))
+        shift = None
+        s1 = torch.zeros(Q, dtype=torch.float64, device=dev)
+        s2 = torch.zeros_like(s1)
+        for k0, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
+            kc = W.shape[1]
+            W = W[parents].contiguous()
+            M = _lib.latent_ref_leaves_batch(*geom, W)  # B_q w_S^(k)
+            D = _lib.latent_ref_leaves_batch(*geom, W, z=self._leaf_normals(k0, kc, n_draws, seed, zq,
+                                                                           self.QUERY_STREAM, size=Q))
+            if response:
+                D = D + math.sqrt(cov.tau2) * self._leaf_normals(k0, kc, n_draws, seed, None,
+                                                                 self.RESPONSE_STREAM, size=Q)
+            draws[k0:k0 + kc] = D.t().cpu().numpy()
+            if shift is None:
+                shift = M[:, 0].clone()
+            for c in range(kc):
+                dev_c = M[:, c] - shift
+                s1 += dev_c
+                s2 += dev_c * dev_c
+        var = None
+        if n_draws >= 2:
+            var = (cov.sigma2 * F_q + (s2 - s1 * s1 / n_draws) / (n_draws - 1)).cpu().numpy()
+        return mean, var, draws

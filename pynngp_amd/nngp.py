@@ -864,27 +864,61 @@ class NNGP:
         self._latent = (mean, self.nbr, lp)
         return lp
 
+    def latent_posterior(self, cov: Optional[Covariance] = None, mean: str = "constant"):
+        """The :class:`pynngp_amd.LatentPosterior` of this instance at ``cov`` (default ``self.cov``), for every
+        ``refType``: 'S=T' puts the field on the data locations (and reuses the neighbour sets held here); a
+        tuple refType puts it on ``s`` with the data locations outside S as leaves that are integrated out
+        (``LatentPosterior(ref=s)``), so the solver's vectors have one entry per reference point.  Kept between
+        calls: a new theta of the same mean is one ``update``.  ``mean="constant"`` estimates an intercept by GLS,
+        ``"zero"`` takes y as centred; NaN in ``y`` = unobserved; ``eps`` as :meth:`latent_mean`.  Its ``mean`` /
+        ``sample`` / ``marginal_variance`` take ``where="data"`` or ``"ref"``, and ``predict(query)`` gives the
+        mean, variance and draws at new locations."""
+        if self._same_sets():
+            return self._latent_posterior(cov, mean)
+        if mean not in ("constant", "zero"):
+            raise ValueError("mean must be 'constant' or 'zero'")
+        from .latent import LatentPosterior
+
+        cv = self.cov if cov is None else cov
+        held = getattr(self, "_latent_ref", None)
+        if held is not None and held[0] == mean and held[1] is self.s:
+            if held[2].cov != cv:
+                held[2].update(cv)
+            return held[2]
+        y = np.asarray(self.y, dtype=np.float64)
+        eps = None
+        if self.eps is not None:
+            ev = np.asarray(self.eps, dtype=np.float64)
+            if ev.shape == y.shape and np.all(np.isfinite(ev)) and np.all(ev > 0):
+                eps = ev
+        X = np.ones((y.shape[0], 1)) if mean == "constant" and y.ndim == 1 else None
+        lp = LatentPosterior(self.t, y, cv, m=self.m, X=X, eps=eps, device=self.device, ref=self.s)
+        self._latent_ref = (mean, self.s, lp)
+        return lp
+
     def latent_mean(self, cov: Optional[Covariance] = None, rtol: float = 1e-8, mean: str = "constant"):
         """Posterior mean of the latent field w on the data locations at a fixed ``cov`` (default ``self.cov``,
         e.g. after :meth:`fit`): ``(w_hat, beta_hat)`` from a conjugate-gradient solve with the NNGP posterior
         precision (:class:`pynngp_amd.LatentPosterior`) -- the deterministic estimator of the reference's ``ws`` /
         ``wt`` state (nngp.py:42-47).  ``mean="constant"`` estimates an intercept by GLS (as :meth:`fit`
         profiles it out), ``"zero"`` takes y as centred.  NaN in ``y`` = unobserved; ``eps``, when it is one
-        positive sigma per location, scales the noise variance to tau2 eps_i^2.  refType 'S=T' only.
+        positive sigma per location, scales the noise variance to tau2 eps_i^2.  refType 'S=T' only; for a
+        reference set (and for prediction with uncertainty) use :meth:`latent_posterior`.
         The latent mean at new locations is ``predict(values=w_hat, cov=cov.replace(tau2=0), query=...)``."""
         return self._latent_posterior(cov, mean).mean(rtol=rtol)
 
     def latent_sample(self, n: int, cov: Optional[Covariance] = None, seed: int = 0, mean: str = "constant"):
         """``(n, N)`` exact draws of w | y, theta at a fixed ``cov`` (perturbation sampling on the same solver;
-        Philox normals keyed by ``seed``).  refType 'S=T' only; arguments as :meth:`latent_mean`."""
+        Philox normals keyed by ``seed``).  refType 'S=T' only (a reference set: :meth:`latent_posterior`);
+        arguments as :meth:`latent_mean`."""
         return self._latent_posterior(cov, mean).sample(n, seed=seed)
 
     def latent_sd(self, n_draws: int = 64, cov: Optional[Covariance] = None, seed: int = 0,
                   mean: str = "constant") -> np.ndarray:
         """``(N,)`` posterior standard deviations of w | y, theta at a fixed ``cov``: the square root of
         :meth:`pynngp_amd.LatentPosterior.marginal_variance` (Rao-Blackwellised over ``n_draws`` exact draws,
-        relative standard error about sqrt(2 / (n_draws - 1)) at worst).  refType 'S=T' only; arguments as
-        :meth:`latent_mean`."""
+        relative standard error about sqrt(2 / (n_draws - 1)) at worst).  refType 'S=T' only (a reference set:
+        :meth:`latent_posterior`); arguments as :meth:`latent_mean`."""
         return np.sqrt(self._latent_posterior(cov, mean).marginal_variance(n_draws, seed=seed))
 
     def oneSample(self, seed: int = 0, X=None, **sampler_kw):

@@ -15,8 +15,17 @@ With --nrhs K1,K2,... it measures the batched operator instead (nngp_precision_a
   * the wall time of 8 posterior draws through the batched path (LatentPosterior.sample) beside the loop of
     single square-root applications and single solves that served before it, and of marginal_variance(64);
   * the gate: one application at nrhs = 8 against 8 single applications.
+With --ref N_S it measures the posterior on a reference set of N_S points drawn uniformly in the data's bounding
+box (seed 1), the leaves integrated out (nngp_precision_ref_*, nngp_latent_ref_cg_batch), beside the AUGMENTED system:
+the same node DAG (reference points, then every data location as a leaf, d = 0 on a node without data) through
+the S = T calls nngp_precision_apply_batch / nngp_latent_cg_batch (the same arithmetic and resource usage as before
+the reference-set forms were added).  Both run in this
+process in alternating rounds: ms per application, iterations and wall time of the posterior mean to --rtol, 8
+draws at every data location, and the solver's workspace bytes; the gate is the mean solve, eliminated against
+augmented beyond three times the larger max - min spread of the pair.
 Synthetic data as bench.py (uniform coordinates, standard-normal values, seed 0); prints one JSON line.
     python tools/bench_latent.py [--n 1000000 --m 15 --reps 1000 --warmup 100] [--nrhs 1,2,4,8 --rounds 3]
+    python tools/bench_latent.py --ref 100000 [--rounds 3 --reps 200]
 """
 import argparse
 import json
@@ -132,6 +141,94 @@ def bench_batch(lp, args, res):
                gate_sample={"passed": bool(statistics.median(batch_ms) <= statistics.median(loop_ms))})
 
 
+def bench_ref(coords, y, args, dev):
+    """The --ref measurement (see the module docstring): the result dict."""
+    import numpy as np
+
+    c_host = coords.detach().cpu().numpy() if isinstance(coords, torch.Tensor) else np.asarray(coords)
+    lo, hi = c_host.min(axis=0), c_host.max(axis=0)
+    ref = np.random.default_rng(1).uniform(lo, hi, (args.ref, c_host.shape[1]))
+    cov = Covariance("exponential", args.sigma2, args.phi, args.tau2)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    lp = LatentPosterior(coords, y, cov, m=args.m, device=dev, ref=ref)
+    torch.cuda.synchronize()
+    setup_s = time.perf_counter() - t0
+    n, n_s, lib = lp.n_nodes, lp.n_s, _lib.load()
+    aug, elim = lp._geom(), lp._rgeom()
+    ws_bytes = {"eliminated": {str(k): lib.nngp_latent_ref_cg_batch_workspace_bytes(n, n_s, k) for k in (1, 8)},
+                "augmented": {str(k): lib.nngp_latent_cg_batch_workspace_bytes(n, k) for k in (1, 8)}}
+    ws_e = _lib._workspace(ws_bytes["eliminated"]["8"], dev)
+    ws_a = _lib._workspace(ws_bytes["augmented"]["8"], dev)
+    gen = torch.Generator(dev).manual_seed(1)
+    xs = torch.randn((n_s, 1), dtype=torch.float64, device=dev, generator=gen)
+    xa = torch.randn((n, 1), dtype=torch.float64, device=dev, generator=gen)
+    os_, oa = torch.empty_like(xs), torch.empty_like(xa)
+    b_s = lp._rhs(())
+    b_a = (lp.d * lp.y)[:, None].contiguous()
+    max_iter = 20000
+    seed = 0
+
+    def mean_elim():
+        X, info = _lib.latent_ref_cg_batch(*elim, b_s[:, None].contiguous(), torch.zeros((n_s, 1), dtype=torch.float64,
+                                                                                         device=dev),
+                                           d=lp.d, rtol=args.rtol, max_iter=max_iter, workspace=ws_e)
+        return lp._node_cols(X, lp._leaf_v((), 1)), info
+
+    def mean_aug():
+        return _lib.latent_cg_batch(*aug, b_a, torch.zeros_like(b_a), d=lp.d, rtol=args.rtol, max_iter=max_iter,
+                                    workspace=ws_a)
+
+    def draws_aug():
+        Z1 = torch.empty((n, 8), dtype=torch.float64, device=dev)
+        Z2 = torch.empty_like(Z1)
+        zz = torch.empty(n, dtype=torch.float64, device=dev)
+        for c in range(8):
+            Z1[:, c] = _lib.gibbs_normals(zz, seed, 2 * c)
+            Z2[:, c] = _lib.gibbs_normals(zz, seed, 2 * c + 1)
+        eta = _lib.precision_sqrt_t_apply_batch(*aug, Z1, Z2, d=lp.d, workspace=ws_a)
+        R = (b_a + eta).contiguous()
+        X, _ = _lib.latent_cg_batch(*aug, R, torch.zeros_like(R), d=lp.d, rtol=args.rtol, max_iter=max_iter,
+                                    workspace=ws_a)
+        return X[lp.slot_of_t].t().cpu().numpy()
+
+    ops = {"eliminated": lambda: _lib.precision_ref_apply_batch(*elim, xs, d=lp.d, out=os_, workspace=ws_e),
+           "augmented": lambda: _lib.precision_apply_batch(*aug, xa, d=lp.d, out=oa, workspace=ws_a)}
+    means = {"eliminated": mean_elim, "augmented": mean_aug}
+    draws = {"eliminated": lambda: lp.sample(8, seed=seed, rtol=args.rtol), "augmented": draws_aug}
+    we, ie = mean_elim()
+    wa, ia = mean_aug()  # (both warm now)
+    diff = float((we[:, 0] - wa[:, 0]).abs().max() / wa[:, 0].abs().max())
+    op_ms = {k: [] for k in ops}
+    mean_ms = {k: [] for k in ops}
+    draw_ms = {k: [] for k in ops}
+    for r in range(args.rounds):  # alternating: every variant once per round
+        for k in ops:
+            op_ms[k].append(timed(ops[k], args.warmup if r == 0 else 10, args.reps))
+        for k in ops:
+            mean_ms[k] += wall_ms(means[k], 1)
+        for k in ops:
+            draw_ms[k] += wall_ms(draws[k], 1)
+    med = lambda v: statistics.median(v)  # noqa: E731
+    spread = lambda v: max(v) - min(v)  # noqa: E731
+    margin = med(mean_ms["augmented"]) - med(mean_ms["eliminated"])
+    worst = 3 * max(spread(mean_ms["augmented"]), spread(mean_ms["eliminated"]))
+    return {"workload": f"latent posterior on a reference set, N={lp.n} data, n_S={n_s}, nodes={n}, m={args.m}, "
+                        f"exponential, sigma2={args.sigma2}, phi={args.phi}, tau2={args.tau2}",
+            "setup_s": setup_s, "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup, "rtol": args.rtol,
+            "operator_ms_rounds": op_ms, "operator_ms_median": {k: med(v) for k, v in op_ms.items()},
+            "mean_iterations": {"eliminated": int(ie[0, 0]), "augmented": int(ia[0, 0])},
+            "mean_converged": {"eliminated": bool(ie[0, 1] > 0), "augmented": bool(ia[0, 1] > 0)},
+            "mean_wall_ms_rounds": mean_ms, "mean_wall_ms_median": {k: med(v) for k, v in mean_ms.items()},
+            "mean_wall_ms_spread": {k: spread(v) for k, v in mean_ms.items()},
+            "mean_max_rel_diff_between_variants": diff,
+            "sample8_wall_ms_rounds": draw_ms, "sample8_wall_ms_median": {k: med(v) for k, v in draw_ms.items()},
+            "cg_workspace_bytes": ws_bytes,
+            "cg_workspace_ratio_nrhs1": ws_bytes["eliminated"]["1"] / ws_bytes["augmented"]["1"],
+            "gate_mean": {"augmented_minus_eliminated_ms": margin, "three_times_larger_spread_ms": worst,
+                          "eliminated_no_slower": bool(margin >= -worst)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -147,13 +244,18 @@ def main():
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--nrhs", type=lambda v: [int(t) for t in v.split(",")], default=None,
                     help="comma-separated column counts: measure the batched operator and the batched draws instead")
-    ap.add_argument("--rounds", type=int, default=3, help="alternating rounds per variant (--nrhs)")
+    ap.add_argument("--rounds", type=int, default=3, help="alternating rounds per variant (--nrhs, --ref)")
+    ap.add_argument("--ref", type=int, default=None,
+                    help="reference-set size: measure the eliminated system against the augmented one instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_latent needs a ROCm GPU (a timing without one says nothing)")
     dev = torch.device("cuda", 0)
     n, m = args.n, args.m
     coords, y = synth(n)
+    if args.ref:
+        print(json.dumps(bench_ref(coords, y, args, dev)))
+        return
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     lp = LatentPosterior(coords, y, Covariance("exponential", args.sigma2, args.phi, args.tau2), m=m, device=dev)
