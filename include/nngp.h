@@ -496,6 +496,38 @@ int nngp_gibbs_stats(int64_t n, const double *r, const double *Ft, const double 
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Binomial / logistic response by Polya-Gamma augmentation (Polson, Scott and Windle 2013; spNNGP's
+ * family = "binomial" -- the reference has no such model): s_i ~ Binomial(b_i, logistic(x_i beta + w_i)).
+ * With omega_i ~ PG(b_i, x_i beta + w_i) the update of w is the Gaussian one of nngp_gibbs_w_sweep with
+ * tau2 = 1, noise_w = omega and yres_i = kappa_i / omega_i - x_i beta, kappa_i = s_i - b_i / 2.
+ * (pynngp_amd/csrc/polya_gamma.h: Devroye's exact PG(1, c) sampler, PG(b, c) the sum of b draws.)
+ * Added within ABI revision 4 (nothing earlier moved).
+ *
+ * nngp_polya_gamma: omega[i] ~ PG(trials[i], c[i]), 0 <= trials[i] <= NNGP_PG_MAX_TRIALS (trials = 0: exactly 0).
+ *   Philox4x32-10, key = seed, counter (i, sweep | 1 << 62 | j << 40) for the location's j-th 128-bit block
+ *   (sweep < 2^40): a draw depends on (seed, sweep, i, trials[i], c[i]) alone, and shares no block with
+ *   nngp_gibbs_normals at any sweep (bit 62).  Faults are data: a location whose c is not finite, whose trials is
+ *   out of range or whose sampler hit one of its loop caps gets NaN, and status[0] (one device int32, zeroed by
+ *   the call) receives the smallest such index + 1; 0 = clean.
+ * nngp_gibbs_pg_update: one sampler iteration's draw, fused: c_i = xb[i] + w[i], omega as nngp_polya_gamma on
+ *   that c (bit for bit), yres[i] = kappa[i] / omega[i] - xb[i]; trials[i] = 0: omega[i] = 0 and yres[i] = 0.
+ * nngp_gibbs_pg_stats: out[0] = sum r_i^2 / Ft_i, then the upper triangle of X' diag(omega) X row by row
+ *   (p (p + 1) / 2 values), then X' (kappa - omega w) (p values); X row-major (n, p), 0 <= p <= 62.  Per-block
+ *   records folded in a fixed order, as nngp_gibbs_stats: the same bits on every call.  workspace: at least
+ *   nngp_gibbs_pg_stats_workspace_bytes(n, p) bytes.
+ * ------------------------------------------------------------------------- */
+#define NNGP_PG_MAX_TRIALS 1024
+int nngp_polya_gamma(int64_t n, const int32_t *trials, const double *c, uint64_t seed, uint64_t sweep,
+                     double *omega, int32_t *status, void *stream);
+int nngp_gibbs_pg_update(int64_t n, const int32_t *trials, const double *kappa, const double *xb,
+                         const double *w, uint64_t seed, uint64_t sweep,
+                         double *omega, double *yres, int32_t *status, void *stream);
+size_t nngp_gibbs_pg_stats_workspace_bytes(int64_t n, int32_t p);
+int nngp_gibbs_pg_stats(int64_t n, const double *r, const double *Ft, const double *omega,
+                        const double *kappa, const double *X, int32_t p, const double *w,
+                        double *out, void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Latent-field posterior at fixed theta (S = T).  The reference keeps the latent state as ws / wt
  * (pyNNGP/nngp.py:42-47) and only names a sampler for it (oneSample, nngp.py:98-101); for fixed
  * (sigma2, phi, tau2) the posterior is Gaussian and explicit,

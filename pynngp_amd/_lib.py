@@ -89,6 +89,10 @@ SYMBOLS = (
     "nngp_latent_ref_cg_batch_workspace_bytes",
     "nngp_latent_ref_cg_batch",
     "nngp_latent_ref_leaves_batch",
+    "nngp_polya_gamma",
+    "nngp_gibbs_pg_update",
+    "nngp_gibbs_pg_stats_workspace_bytes",
+    "nngp_gibbs_pg_stats",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -101,6 +105,7 @@ PLAN_INFO_LEN = 10  # NNGP_PLAN_INFO_LEN
 CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
 BLOCKS_MAX_M = 32  # nngp_bf_sweep_blocks: 1 <= m <= 32
 LATENT_MAX_RHS = 8  # NNGP_LATENT_MAX_RHS: right-hand sides per batched latent call
+PG_MAX_TRIALS = 1024  # NNGP_PG_MAX_TRIALS: binomial trials per location of a Polya-Gamma draw
 
 
 class NNGPExtensionError(RuntimeError):
@@ -199,6 +204,14 @@ def load() -> ctypes.CDLL:
     lib.nngp_gibbs_stats_workspace_bytes.restype = SZ
     lib.nngp_gibbs_stats.argtypes = [I64, P, P, P, P, P, I32, P, P, P, P, SZ, P]
     lib.nngp_gibbs_stats.restype = ctypes.c_int
+    lib.nngp_polya_gamma.argtypes = [I64, P, P, U64, U64, P, P, P]
+    lib.nngp_polya_gamma.restype = ctypes.c_int
+    lib.nngp_gibbs_pg_update.argtypes = [I64, P, P, P, P, U64, U64, P, P, P, P]
+    lib.nngp_gibbs_pg_update.restype = ctypes.c_int
+    lib.nngp_gibbs_pg_stats_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_gibbs_pg_stats_workspace_bytes.restype = SZ
+    lib.nngp_gibbs_pg_stats.argtypes = [I64, P, P, P, P, P, I32, P, P, P, P]
+    lib.nngp_gibbs_pg_stats.restype = ctypes.c_int
     lib.nngp_bf_sweep.restype = ctypes.c_int
     lib.nngp_color_moral_graph_dev.argtypes = [P, P, P, I64, I32, P, P, SZ, P]
     lib.nngp_color_moral_graph_dev.restype = I64
@@ -1167,6 +1180,98 @@ def gibbs_stats(r: torch.Tensor, Ft: torch.Tensor, yres: torch.Tensor, y: torch.
         workspace = _workspace(need, dev)
     _check(lib.nngp_gibbs_stats(n, _ptr(r), _ptr(Ft), _ptr(yres), _ptr(y), _ptr(X), p, _ptr(w), _ptr(noise_w), _ptr(out),
                                 _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_gibbs_stats")
+    return out
+
+
+# ---------------------------------------------------------------------------- Polya-Gamma draws (binomial model)
+def check_trials(trials) -> None:
+    """Refuse trials outside [0, PG_MAX_TRIALS] before any launch (one host synchronisation for a device tensor)."""
+    if trials.numel() and (int(trials.min()) < 0 or int(trials.max()) > PG_MAX_TRIALS):
+        raise ValueError(f"trials must lie in [0, {PG_MAX_TRIALS}] (got [{int(trials.min())}, {int(trials.max())}])")
+
+
+def _pg_vec(t, n, name, dtype=torch.float64):
+    if t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} ({n},) tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def _pg_sweep(sweep) -> int:
+    if not 0 <= int(sweep) < 2 ** 40:
+        raise ValueError("sweep (the iteration) must lie in [0, 2^40)")
+    return int(sweep)
+
+
+def polya_gamma(trials: torch.Tensor, c: torch.Tensor, seed: int = 0, sweep: int = 0,
+                omega: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, checked: bool = False):
+    """omega[i] ~ PG(trials[i], c[i]) (nngp_polya_gamma): returns (omega, status), status an int32 (1,) device
+    tensor holding 0 (clean) or the smallest index + 1 whose draw is NaN (non-finite c, or a loop cap).
+    ``checked``: the caller has range-checked ``trials`` already."""
+    if not (trials.is_cuda and c.is_cuda):
+        raise NotImplementedError("pynngp_amd has no CPU path: polya_gamma needs ROCm GPU tensors")
+    dev = _require_gpu(trials, c, omega, status)
+    n = trials.shape[0] if trials.dim() == 1 else -1
+    _pg_vec(trials, n, "trials", torch.int32)
+    _pg_vec(c, n, "c")
+    if not checked:
+        check_trials(trials)
+    omega = torch.empty(n, dtype=torch.float64, device=dev) if omega is None else omega
+    status = torch.empty(1, dtype=torch.int32, device=dev) if status is None else status
+    _pg_vec(omega, n, "omega")
+    _pg_vec(status, 1, "status", torch.int32)
+    _check(load().nngp_polya_gamma(n, _ptr(trials), _ptr(c), int(seed) & (2 ** 64 - 1), _pg_sweep(sweep), _ptr(omega),
+                                   _ptr(status), _stream(dev)), "nngp_polya_gamma")
+    return omega, status
+
+
+def gibbs_pg_update(trials: torch.Tensor, kappa: torch.Tensor, xb: torch.Tensor, w: torch.Tensor, seed: int,
+                    sweep: int, omega: Optional[torch.Tensor] = None, yres: Optional[torch.Tensor] = None,
+                    status: Optional[torch.Tensor] = None, checked: bool = False):
+    """The binomial sampler's fused draw (nngp_gibbs_pg_update): omega ~ PG(trials, xb + w) and
+    yres = kappa / omega - xb (both 0 where trials = 0); returns (omega, yres, status)."""
+    if not (trials.is_cuda and kappa.is_cuda and xb.is_cuda and w.is_cuda):
+        raise NotImplementedError("pynngp_amd has no CPU path: gibbs_pg_update needs ROCm GPU tensors")
+    dev = _require_gpu(trials, kappa, xb, w, omega, yres, status)
+    n = trials.shape[0] if trials.dim() == 1 else -1
+    _pg_vec(trials, n, "trials", torch.int32)
+    for t, name in ((kappa, "kappa"), (xb, "xb"), (w, "w")):
+        _pg_vec(t, n, name)
+    if not checked:
+        check_trials(trials)
+    omega = torch.empty(n, dtype=torch.float64, device=dev) if omega is None else omega
+    yres = torch.empty(n, dtype=torch.float64, device=dev) if yres is None else yres
+    status = torch.empty(1, dtype=torch.int32, device=dev) if status is None else status
+    _pg_vec(omega, n, "omega")
+    _pg_vec(yres, n, "yres")
+    _pg_vec(status, 1, "status", torch.int32)
+    _check(load().nngp_gibbs_pg_update(n, _ptr(trials), _ptr(kappa), _ptr(xb), _ptr(w), int(seed) & (2 ** 64 - 1),
+                                       _pg_sweep(sweep), _ptr(omega), _ptr(yres), _ptr(status), _stream(dev)),
+           "nngp_gibbs_pg_update")
+    return omega, yres, status
+
+
+def gibbs_pg_stats(r: torch.Tensor, Ft: torch.Tensor, omega: torch.Tensor, kappa: torch.Tensor,
+                   X: Optional[torch.Tensor], w: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[sum r^2/Ft, upper triangle of X' Omega X (row by row), X'(kappa - Omega w)] as a float64 device tensor
+    (1 + p (p + 1) / 2 + p,) (nngp_gibbs_pg_stats; fixed-order folds: the same bits on every call)."""
+    dev = _require_gpu(r, Ft, omega, kappa, X, w, out, workspace)
+    n = r.shape[0] if r.dim() == 1 else -1
+    for t, name in ((r, "r"), (Ft, "Ft"), (omega, "omega"), (kappa, "kappa"), (w, "w")):
+        _pg_vec(t, n, name)
+    p = 0 if X is None else X.shape[1]
+    if X is not None and (X.dtype != torch.float64 or tuple(X.shape) != (n, p) or not X.is_contiguous()):
+        raise ValueError(f"X must be a contiguous float64 ({n}, p) tensor")
+    nv = 1 + p * (p + 1) // 2 + p
+    lib = load()
+    need = lib.nngp_gibbs_pg_stats_workspace_bytes(n, p)
+    if need == 0:
+        raise ValueError(f"gibbs_pg_stats needs n >= 1 and 0 <= p <= 62 (n={n}, p={p})")
+    out = torch.empty(nv, dtype=torch.float64, device=dev) if out is None else out
+    _pg_vec(out, nv, "out")
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_gibbs_pg_stats(n, _ptr(r), _ptr(Ft), _ptr(omega), _ptr(kappa), _ptr(X), p, _ptr(w), _ptr(out),
+                                   _ptr(workspace), _stream(dev)), "nngp_gibbs_pg_stats")
     return out
 
 

@@ -767,6 +767,48 @@ int nngp_gibbs_stats(int64_t n, const double* r, const double* Ft, const double*
     return NNGP_OK;
 }
 
+// ---------------------------------------------------------------- Polya-Gamma draws (polya_gamma.hip)
+int nngp_polya_gamma(int64_t n, const int32_t* trials, const double* c, uint64_t seed, uint64_t sweep, double* omega,
+                     int32_t* status, void* stream) {
+    if (n < 0 || n >= INT32_MAX) return fail(NNGP_EINVAL, "bad n=%lld (0 <= n < 2^31 - 1)", (long long)n);
+    if (status == nullptr || (n > 0 && (trials == nullptr || c == nullptr || omega == nullptr)))
+        return fail(NNGP_EINVAL, "null pointer argument");
+    if (sweep >> 40) return fail(NNGP_EINVAL, "sweep must be below 2^40");
+    hipError_t e = nngp::polya_gamma_launch(n, trials, c, nullptr, nullptr, nullptr, seed, sweep, omega, nullptr,
+                                            status, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "polya_gamma launch");
+    return NNGP_OK;
+}
+
+int nngp_gibbs_pg_update(int64_t n, const int32_t* trials, const double* kappa, const double* xb, const double* w,
+                         uint64_t seed, uint64_t sweep, double* omega, double* yres, int32_t* status, void* stream) {
+    if (n < 0 || n >= INT32_MAX) return fail(NNGP_EINVAL, "bad n=%lld (0 <= n < 2^31 - 1)", (long long)n);
+    if (status == nullptr || (n > 0 && (trials == nullptr || kappa == nullptr || xb == nullptr || w == nullptr ||
+                                        omega == nullptr || yres == nullptr)))
+        return fail(NNGP_EINVAL, "null pointer argument");
+    if (sweep >> 40) return fail(NNGP_EINVAL, "sweep must be below 2^40");
+    hipError_t e = nngp::polya_gamma_launch(n, trials, nullptr, kappa, xb, w, seed, sweep, omega, yres, status,
+                                            (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gibbs_pg_update launch");
+    return NNGP_OK;
+}
+
+size_t nngp_gibbs_pg_stats_workspace_bytes(int64_t n, int32_t p) {
+    if (n < 1 || p < 0 || p > 62) return 0;
+    return nngp::gibbs_pg_stats_workspace_bytes(n, p);
+}
+
+int nngp_gibbs_pg_stats(int64_t n, const double* r, const double* Ft, const double* omega, const double* kappa,
+                        const double* X, int32_t p, const double* w, double* out, void* workspace, void* stream) {
+    if (r == nullptr || Ft == nullptr || omega == nullptr || kappa == nullptr || w == nullptr || out == nullptr ||
+        workspace == nullptr || (p > 0 && X == nullptr))
+        return fail(NNGP_EINVAL, "null pointer argument");
+    if (n < 1 || p < 0 || p > 62) return fail(NNGP_EINVAL, "bad n or p");
+    hipError_t e = nngp::gibbs_pg_stats_launch(n, r, Ft, omega, kappa, X, p, w, out, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "gibbs_pg_stats launch");
+    return NNGP_OK;
+}
+
 // ---------------------------------------------------------------- latent-field posterior (latent.hip)
 // the checks the three calls share, before any launch; fills g
 static int latent_common(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,

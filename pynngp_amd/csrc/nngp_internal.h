@@ -217,6 +217,16 @@ hipError_t gibbs_stats_launch(int64_t n, const double* r, const double* Ft, cons
                               const double* X, int p, const double* w, const double* noise_w, double* out,
                               void* workspace, hipStream_t s);
 
+// Polya-Gamma draws and the binomial sampler's statistics (polya_gamma.hip).  c given: the plain sampler;
+// c == nullptr: the fused update (c = xb + w, yres = kappa / omega - xb written too)
+hipError_t polya_gamma_launch(int64_t n, const int32_t* trials, const double* c, const double* kappa,
+                              const double* xb, const double* w, uint64_t seed, uint64_t sweep, double* omega,
+                              double* yres, int32_t* status, hipStream_t s);
+size_t gibbs_pg_stats_workspace_bytes(int64_t n, int p);
+hipError_t gibbs_pg_stats_launch(int64_t n, const double* r, const double* Ft, const double* omega,
+                                 const double* kappa, const double* X, int p, const double* w, double* out,
+                                 void* workspace, hipStream_t s);
+
 // row-order plan (nngp_row_order): Morton-sorted local rows for cache locality
 size_t row_order_workspace_bytes(int64_t n_rows);
 hipError_t row_order_launch(const double* coords, int dim, int64_t i0, int64_t n_rows, int32_t* order,

@@ -454,6 +454,28 @@ std::tuple<at::Tensor, at::Tensor> latent_cg_batch(const at::Tensor& nbr, const 
     return {x, info};
 }
 
+// ---------------------------------------------------------------- Polya-Gamma draws (binomial model)
+// omega ~ PG(trials, c) per location and the status word (0 = clean, else the smallest index + 1 whose draw is
+// NaN: a non-finite c, trials outside [0, NNGP_PG_MAX_TRIALS] or a loop cap -- faults are data, the op does not
+// synchronise to read it)
+std::tuple<at::Tensor, at::Tensor> polya_gamma(const at::Tensor& trials, const at::Tensor& c, int64_t seed,
+                                               int64_t sweep) {
+    TORCH_CHECK(trials.is_cuda() && c.is_cuda(), "trials and c must be ROCm GPU tensors (there is no CPU fallback)");
+    const at::OptionalDeviceGuard guard(c.device());
+    check_same_device(c, trials, "trials");
+    TORCH_CHECK(trials.scalar_type() == at::kInt && trials.dim() == 1 && trials.is_contiguous(),
+                "trials must be a contiguous int32 (n,) tensor");
+    TORCH_CHECK(c.scalar_type() == at::kDouble && c.dim() == 1 && c.is_contiguous() && c.size(0) == trials.size(0),
+                "c must be a contiguous float64 (n,) tensor");
+    TORCH_CHECK(sweep >= 0 && sweep < ((int64_t)1 << 40), "sweep must lie in [0, 2^40)");
+    auto omega = at::empty_like(c);
+    auto status = at::empty({1}, c.options().dtype(at::kInt));
+    check_rc(nngp_polya_gamma(c.size(0), trials.data_ptr<int32_t>(), c.data_ptr<double>(), (uint64_t)seed,
+                              (uint64_t)sweep, omega.data_ptr<double>(), status.data_ptr<int32_t>(), stream(c)),
+             "nngp_polya_gamma");
+    return {omega, status};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
@@ -467,6 +489,7 @@ TORCH_LIBRARY(nngp, m) {
     m.def("latent_cg(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
           "Tensor? d, Tensor b, Tensor? x0=None, float rtol=1e-08, int max_iter=1000, int check_every=8) -> "
           "(Tensor, Tensor)");
+    m.def("polya_gamma(Tensor trials, Tensor c, int seed, int sweep) -> (Tensor, Tensor)");
     m.def("knn_prior(Tensor coords, int m, int q0, int q1) -> Tensor");
     m.def("knn_prior_rows(Tensor coords, int m, Tensor rows) -> Tensor");
     m.def("knn_query(Tensor ref, Tensor query, int k) -> Tensor");
@@ -487,6 +510,7 @@ TORCH_LIBRARY(nngp, m) {
 }
 
 TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
+    m.impl("polya_gamma", &polya_gamma);
     m.impl("knn_prior", &knn_prior);
     m.impl("knn_prior_rows", &knn_prior_rows);
     m.impl("knn_query", &knn_query);

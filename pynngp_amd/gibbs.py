@@ -82,6 +82,15 @@ def colour_dag(nbr, off, rev_j, n_s):
     return colors, n_colors, n_colors
 
 
+def refuse_binomial(what: str, args, kw) -> None:
+    """The multi-chain and sharded samplers are Gaussian only: refuse a binomial sampler (or its arguments)."""
+    if (kw.get("family", "gaussian") != "gaussian" or "trials" in kw or "successes" in kw
+            or any(getattr(a, "family", None) == "binomial" for a in args)):
+        raise NotImplementedError(f"{what} runs the Gaussian response model only: multi-chain and sharded binomial "
+                                  "runs are out of scope (run one BinomialSeqNNGP per chain on one GPU)")
+    kw.pop("family", None)
+
+
 @dataclasses.dataclass
 class Priors:
     sigma2_ig: tuple = (2.0, 1.0)  # inverse-gamma (shape, scale)
@@ -779,6 +788,7 @@ class SeqNNGPChains:
     """
 
     def __init__(self, coords, y, X=None, seeds=(0,), interleave: bool = True, **kw):
+        refuse_binomial("SeqNNGPChains", (coords, y, X), kw)
         seeds = [int(s) for s in seeds]
         # interleave: the colour steps read the chains' w and r from (n, C) copies (one sector per scattered
         # access for all chains; packed before and unpacked after each iteration's colour sweeps)

@@ -38,7 +38,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, ops
-from .gibbs import SeqNNGP
+from .gibbs import SeqNNGP, refuse_binomial
 from .sweep import combine_partials, shard_range
 
 
@@ -217,6 +217,7 @@ class ShardedSeqNNGP(SeqNNGP):
     def __init__(self, *args, rank: Optional[int] = None, world: Optional[int] = None, group=None,
                  collective: Optional[bool] = None, graphs: Optional[bool] = None, exchange: str = "halo",
                  **kwargs):
+        refuse_binomial("ShardedSeqNNGP", args, kwargs)
         if kwargs.get("cov") is not None:
             raise NotImplementedError("ShardedSeqNNGP runs the built-in covariance kinds; a callable cov(a, b) "
                                       "chain runs on one GPU (SeqNNGP(cov=...))")
