@@ -1276,31 +1276,101 @@ def gibbs_pg_stats(r: torch.Tensor, Ft: torch.Tensor, omega: torch.Tensor, kappa
 
 
 # ---------------------------------------------------------------------------- latent-field posterior
-def _latent_geometry(nbr, B, off, rev_j, rev_k, prep, *vectors):
-    """Shape / dtype checks of the operator's arguments (raw pointers below: a short array must never reach a
-    kernel); returns (device, n, m)."""
-    if nbr.dtype != torch.int32 or nbr.dim() != 2:
-        raise ValueError(f"nbr must be int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
-    n, m = nbr.shape
-    if not 1 <= m <= MAX_M:
-        raise ValueError(f"m={m} outside [1, {MAX_M}]")
-    if B.dtype != torch.float64 or tuple(B.shape) != (n, m):
-        raise ValueError(f"B must be float64 ({n}, {m}), got {B.dtype} {tuple(B.shape)}")
-    if off.dtype != torch.int32 or tuple(off.shape) != (n + 1,):
-        raise ValueError(f"off must be int32 ({n + 1},)")
-    for name, t in (("rev_j", rev_j), ("rev_k", rev_k)):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n * m:
-            raise ValueError(f"{name} must be int32 with at least n * m = {n * m} entries")
-    for t in vectors:
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (n,)):
-            raise ValueError(f"vectors must be float64 ({n},), got {t.dtype} {tuple(t.shape)}")
-    for t in (nbr, B, off, rev_j, rev_k, prep) + tuple(vectors):
-        if t is not None and not t.is_contiguous():
+# (include/nngp.h: "Latent-field posterior at fixed theta" and "... on a reference set")
+class _LatentCall:
+    """The arguments of one latent call, checked (raw pointers below: a short array must never reach a kernel), and
+    the call itself.  ``geom`` = (nbr, B, off, rev_j, rev_k, prep) of an n-node DAG whose first ``n_s`` nodes are
+    the reference set; ``n_s`` None: an S = T entry point (n_s = n, and the C call takes no n_s).  ``vectors``:
+    name -> (tensor, rows), rows one of "s" (the n_s reference nodes), "n" (all nodes) or "l" (the leaves), with a
+    "?" where the tensor may be None; each is float64 (rows, nrhs) with one nrhs in [1, LATENT_MAX_RHS], or
+    (rows,) when not ``batched`` (the C call then takes no nrhs).  ``d``: (n,) or None.  Every ValueError comes
+    before any device work."""
+
+    def __init__(self, geom, n_s, sigma2, d, batched=True, **vectors):
+        nbr, B, off, rev_j, rev_k, prep = geom
+        if nbr.dtype != torch.int32 or nbr.dim() != 2:
+            raise ValueError(f"nbr must be int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
+        n, m = nbr.shape
+        self.ref = n_s is not None
+        n_s = int(n_s) if self.ref else n
+        if not 0 <= n_s <= n:
+            raise ValueError(f"need 0 <= n_s <= n = {n}, got n_s={n_s}")
+        if not 1 <= m <= MAX_M:
+            raise ValueError(f"m={m} outside [1, {MAX_M}]")
+        if B.dtype != torch.float64 or tuple(B.shape) != (n, m):
+            raise ValueError(f"B must be float64 ({n}, {m}), got {B.dtype} {tuple(B.shape)}")
+        if off.dtype != torch.int32 or tuple(off.shape) != (n + 1,):
+            raise ValueError(f"off must be int32 ({n + 1},)")
+        for name, t in (("rev_j", rev_j), ("rev_k", rev_k)):
+            if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n * m:
+                raise ValueError(f"{name} must be int32 with at least n * m = {n * m} entries")
+        rows = {"s": n_s, "n": n, "l": n - n_s}
+        nrhs = None if batched else 1
+        for name, (t, kind) in vectors.items():
+            if t is None:
+                if not kind.endswith("?"):
+                    raise ValueError(f"{name} is needed")
+                continue
+            cols = nrhs if nrhs is not None else t.shape[1] if t.dim() == 2 else "nrhs"
+            shape = (rows[kind[0]], cols) if batched else (rows[kind[0]],)
+            if t.dtype != torch.float64 or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be float64 {shape}, got {t.dtype} {tuple(t.shape)}")
+            if nrhs is None:
+                nrhs = cols
+                if not 1 <= nrhs <= LATENT_MAX_RHS:
+                    raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
+        if d is not None and (d.dtype != torch.float64 or tuple(d.shape) != (n,)):
+            raise ValueError(f"d must be float64 ({n},), got {d.dtype} {tuple(d.shape)}")
+        if d is not None and "z2" in vectors and vectors["z2"][0] is None:
+            raise ValueError("z2 is needed when d is given")
+        tensors = geom + (d,) + tuple(t for t, _ in vectors.values())
+        if not all(t.is_contiguous() for t in tensors if t is not None):
             raise ValueError("the operator's arguments must be contiguous")
-    dev = _require_gpu(nbr, B, off, rev_j, rev_k, prep, *vectors)
-    if prep.dtype != torch.uint8 or prep.numel() < load().nngp_gibbs_prep_bytes(n, m):
-        raise ValueError("prep must be the uint8 buffer of gibbs_prepare for these factors")
-    return dev, n, m
+        self.dev = _require_gpu(*tensors)
+        if prep.dtype != torch.uint8 or prep.numel() < load().nngp_gibbs_prep_bytes(n, m):
+            raise ValueError("prep must be the uint8 buffer of gibbs_prepare for these factors")
+        self.geom, self.sigma2, self.d, self.batched, self.rows = geom, float(sigma2), d, batched, rows
+        self.n, self.n_s, self.m, self.nrhs = n, n_s, m, nrhs
+
+    def empty(self, kind):
+        """A result vector on the rows ``kind``."""
+        shape = (self.rows[kind], self.nrhs) if self.batched else (self.rows[kind],)
+        return torch.empty(shape, dtype=torch.float64, device=self.dev)
+
+    def __call__(self, symbol, args, ws_symbol=None, workspace=None):
+        """``symbol``(geometry, n[, n_s], m, sigma2, d[, nrhs], *args[, workspace, its bytes], stream); tensors
+        among ``args`` go as pointers.  ``ws_symbol``: the call takes a workspace of that many bytes, made here
+        unless the caller's is large enough."""
+        lib = load()
+        sizes = (self.n, self.n_s) if self.ref else (self.n,)
+        k = (self.nrhs,) if self.batched else ()
+        argv = [_ptr(t) for t in self.geom] + [*sizes, self.m, self.sigma2, _ptr(self.d), *k]
+        argv += [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+        if ws_symbol is not None:
+            need = getattr(lib, ws_symbol)(*sizes, *(k or ((1,) if self.ref else ())))
+            if workspace is None or workspace.numel() < need:
+                workspace = _workspace(need, self.dev)
+            argv += [_ptr(workspace), workspace.numel()]
+        _check(getattr(lib, symbol)(*argv, _stream(self.dev)), symbol)
+
+
+def _latent_apply(c, symbol, ws_symbol, x, out, workspace):
+    out = c.empty("s") if out is None else out
+    c(symbol, (x, out), ws_symbol, workspace)
+    return out
+
+
+def _latent_sqrt_t_apply(c, symbol, ws_symbol, z1, z2, out, workspace):
+    out = c.empty("s") if out is None else out
+    c(symbol, (z1, z2, out), ws_symbol, workspace)
+    return out
+
+
+def _latent_cg(c, symbol, ws_symbol, b, x, rtol, max_iter, check_every, workspace):
+    info = np.zeros((c.nrhs, 4), dtype=np.float64)
+    c(symbol, (b, x, float(rtol), int(max_iter), int(check_every), info.ctypes.data_as(ctypes.c_void_p)), ws_symbol,
+      workspace)
+    return x, info
 
 
 def precision_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
@@ -1309,16 +1379,8 @@ def precision_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j
     """out = [(I - B)^T (sigma2 F)^-1 (I - B) + diag(d)] x (nngp_precision_apply): ``prep`` from
     :func:`gibbs_prepare` of the unit-variance (B, F), the reverse lists from :func:`reverse_neighbors`;
     ``d`` None = the prior precision alone.  Bit-reproducible; stream-ordered, no host synchronisation."""
-    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, x, d, out)
-    lib = load()
-    out = torch.empty_like(x) if out is None else out
-    need = lib.nngp_precision_workspace_bytes(n)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    _check(lib.nngp_precision_apply(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
-                                    float(sigma2), _ptr(d), _ptr(x), _ptr(out), _ptr(workspace), workspace.numel(),
-                                    _stream(dev)), "nngp_precision_apply")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, False, x=(x, "s"), out=(out, "s?"))
+    return _latent_apply(c, "nngp_precision_apply", "nngp_precision_workspace_bytes", x, out, workspace)
 
 
 def precision_sqrt_t_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
@@ -1328,18 +1390,10 @@ def precision_sqrt_t_apply(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor
                            workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2 (nngp_precision_sqrt_t_apply): Cov(out) = A for standard
     normal z1, z2 -- the perturbation of exact posterior draws."""
-    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, z1, z2, d, out)
-    if d is not None and z2 is None:
-        raise ValueError("z2 is needed when d is given")
-    lib = load()
-    out = torch.empty_like(z1) if out is None else out
-    need = lib.nngp_precision_workspace_bytes(n)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    _check(lib.nngp_precision_sqrt_t_apply(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
-                                           float(sigma2), _ptr(d), _ptr(z1), _ptr(z2), _ptr(out), _ptr(workspace),
-                                           workspace.numel(), _stream(dev)), "nngp_precision_sqrt_t_apply")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, False, z1=(z1, "n"), z2=(z2, "s?"),
+                    out=(out, "s?"))
+    return _latent_sqrt_t_apply(c, "nngp_precision_sqrt_t_apply", "nngp_precision_workspace_bytes", z1, z2, out,
+                                workspace)
 
 
 def latent_cg(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
@@ -1349,37 +1403,10 @@ def latent_cg(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torc
     """Jacobi-preconditioned CG for A x = b in place on ``x`` (its start; nngp_latent_cg).  Returns
     ``(x, info)``, info = [iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2] as host floats.
     Synchronises the stream once per ``check_every`` iterations."""
-    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, b, x, d)
-    lib = load()
-    need = lib.nngp_latent_cg_workspace_bytes(n)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    info = (ctypes.c_double * 4)()
-    _check(lib.nngp_latent_cg(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m, float(sigma2),
-                              _ptr(d), _ptr(b), _ptr(x), float(rtol), int(max_iter), int(check_every), info,
-                              _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_latent_cg")
-    return x, [float(v) for v in info]
-
-
-def _latent_batch(nbr, B, off, rev_j, rev_k, prep, first, others=(), d=None):
-    """Checks of the batched calls: ``first`` float64 (n, nrhs) with 1 <= nrhs <= LATENT_MAX_RHS, ``others``
-    (None allowed) of its shape, ``d`` (n,) or None; returns (device, n, m, nrhs)."""
-    if first.dim() != 2 or first.dtype != torch.float64:
-        raise ValueError(f"batched vectors must be float64 (n, nrhs), got {first.dtype} {tuple(first.shape)}")
-    n, nrhs = first.shape
-    if not 1 <= nrhs <= LATENT_MAX_RHS:
-        raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
-    for t in others:
-        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != (n, nrhs)):
-            raise ValueError(f"batched vectors must be float64 ({n}, {nrhs}), got {t.dtype} {tuple(t.shape)}")
-    for t in (first,) + tuple(others):
-        if t is not None and not t.is_contiguous():
-            raise ValueError("the operator's arguments must be contiguous")
-    if nbr.dim() == 2 and nbr.shape[0] != n:
-        raise ValueError(f"batched vectors must have one row per location ({nbr.shape[0]}), got {n}")
-    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, d)
-    _require_gpu(nbr, first, *others)
-    return dev, n, m, nrhs
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, False, b=(b, "s"), x=(x, "s"))
+    x, info = _latent_cg(c, "nngp_latent_cg", "nngp_latent_cg_workspace_bytes", b, x, rtol, max_iter, check_every,
+                         workspace)
+    return x, [float(v) for v in info[0]]
 
 
 def precision_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
@@ -1388,16 +1415,8 @@ def precision_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor,
                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = A x for ``x`` (n, nrhs), 1 <= nrhs <= LATENT_MAX_RHS (nngp_precision_apply_batch): every index and
     coefficient is read once for all columns.  Column c is bit-identical to :func:`precision_apply` on it."""
-    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, x, (out,), d)
-    lib = load()
-    out = torch.empty_like(x) if out is None else out
-    need = lib.nngp_precision_batch_workspace_bytes(n, nrhs)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    _check(lib.nngp_precision_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
-                                          float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(out), _ptr(workspace),
-                                          workspace.numel(), _stream(dev)), "nngp_precision_apply_batch")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, x=(x, "s"), out=(out, "s?"))
+    return _latent_apply(c, "nngp_precision_apply_batch", "nngp_precision_batch_workspace_bytes", x, out, workspace)
 
 
 def precision_sqrt_t_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor,
@@ -1407,19 +1426,9 @@ def precision_sqrt_t_apply_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.
                                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = (I - B)^T (sigma2 F)^-1/2 z1 + sqrt(d) z2 for ``z1`` / ``z2`` (n, nrhs)
     (nngp_precision_sqrt_t_apply_batch); column c is bit-identical to :func:`precision_sqrt_t_apply` on it."""
-    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, z1, (z2, out), d)
-    if d is not None and z2 is None:
-        raise ValueError("z2 is needed when d is given")
-    lib = load()
-    out = torch.empty_like(z1) if out is None else out
-    need = lib.nngp_precision_batch_workspace_bytes(n, nrhs)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    _check(lib.nngp_precision_sqrt_t_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep),
-                                                 n, m, float(sigma2), _ptr(d), nrhs, _ptr(z1), _ptr(z2), _ptr(out),
-                                                 _ptr(workspace), workspace.numel(), _stream(dev)),
-           "nngp_precision_sqrt_t_apply_batch")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, z1=(z1, "n"), z2=(z2, "s?"), out=(out, "s?"))
+    return _latent_sqrt_t_apply(c, "nngp_precision_sqrt_t_apply_batch", "nngp_precision_batch_workspace_bytes", z1,
+                                z2, out, workspace)
 
 
 def latent_cg_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j: torch.Tensor, rev_k: torch.Tensor,
@@ -1429,23 +1438,15 @@ def latent_cg_batch(nbr: torch.Tensor, B: torch.Tensor, off: torch.Tensor, rev_j
     """nrhs Jacobi-PCG solves in lock step, in place on ``x`` (n, nrhs) (its start; nngp_latent_cg_batch).
     Returns ``(x, info)``, info a numpy (nrhs, 4) array whose row c is :func:`latent_cg`'s info of column c;
     column c of ``x`` is bit-identical to that single solve.  Synchronises once per ``check_every`` iterations."""
-    dev, n, m, nrhs = _latent_batch(nbr, B, off, rev_j, rev_k, prep, b, (x,), d)
-    lib = load()
-    need = lib.nngp_latent_cg_batch_workspace_bytes(n, nrhs)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    info = np.zeros((nrhs, 4), dtype=np.float64)
-    _check(lib.nngp_latent_cg_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, m,
-                                    float(sigma2), _ptr(d), nrhs, _ptr(b), _ptr(x), float(rtol), int(max_iter),
-                                    int(check_every), info.ctypes.data_as(ctypes.c_void_p), _ptr(workspace),
-                                    workspace.numel(), _stream(dev)), "nngp_latent_cg_batch")
-    return x, info
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), None, sigma2, d, b=(b, "s"), x=(x, "s"))
+    return _latent_cg(c, "nngp_latent_cg_batch", "nngp_latent_cg_batch_workspace_bytes", b, x, rtol, max_iter,
+                      check_every, workspace)
 
 
 def precision_diag(prep: torch.Tensor, n: int, m: int, sigma2: float, d: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """diag(A) = d + (invF + P) / sigma2 from the ``prep`` buffer (nngp_precision_diag): the expression whose
-    reciprocal preconditions the CG."""
+    reciprocal preconditions the CG.  (No DAG is passed, so its few checks are its own.)"""
     n, m = int(n), int(m)
     if n < 0 or not 1 <= m <= MAX_M:
         raise ValueError(f"need n >= 0 and 1 <= m <= {MAX_M}, got n={n}, m={m}")
@@ -1462,56 +1463,15 @@ def precision_diag(prep: torch.Tensor, n: int, m: int, sigma2: float, d: Optiona
     return out
 
 
-# ---- a reference set with the leaves integrated out (include/nngp.h: "Latent-field posterior on a reference set")
-def _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, **vectors):
-    """Checks of the reference-set calls.  ``vectors``: name -> (tensor or None, rows), rows one of "s" (n_s),
-    "n" (all nodes) or "l" (the leaves); the first one given fixes nrhs.  Returns (device, n, n_s, m, nrhs)."""
-    if nbr.dtype != torch.int32 or nbr.dim() != 2:
-        raise ValueError(f"nbr must be int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
-    n, n_s = nbr.shape[0], int(n_s)
-    if not 0 <= n_s <= n:
-        raise ValueError(f"need 0 <= n_s <= n = {n}, got n_s={n_s}")
-    rows = {"s": n_s, "n": n, "l": n - n_s}
-    nrhs = None
-    for name, (t, kind) in vectors.items():
-        if t is None:
-            continue
-        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != rows[kind] or not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous float64 ({rows[kind]}, nrhs), got {t.dtype} {tuple(t.shape)}")
-        if nrhs is None:
-            nrhs = t.shape[1]
-            if not 1 <= nrhs <= LATENT_MAX_RHS:
-                raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
-        elif t.shape[1] != nrhs:
-            raise ValueError(f"{name} must have nrhs={nrhs} columns, got {t.shape[1]}")
-    dev, n, m = _latent_geometry(nbr, B, off, rev_j, rev_k, prep, d)
-    _require_gpu(nbr, *[t for t, _ in vectors.values()])
-    return dev, n, n_s, m, nrhs
-
-
-def _ref_ws(lib, dev, n, n_s, nrhs, workspace, cg=False):
-    need = (lib.nngp_latent_ref_cg_batch_workspace_bytes if cg else lib.nngp_precision_ref_batch_workspace_bytes)(
-        n, n_s, nrhs)
-    if workspace is None or workspace.numel() < need:
-        workspace = _workspace(need, dev)
-    return workspace
-
-
 def precision_ref_apply_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, x: torch.Tensor,
                               d: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = A_S x for ``x`` (n_s, nrhs) on the n-node DAG whose first ``n_s`` nodes are the reference set
     (nngp_precision_ref_apply_batch): A_S = (I - B_S)^T f_S (I - B_S) + d_S + B_L^T g B_L, the leaves integrated
     out.  ``d`` (n,) or None.  With n_s = n it equals :func:`precision_apply_batch` bit for bit."""
-    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, x=(x, "s"), out=(out, "s"))
-    lib = load()
-    out = torch.empty_like(x) if out is None else out
-    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
-    _check(lib.nngp_precision_ref_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
-                                              n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(out),
-                                              _ptr(workspace), workspace.numel(), _stream(dev)),
-           "nngp_precision_ref_apply_batch")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, x=(x, "s"), out=(out, "s?"))
+    return _latent_apply(c, "nngp_precision_ref_apply_batch", "nngp_precision_ref_batch_workspace_bytes", x, out,
+                         workspace)
 
 
 def precision_ref_sqrt_t_apply_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, z1: torch.Tensor,
@@ -1520,18 +1480,9 @@ def precision_ref_sqrt_t_apply_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, 
                                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (n_s, nrhs) = (I - B_S)^T f_S^1/2 z1_S + B_L^T g^1/2 z1_L + d_S^1/2 z2 for ``z1`` (n, nrhs) and ``z2``
     (n_s, nrhs) (nngp_precision_ref_sqrt_t_apply_batch): Cov(out) = A_S for standard normals."""
-    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, z1=(z1, "n"), z2=(z2, "s"),
-                                       out=(out, "s"))
-    if d is not None and z2 is None:
-        raise ValueError("z2 is needed when d is given")
-    lib = load()
-    out = torch.empty((n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
-    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
-    _check(lib.nngp_precision_ref_sqrt_t_apply_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k),
-                                                     _ptr(prep), n, n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(z1),
-                                                     _ptr(z2), _ptr(out), _ptr(workspace), workspace.numel(),
-                                                     _stream(dev)), "nngp_precision_ref_sqrt_t_apply_batch")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, z1=(z1, "n"), z2=(z2, "s?"), out=(out, "s?"))
+    return _latent_sqrt_t_apply(c, "nngp_precision_ref_sqrt_t_apply_batch",
+                                "nngp_precision_ref_batch_workspace_bytes", z1, z2, out, workspace)
 
 
 def precision_ref_fold_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, v: torch.Tensor,
@@ -1539,31 +1490,18 @@ def precision_ref_fold_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: 
                              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (n_s, nrhs) = d_S v_S + B_L^T (g v_L) for ``v`` (n, nrhs) on all nodes (nngp_precision_ref_fold_batch):
     the right-hand side b_S of the mean when v is the centred response."""
-    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, v=(v, "n"), out=(out, "s"))
-    lib = load()
-    out = torch.empty((n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
-    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace)
-    _check(lib.nngp_precision_ref_fold_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
-                                             n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(v), _ptr(out),
-                                             _ptr(workspace), workspace.numel(), _stream(dev)),
-           "nngp_precision_ref_fold_batch")
-    return out
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, v=(v, "n"), out=(out, "s?"))
+    return _latent_apply(c, "nngp_precision_ref_fold_batch", "nngp_precision_ref_batch_workspace_bytes", v, out,
+                         workspace)
 
 
 def precision_ref_diag(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, d: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """diag(A_S) (n_s,) (nngp_precision_ref_diag): d_i + f_i + sum over children of B^2 s, the expression whose
     reciprocal preconditions :func:`latent_ref_cg_batch`."""
-    if out is not None and (out.dtype != torch.float64 or tuple(out.shape) != (int(n_s),) or not out.is_contiguous()):
-        raise ValueError(f"out must be contiguous float64 ({int(n_s)},)")
-    dev, n, n_s, m, _ = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d)
-    _require_gpu(nbr, out)
-    lib = load()
-    out = torch.empty(n_s, dtype=torch.float64, device=dev) if out is None else out
-    workspace = _ref_ws(lib, dev, n, n_s, 1, workspace)
-    _check(lib.nngp_precision_ref_diag(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, n_s, m,
-                                       float(sigma2), _ptr(d), _ptr(out), _ptr(workspace), workspace.numel(),
-                                       _stream(dev)), "nngp_precision_ref_diag")
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, False, out=(out, "s?"))
+    out = c.empty("s") if out is None else out
+    c("nngp_precision_ref_diag", (out,), "nngp_precision_ref_batch_workspace_bytes", workspace)
     return out
 
 
@@ -1572,17 +1510,9 @@ def latent_ref_cg_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float
                         check_every: int = 8, workspace: Optional[torch.Tensor] = None):
     """nrhs Jacobi-PCG solves of A_S x = b in lock step, in place on ``x`` (n_s, nrhs) (nngp_latent_ref_cg_batch);
     ``(x, info)`` as :func:`latent_cg_batch`."""
-    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, b=(b, "s"), x=(x, "s"))
-    if b is None or x is None:
-        raise ValueError("b and x are needed")
-    lib = load()
-    workspace = _ref_ws(lib, dev, n, n_s, nrhs, workspace, cg=True)
-    info = np.zeros((nrhs, 4), dtype=np.float64)
-    _check(lib.nngp_latent_ref_cg_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n, n_s,
-                                        m, float(sigma2), _ptr(d), nrhs, _ptr(b), _ptr(x), float(rtol), int(max_iter),
-                                        int(check_every), info.ctypes.data_as(ctypes.c_void_p), _ptr(workspace),
-                                        workspace.numel(), _stream(dev)), "nngp_latent_ref_cg_batch")
-    return x, info
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, b=(b, "s"), x=(x, "s"))
+    return _latent_cg(c, "nngp_latent_ref_cg_batch", "nngp_latent_ref_cg_batch_workspace_bytes", b, x, rtol,
+                      max_iter, check_every, workspace)
 
 
 def latent_ref_leaves_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, x: torch.Tensor,
@@ -1591,13 +1521,8 @@ def latent_ref_leaves_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: f
     """The leaves given ``x`` (n_s, nrhs) on the reference set (nngp_latent_ref_leaves_batch): out (n - n_s, nrhs) =
     (f a + d v) / (f + d) [+ z / sqrt(f + d)], a = B_L x; ``v``, ``z`` (n - n_s, nrhs) or None.  ``d`` None: out =
     a [+ z / sqrt(f)], kriging of the nrhs fields to unobserved leaves."""
-    dev, n, n_s, m, nrhs = _latent_ref(nbr, B, off, rev_j, rev_k, prep, n_s, d, x=(x, "s"), v=(v, "l"), z=(z, "l"),
-                                       out=(out, "l"))
-    if x is None:
-        raise ValueError("x is needed")
-    lib = load()
-    out = torch.empty((n - n_s, nrhs), dtype=torch.float64, device=dev) if out is None else out
-    _check(lib.nngp_latent_ref_leaves_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep), n,
-                                            n_s, m, float(sigma2), _ptr(d), nrhs, _ptr(x), _ptr(v), _ptr(z),
-                                            _ptr(out), _stream(dev)), "nngp_latent_ref_leaves_batch")
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, x=(x, "s"), v=(v, "l?"), z=(z, "l?"),
+                    out=(out, "l?"))
+    out = c.empty("l") if out is None else out
+    c("nngp_latent_ref_leaves_batch", (x, v, z, out))
     return out

@@ -810,62 +810,136 @@ int nngp_gibbs_pg_stats(int64_t n, const double* r, const double* Ft, const doub
 }
 
 // ---------------------------------------------------------------- latent-field posterior (latent.hip)
-// the checks the three calls share, before any launch; fills g
-static int latent_common(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                         const void* prep, int64_t n, int32_t m, double sigma2, const double* d, void* workspace,
-                         size_t workspace_bytes, size_t need, nngp::LatentGeom* g) {
-    if (nbr == nullptr || B == nullptr || off == nullptr || rev_j == nullptr || prep == nullptr ||
-        workspace == nullptr)
-        return fail(NNGP_EINVAL, "nbr, B, off, rev_j, prep and workspace must be non-null");
-    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
-    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
-    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
-    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
-        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
-    if (((uintptr_t)workspace & 255) != 0 || ((uintptr_t)prep & 255) != 0)
-        return fail(NNGP_EINVAL, "workspace and prep must be 256-byte aligned");
-    if (workspace_bytes < need)
-        return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    *g = nngp::LatentGeom{nbr, B, off, rev_j, nngp::latent_prep_view(prep, n, m), n, m, sigma2, d};
-    return NNGP_OK;
-}
-
-// Each operation is written once, for vectors (n, nrhs); the single-vector entry points are its nrhs = 1.
-// `what` names the public call in the launch-failure message.
+// Each operation is written once, in its reference-set, multi-vector form: an n-node DAG whose first n_s nodes
+// carry the field, vectors (rows, nrhs).  An S = T entry point is that call with n_s = n, a single-vector one with
+// nrhs = 1.
 static bool bad_nrhs(int32_t nrhs) { return nrhs < 1 || nrhs > NNGP_LATENT_MAX_RHS; }
 static int fail_nrhs(int32_t nrhs) {
     return fail(NNGP_EINVAL, "nrhs=%d outside [1, %d]", nrhs, NNGP_LATENT_MAX_RHS);
+}
+static bool bad_ref(int64_t n, int64_t n_s, int32_t nrhs) { return n < 0 || n_s < 0 || n_s > n || bad_nrhs(nrhs); }
+static int fail_n_s(int64_t n, int64_t n_s) {
+    return fail(NNGP_EINVAL, "need 0 <= n_s <= n (got n_s=%lld, n=%lld)", (long long)n_s, (long long)n);
 }
 
 size_t nngp_precision_batch_workspace_bytes(int64_t n, int32_t nrhs) {
     return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_apply_workspace_bytes(n, nrhs);
 }
-
 size_t nngp_precision_workspace_bytes(int64_t n) { return nngp_precision_batch_workspace_bytes(n, 1); }
+size_t nngp_latent_cg_batch_workspace_bytes(int64_t n, int32_t nrhs) {
+    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_cg_workspace_bytes(n, nrhs);
+}
+size_t nngp_latent_cg_workspace_bytes(int64_t n) { return nngp_latent_cg_batch_workspace_bytes(n, 1); }
+size_t nngp_precision_ref_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
+    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_apply_workspace_bytes(n, n_s, nrhs);
+}
+size_t nngp_latent_ref_cg_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
+    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_cg_workspace_bytes(n, n_s, nrhs);
+}
 
-static int precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                           const void* prep, int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs,
-                           const double* x, double* out, void* workspace, size_t workspace_bytes, void* stream,
-                           const char* what) {
-    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
-    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_apply_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, what);
+// what every latent call passes besides its own vectors (rev_k is unused by all of them: prep holds B in
+// reverse-list order already)
+struct LatentArgs {
+    const int32_t* nbr;
+    const double* B;
+    const int32_t* off;
+    const int32_t* rev_j;
+    const void* prep;
+    int64_t n, n_s;
+    int32_t m;
+    double sigma2;
+    const double* d;
+    int32_t nrhs;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    bool st;           // an S = T entry point: n_s is n by construction, the workspace to bring the S = T one
+    const char* what;  // names the public call in the launch-failure message
+};
+
+static int latent_sizes(int64_t n, int32_t m, double sigma2) {
+    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
+        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
     return NNGP_OK;
 }
 
-// rev_k is unused by the latent calls: prep holds B in reverse-list order already
+static nngp::LatentGeom latent_geom(const LatentArgs& a) {
+    return nngp::LatentGeom{a.nbr, a.B, a.off, a.rev_j, nngp::latent_prep_view(a.prep, a.n, a.m), a.n, a.m,
+                            a.sigma2, a.d, a.n_s, nullptr};
+}
+
+// the checks of the calls with a workspace, after those of their own vectors and before any launch; fills g.
+// cg: the solver's workspace, not the operator's
+static int latent_common(const LatentArgs& a, bool cg, nngp::LatentGeom* g) {
+    if (bad_nrhs(a.nrhs)) return fail_nrhs(a.nrhs);
+    if (!a.st && (a.n < 0 || a.n_s < 0 || a.n_s > a.n)) return fail_n_s(a.n, a.n_s);
+    if (a.nbr == nullptr || a.B == nullptr || a.off == nullptr || a.rev_j == nullptr || a.prep == nullptr ||
+        a.workspace == nullptr)
+        return fail(NNGP_EINVAL, "nbr, B, off, rev_j, prep and workspace must be non-null");
+    const int rc = latent_sizes(a.n, a.m, a.sigma2);
+    if (rc != NNGP_OK) return rc;
+    if (((uintptr_t)a.workspace & 255) != 0 || ((uintptr_t)a.prep & 255) != 0)
+        return fail(NNGP_EINVAL, "workspace and prep must be 256-byte aligned");
+    const size_t need = a.st ? (cg ? nngp_latent_cg_batch_workspace_bytes(a.n, a.nrhs)
+                                   : nngp_precision_batch_workspace_bytes(a.n, a.nrhs))
+                             : (cg ? nngp_latent_ref_cg_batch_workspace_bytes(a.n, a.n_s, a.nrhs)
+                                   : nngp_precision_ref_batch_workspace_bytes(a.n, a.n_s, a.nrhs));
+    if (a.workspace_bytes < need)
+        return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", a.workspace_bytes, need);
+    *g = latent_geom(a);
+    return NNGP_OK;
+}
+
+static int latent_launched(hipError_t e, const LatentArgs& a) {
+    return e != hipSuccess ? hip_fail(e, a.what) : NNGP_OK;
+}
+
+static int precision_apply(const LatentArgs& a, const double* x, double* out) {
+    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
+    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_common(a, false, &g);
+    if (rc != NNGP_OK) return rc;
+    return latent_launched(nngp::latent_apply_launch(g, a.nrhs, x, out, a.workspace, (hipStream_t)a.stream), a);
+}
+
+static int precision_sqrt_t_apply(const LatentArgs& a, const double* z1, const double* z2, double* out) {
+    if (z1 == nullptr || out == nullptr || (a.d != nullptr && z2 == nullptr))
+        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
+    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
+    nngp::LatentGeom g;
+    const int rc = latent_common(a, false, &g);
+    if (rc != NNGP_OK) return rc;
+    return latent_launched(
+        nngp::latent_sqrt_t_apply_launch(g, a.nrhs, z1, z2, out, a.workspace, (hipStream_t)a.stream), a);
+}
+
+static int latent_cg(const LatentArgs& a, const double* b, double* x, double rtol, int64_t max_iter,
+                     int32_t check_every, double* info_host) {
+    if (b == nullptr || x == nullptr || info_host == nullptr)
+        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
+    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
+    if (a.st && bad_nrhs(a.nrhs)) return fail_nrhs(a.nrhs);  // the S = T calls name a bad nrhs before a bad rtol
+    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
+    if (max_iter < 0 || check_every < 1)
+        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
+                    check_every);
+    nngp::LatentGeom g;
+    const int rc = latent_common(a, true, &g);
+    if (rc != NNGP_OK) return rc;
+    return latent_launched(nngp::latent_cg_run(g, a.nrhs, b, x, rtol, max_iter, check_every, info_host, a.workspace,
+                                               (hipStream_t)a.stream), a);
+}
+
 int nngp_precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
                          const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
                          const double* x, double* out, void* workspace, size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    return precision_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, x, out, workspace, workspace_bytes, stream,
-                           "precision_apply launch");
+    return precision_apply({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, 1, workspace, workspace_bytes, stream, true,
+                            "precision_apply launch"}, x, out);
 }
 
 int nngp_precision_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -873,129 +947,8 @@ int nngp_precision_apply_batch(const int32_t* nbr, const double* B, const int32_
                                const double* d, int32_t nrhs, const double* x, double* out, void* workspace,
                                size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    return precision_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, x, out, workspace, workspace_bytes,
-                           stream, "precision_apply_batch launch");
-}
-
-static int precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                                  const void* prep, int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs,
-                                  const double* z1, const double* z2, double* out, void* workspace,
-                                  size_t workspace_bytes, void* stream, const char* what) {
-    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
-        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
-    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_precision_batch_workspace_bytes(n, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, what);
-    return NNGP_OK;
-}
-
-int nngp_precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                                const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
-                                const double* d, const double* z1, const double* z2, double* out, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    return precision_sqrt_t_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, z1, z2, out, workspace,
-                                  workspace_bytes, stream, "precision_sqrt_t_apply launch");
-}
-
-int nngp_precision_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                                      const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
-                                      const double* d, int32_t nrhs, const double* z1, const double* z2, double* out,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    return precision_sqrt_t_apply(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, z1, z2, out, workspace,
-                                  workspace_bytes, stream, "precision_sqrt_t_apply_batch launch");
-}
-
-size_t nngp_latent_cg_batch_workspace_bytes(int64_t n, int32_t nrhs) {
-    return n < 0 || bad_nrhs(nrhs) ? 0 : nngp::latent_cg_workspace_bytes(n, nrhs);
-}
-
-size_t nngp_latent_cg_workspace_bytes(int64_t n) { return nngp_latent_cg_batch_workspace_bytes(n, 1); }
-
-static int latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j, const void* prep,
-                     int64_t n, int32_t m, double sigma2, const double* d, int32_t nrhs, const double* b, double* x,
-                     double rtol, int64_t max_iter, int32_t check_every, double* info_host, void* workspace,
-                     size_t workspace_bytes, void* stream, const char* what) {
-    if (b == nullptr || x == nullptr || info_host == nullptr)
-        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
-    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
-    if (max_iter < 0 || check_every < 1)
-        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
-                    check_every);
-    nngp::LatentGeom g;
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes,
-                                 nngp_latent_cg_batch_workspace_bytes(n, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
-                                       (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, what);
-    return NNGP_OK;
-}
-
-int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                   const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
-                   const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every, double* info_host,
-                   void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    return latent_cg(nbr, B, off, rev_j, prep, n, m, sigma2, d, 1, b, x, rtol, max_iter, check_every, info_host,
-                     workspace, workspace_bytes, stream, "latent_cg");
-}
-
-int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
-                         int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every,
-                         double* info_host, void* workspace, size_t workspace_bytes, void* stream) {
-    (void)rev_k;
-    return latent_cg(nbr, B, off, rev_j, prep, n, m, sigma2, d, nrhs, b, x, rtol, max_iter, check_every, info_host,
-                     workspace, workspace_bytes, stream, "latent_cg_batch");
-}
-
-int nngp_precision_diag(const void* prep, int64_t n, int32_t m, double sigma2, const double* d, double* out,
-                        void* stream) {
-    if (prep == nullptr || out == nullptr) return fail(NNGP_EINVAL, "prep and out must be non-null");
-    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
-    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
-    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
-    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
-        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
-    if (((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
-    hipError_t e = nngp::latent_diag_launch(nngp::latent_prep_view(prep, n, m), n, sigma2, d, out,
-                                            (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_diag launch");
-    return NNGP_OK;
-}
-
-// ---- a reference set with the leaves integrated out: latent_common's checks plus 0 <= n_s <= n
-static int latent_ref_common(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                             const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2, const double* d,
-                             int32_t nrhs, void* workspace, size_t workspace_bytes, size_t need,
-                             nngp::LatentGeom* g) {
-    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    if (n < 0 || n_s < 0 || n_s > n)
-        return fail(NNGP_EINVAL, "need 0 <= n_s <= n (got n_s=%lld, n=%lld)", (long long)n_s, (long long)n);
-    const int rc = latent_common(nbr, B, off, rev_j, prep, n, m, sigma2, d, workspace, workspace_bytes, need, g);
-    if (rc != NNGP_OK) return rc;
-    g->n_s = n_s;
-    g->s = nullptr;
-    return NNGP_OK;
-}
-
-static bool bad_ref(int64_t n, int64_t n_s, int32_t nrhs) { return n < 0 || n_s < 0 || n_s > n || bad_nrhs(nrhs); }
-
-size_t nngp_precision_ref_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
-    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_apply_workspace_bytes(n, n_s, nrhs);
-}
-
-size_t nngp_latent_ref_cg_batch_workspace_bytes(int64_t n, int64_t n_s, int32_t nrhs) {
-    return bad_ref(n, n_s, nrhs) ? 0 : nngp::latent_ref_cg_workspace_bytes(n, n_s, nrhs);
+    return precision_apply({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, nrhs, workspace, workspace_bytes, stream,
+                            true, "precision_apply_batch launch"}, x, out);
 }
 
 int nngp_precision_ref_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -1003,15 +956,26 @@ int nngp_precision_ref_apply_batch(const int32_t* nbr, const double* B, const in
                                    double sigma2, const double* d, int32_t nrhs, const double* x, double* out,
                                    void* workspace, size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    if (x == nullptr || out == nullptr) return fail(NNGP_EINVAL, "x and out must be non-null");
-    if (x == out) return fail(NNGP_EINVAL, "x and out must not alias");
-    nngp::LatentGeom g;
-    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
-                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_ref_apply_launch(g, nrhs, x, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_ref_apply_batch launch");
-    return NNGP_OK;
+    return precision_apply({nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes, stream,
+                            false, "precision_ref_apply_batch launch"}, x, out);
+}
+
+int nngp_precision_sqrt_t_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                                const double* d, const double* z1, const double* z2, double* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return precision_sqrt_t_apply({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, 1, workspace, workspace_bytes, stream,
+                                   true, "precision_sqrt_t_apply launch"}, z1, z2, out);
+}
+
+int nngp_precision_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                      const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2,
+                                      const double* d, int32_t nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return precision_sqrt_t_apply({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                   stream, true, "precision_sqrt_t_apply_batch launch"}, z1, z2, out);
 }
 
 int nngp_precision_ref_sqrt_t_apply_batch(const int32_t* nbr, const double* B, const int32_t* off,
@@ -1020,16 +984,36 @@ int nngp_precision_ref_sqrt_t_apply_batch(const int32_t* nbr, const double* B, c
                                           const double* z1, const double* z2, double* out, void* workspace,
                                           size_t workspace_bytes, void* stream) {
     (void)rev_k;
-    if (z1 == nullptr || out == nullptr || (d != nullptr && z2 == nullptr))
-        return fail(NNGP_EINVAL, "z1 and out must be non-null (and z2 when d is given)");
-    if (z1 == out || z2 == out) return fail(NNGP_EINVAL, "z1 / z2 and out must not alias");
-    nngp::LatentGeom g;
-    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
-                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
-    if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_ref_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_ref_sqrt_t_apply_batch launch");
-    return NNGP_OK;
+    return precision_sqrt_t_apply({nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
+                                   stream, false, "precision_ref_sqrt_t_apply_batch launch"}, z1, z2, out);
+}
+
+int nngp_latent_cg(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                   const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                   const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every, double* info_host,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return latent_cg({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, 1, workspace, workspace_bytes, stream, true,
+                      "latent_cg"}, b, x, rtol, max_iter, check_every, info_host);
+}
+
+int nngp_latent_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                         const int32_t* rev_k, const void* prep, int64_t n, int32_t m, double sigma2, const double* d,
+                         int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter, int32_t check_every,
+                         double* info_host, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)rev_k;
+    return latent_cg({nbr, B, off, rev_j, prep, n, n, m, sigma2, d, nrhs, workspace, workspace_bytes, stream, true,
+                      "latent_cg_batch"}, b, x, rtol, max_iter, check_every, info_host);
+}
+
+int nngp_latent_ref_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                             const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
+                             const double* d, int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                             int32_t check_every, double* info_host, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    (void)rev_k;
+    return latent_cg({nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes, stream, false,
+                      "latent_ref_cg_batch"}, b, x, rtol, max_iter, check_every, info_host);
 }
 
 int nngp_precision_ref_fold_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -1039,13 +1023,12 @@ int nngp_precision_ref_fold_batch(const int32_t* nbr, const double* B, const int
     (void)rev_k;
     if (v == nullptr || out == nullptr) return fail(NNGP_EINVAL, "v and out must be non-null");
     if (v == out) return fail(NNGP_EINVAL, "v and out must not alias");
+    const LatentArgs a{nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes, stream,
+                       false, "precision_ref_fold_batch launch"};
     nngp::LatentGeom g;
-    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
-                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, nrhs), &g);
+    const int rc = latent_common(a, false, &g);
     if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_ref_fold_launch(g, nrhs, v, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_ref_fold_batch launch");
-    return NNGP_OK;
+    return latent_launched(nngp::latent_fold_launch(g, nrhs, v, out, workspace, (hipStream_t)stream), a);
 }
 
 int nngp_precision_ref_diag(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -1053,61 +1036,44 @@ int nngp_precision_ref_diag(const int32_t* nbr, const double* B, const int32_t* 
                             const double* d, double* out, void* workspace, size_t workspace_bytes, void* stream) {
     (void)rev_k;
     if (out == nullptr) return fail(NNGP_EINVAL, "out must be non-null");
+    const LatentArgs a{nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, 1, workspace, workspace_bytes, stream, false,
+                       "precision_ref_diag launch"};
     nngp::LatentGeom g;
-    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, 1, workspace, workspace_bytes,
-                                     nngp_precision_ref_batch_workspace_bytes(n, n_s, 1), &g);
+    const int rc = latent_common(a, false, &g);
     if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_ref_diag_launch(g, out, workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "precision_ref_diag launch");
-    return NNGP_OK;
+    return latent_launched(nngp::latent_diag_launch(g, out, workspace, (hipStream_t)stream), a);
 }
 
-int nngp_latent_ref_cg_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
-                             const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m, double sigma2,
-                             const double* d, int32_t nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                             int32_t check_every, double* info_host, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-    (void)rev_k;
-    if (b == nullptr || x == nullptr || info_host == nullptr)
-        return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
-    if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
-    if (!(rtol > 0.0 && rtol < 1.0)) return fail(NNGP_EINVAL, "rtol must be in (0, 1) (got %g)", rtol);
-    if (max_iter < 0 || check_every < 1)
-        return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
-                    check_every);
-    nngp::LatentGeom g;
-    const int rc = latent_ref_common(nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes,
-                                     nngp_latent_ref_cg_batch_workspace_bytes(n, n_s, nrhs), &g);
+// The two calls without a workspace keep their own pointer rules around the shared size checks.  With no leaf
+// (n_s = n) the diagonal needs none: it is read off prep.
+int nngp_precision_diag(const void* prep, int64_t n, int32_t m, double sigma2, const double* d, double* out,
+                        void* stream) {
+    if (prep == nullptr || out == nullptr) return fail(NNGP_EINVAL, "prep and out must be non-null");
+    const int rc = latent_sizes(n, m, sigma2);
     if (rc != NNGP_OK) return rc;
-    hipError_t e = nngp::latent_ref_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "latent_ref_cg_batch");
-    return NNGP_OK;
+    if (((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
+    const LatentArgs a{nullptr, nullptr, nullptr, nullptr, prep, n, n, m, sigma2, d, 1, nullptr, 0, stream, true,
+                       "precision_diag launch"};
+    return latent_launched(nngp::latent_diag_launch(latent_geom(a), out, nullptr, (hipStream_t)stream), a);
 }
 
 int nngp_latent_ref_leaves_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
                                  const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m,
                                  double sigma2, const double* d, int32_t nrhs, const double* x, const double* v,
                                  const double* z, double* out, void* stream) {
-    (void)off;
-    (void)rev_j;
     (void)rev_k;
     if (nbr == nullptr || B == nullptr || prep == nullptr) return fail(NNGP_EINVAL, "nbr, B and prep must be non-null");
     if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
-    if (n < 0 || n_s < 0 || n_s > n)
-        return fail(NNGP_EINVAL, "need 0 <= n_s <= n (got n_s=%lld, n=%lld)", (long long)n_s, (long long)n);
-    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
-    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
-    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
-        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
+    if (n < 0 || n_s < 0 || n_s > n) return fail_n_s(n, n_s);
+    const int rc = latent_sizes(n, m, sigma2);
+    if (rc != NNGP_OK) return rc;
     if (((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
     if (n > n_s && (out == nullptr || (n_s > 0 && x == nullptr)))
         return fail(NNGP_EINVAL, "x and out must be non-null");
     if (out != nullptr && (out == x || out == v || out == z)) return fail(NNGP_EINVAL, "out must not alias an input");
-    nngp::LatentGeom g{nbr, B, off, rev_j, nngp::latent_prep_view(prep, n, m), n, m, sigma2, d, n_s, nullptr};
-    hipError_t e = nngp::latent_ref_leaves_launch(g, nrhs, x, v, z, out, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "latent_ref_leaves_batch launch");
-    return NNGP_OK;
+    const LatentArgs a{nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, nullptr, 0, stream, false,
+                       "latent_ref_leaves_batch launch"};
+    return latent_launched(nngp::latent_leaves_launch(latent_geom(a), nrhs, x, v, z, out, (hipStream_t)stream), a);
 }
 
 size_t nngp_row_order_workspace_bytes(int64_t n_rows) { return nngp::row_order_workspace_bytes(n_rows); }

@@ -36,6 +36,10 @@
 // column kernels take the row scale from the vector s, give a leaf row no self term (its x is implicitly 0) and
 // run the column phase over the first n_s nodes only, whose reverse lists hold both kinds of children.  The
 // S = T instantiations (REF = false) are the text they were.
+//
+// The host side has one launch per operation, in the reference-set form (latent.h).  S = T is the system without
+// leaves, n_s = n: each launch then leaves g.s null, which selects the REF = false instantiations and the plain
+// workspace layout, so nothing is computed or read for leaves that do not exist.
 #include "latent.h"
 
 #include <math.h>
@@ -799,6 +803,23 @@ void cg_info_clear(int nrhs, double* info_host) {
 
 size_t max_size(size_t a, size_t b) { return a > b ? a : b; }
 
+// t and s of an operator workspace; s is computed and g made a reference-set geometry
+double* ref_begin(LatentGeom* g, int nrhs, void* workspace, hipStream_t s) {
+    char* w = (char*)workspace;
+    double* sv = (double*)(w + align256((size_t)g->n * nrhs * 8));
+    ref_s_launch(*g, sv, s);
+    g->s = sv;
+    return (double*)w;
+}
+
+// Without a leaf (g.n_s == g.n) g.s stays null: the REF = false instantiations serve the call on prep's own
+// scale, and the workspace is t alone.  These are the launches, and the bits, S = T always had.
+bool leafless(const LatentGeom& g) { return g.n_s == g.n; }
+
+double* op_begin(LatentGeom* g, int nrhs, void* workspace, hipStream_t s) {
+    return leafless(*g) ? (double*)workspace : ref_begin(g, nrhs, workspace, s);
+}
+
 }  // namespace
 
 size_t latent_apply_workspace_bytes(int64_t n, int nrhs) { return align256((size_t)(n > 0 ? n : 1) * nrhs * 8); }
@@ -807,43 +828,7 @@ size_t latent_cg_workspace_bytes(int64_t n, int nrhs) {
     return 6 * align256((size_t)n * nrhs * 8) + kCgTailBytes;
 }
 
-hipError_t latent_apply_launch(const LatentGeom& g, int nrhs, const double* x, double* out, void* workspace,
-                               hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* t = (double*)workspace;
-    row_launch(g, nrhs, x, t, nullptr, s);
-    col_launch<kColApply>(g, nrhs, t, x, out, nullptr, nullptr, s);
-    return hipGetLastError();
-}
-
-hipError_t latent_sqrt_t_apply_launch(const LatentGeom& g, int nrhs, const double* z1, const double* z2, double* out,
-                                      void* workspace, hipStream_t s) {
-    if (g.n == 0) return hipSuccess;
-    double* u = (double*)workspace;
-    hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n, nrhs,
-                       1.0 / g.sigma2);
-    col_launch<kColSqrt>(g, nrhs, u, z2, out, nullptr, nullptr, s);
-    return hipGetLastError();
-}
-
-hipError_t latent_diag_launch(const LatentPrep& prep, int64_t n, double sigma2, const double* d, double* out,
-                              hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(latent_diag_kernel, dim3(vec_blocks(n)), dim3(kBlock), 0, s, n, d, prep.invF, prep.P,
-                       1.0 / sigma2, out);
-    return hipGetLastError();
-}
-
-hipError_t latent_cg_run(const LatentGeom& g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s) {
-    cg_info_clear(nrhs, info_host);
-    if (g.n == 0) return hipSuccess;
-    return cg_iterate(g, cg_layout(workspace, g.n, nrhs), nrhs, b, x, rtol, max_iter, check_every, info_host, s);
-}
-
-// ---------------------------------------------------------------- reference-set systems
-// g.n_s == g.n: there is no leaf and the S = T launches serve the call, so the bits are theirs.  Otherwise the
-// workspace starts with t (n, nrhs) and s (n,) (the CG's: ref_cg_layout).
+// with leaves the workspace starts with t (n, nrhs) and s (n,) (the CG's: ref_cg_layout)
 size_t latent_ref_apply_workspace_bytes(int64_t n, int64_t n_s, int nrhs) {
     const size_t w = align256((size_t)(n > 0 ? n : 1) * nrhs * 8) + align256((size_t)(n > 0 ? n : 1) * 8);
     return n_s == n ? max_size(w, latent_apply_workspace_bytes(n, nrhs)) : w;
@@ -854,40 +839,29 @@ size_t latent_ref_cg_workspace_bytes(int64_t n, int64_t n_s, int nrhs) {
     return n_s == n ? max_size(w, latent_cg_workspace_bytes(n, nrhs)) : w;
 }
 
-namespace {
-// t and s of an operator workspace; s is computed and g made a reference-set geometry
-double* ref_begin(LatentGeom* g, int nrhs, void* workspace, hipStream_t s) {
-    char* w = (char*)workspace;
-    double* sv = (double*)(w + align256((size_t)g->n * nrhs * 8));
-    ref_s_launch(*g, sv, s);
-    g->s = sv;
-    return (double*)w;
-}
-}  // namespace
-
-hipError_t latent_ref_apply_launch(LatentGeom g, int nrhs, const double* x, double* out, void* workspace,
-                                   hipStream_t s) {
-    if (g.n_s == g.n) return latent_apply_launch(g, nrhs, x, out, workspace, s);
+hipError_t latent_apply_launch(LatentGeom g, int nrhs, const double* x, double* out, void* workspace, hipStream_t s) {
     if (g.n_s == 0) return hipSuccess;
-    double* t = ref_begin(&g, nrhs, workspace, s);
+    double* t = op_begin(&g, nrhs, workspace, s);
     row_launch(g, nrhs, x, t, nullptr, s);
     col_launch<kColApply>(g, nrhs, t, x, out, nullptr, nullptr, s);
     return hipGetLastError();
 }
 
-hipError_t latent_ref_sqrt_t_apply_launch(LatentGeom g, int nrhs, const double* z1, const double* z2, double* out,
-                                          void* workspace, hipStream_t s) {
-    if (g.n_s == g.n) return latent_sqrt_t_apply_launch(g, nrhs, z1, z2, out, workspace, s);
+hipError_t latent_sqrt_t_apply_launch(LatentGeom g, int nrhs, const double* z1, const double* z2, double* out,
+                                      void* workspace, hipStream_t s) {
     if (g.n_s == 0) return hipSuccess;
-    double* u = ref_begin(&g, nrhs, workspace, s);
-    hipLaunchKernelGGL(latent_ref_scale_kernel<false>, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.s, z1, u, g.n,
-                       g.n_s, nrhs);
+    double* u = op_begin(&g, nrhs, workspace, s);
+    if (leafless(g))
+        hipLaunchKernelGGL(latent_scale_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.prep.invF, z1, u, g.n,
+                           nrhs, 1.0 / g.sigma2);
+    else
+        hipLaunchKernelGGL(latent_ref_scale_kernel<false>, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.s, z1, u, g.n,
+                           g.n_s, nrhs);
     col_launch<kColSqrt>(g, nrhs, u, z2, out, nullptr, nullptr, s);
     return hipGetLastError();
 }
 
-hipError_t latent_ref_fold_launch(LatentGeom g, int nrhs, const double* v, double* out, void* workspace,
-                                  hipStream_t s) {
+hipError_t latent_fold_launch(LatentGeom g, int nrhs, const double* v, double* out, void* workspace, hipStream_t s) {
     if (g.n_s == 0) return hipSuccess;
     double* u = ref_begin(&g, nrhs, workspace, s);
     hipLaunchKernelGGL(latent_ref_scale_kernel<true>, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.s, v, u, g.n,
@@ -896,19 +870,24 @@ hipError_t latent_ref_fold_launch(LatentGeom g, int nrhs, const double* v, doubl
     return hipGetLastError();
 }
 
-hipError_t latent_ref_diag_launch(LatentGeom g, double* out, void* workspace, hipStream_t s) {
-    if (g.n_s == g.n) return latent_diag_launch(g.prep, g.n, g.sigma2, g.d, out, s);
+hipError_t latent_diag_launch(LatentGeom g, double* out, void* workspace, hipStream_t s) {
     if (g.n_s == 0) return hipSuccess;
-    ref_begin(&g, 1, workspace, s);
-    ref_diag_launch(g, out, s);
+    if (leafless(g)) {
+        hipLaunchKernelGGL(latent_diag_kernel, dim3(vec_blocks(g.n)), dim3(kBlock), 0, s, g.n, g.d, g.prep.invF,
+                           g.prep.P, 1.0 / g.sigma2, out);
+    } else {
+        ref_begin(&g, 1, workspace, s);
+        ref_diag_launch(g, out, s);
+    }
     return hipGetLastError();
 }
 
-hipError_t latent_ref_cg_run(LatentGeom g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                             int check_every, double* info_host, void* workspace, hipStream_t s) {
-    if (g.n_s == g.n) return latent_cg_run(g, nrhs, b, x, rtol, max_iter, check_every, info_host, workspace, s);
+hipError_t latent_cg_run(LatentGeom g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
+                         int check_every, double* info_host, void* workspace, hipStream_t s) {
     cg_info_clear(nrhs, info_host);
     if (g.n_s == 0) return hipSuccess;
+    if (leafless(g))
+        return cg_iterate(g, cg_layout(workspace, g.n, nrhs), nrhs, b, x, rtol, max_iter, check_every, info_host, s);
     const CgLayout L = ref_cg_layout(workspace, g.n, g.n_s, nrhs);
     ref_s_launch(g, L.s, s);
     g.s = L.s;
@@ -916,8 +895,8 @@ hipError_t latent_ref_cg_run(LatentGeom g, int nrhs, const double* b, double* x,
     return cg_iterate(g, L, nrhs, b, x, rtol, max_iter, check_every, info_host, s);
 }
 
-hipError_t latent_ref_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,
-                                    double* out, hipStream_t s) {
+hipError_t latent_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,
+                                double* out, hipStream_t s) {
     const int64_t n_l = g.n - g.n_s;
     if (n_l == 0) return hipSuccess;
     const double inv_s2 = 1.0 / g.sigma2;

@@ -90,8 +90,6 @@ class LatentPosterior:
     estimate here, so they change nothing.  ``nbr`` is for S = T only.
     """
 
-    _ref = False  # S = T unless __init__ builds a reference set
-
     def __init__(self, coords, y, cov, m: int = 15, X=None, eps=None, device=None, nbr=None, ref=None, X_ref=None):
         cov = _check_cov(cov)
         self.m = int(m)
@@ -158,35 +156,48 @@ class LatentPosterior:
         self.device = dev = _default_device(device)
         self.n, self.p = n, X_host.shape[1]
         to = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731
-        if s_host is not None:
-            self._init_ref(to, c_host, s_host, y_host, observed, h_host, X_host)
-            self.update(cov)
-            return
-        self.n_nodes = self.n_s = n
-        coords0 = to(c_host)
-        nbr0 = _lib.knn_prior(coords0, self.m) if nbr is None else nbr.to(dev)
-        # Z-order storage: slot s holds location perm[s]; neighbour sets relabelled into storage labels
-        self.perm = _lib.row_order(coords0)[0].long()
+        self._ref = s_host is not None  # the caller gave ref=: nothing below the constructor depends on it
+        if self._ref:
+            coords0, nbr0, n_s, node_of_t = self._ref_nodes(to(c_host), to(s_host))
+        else:  # S = T: the reference set is the data locations, and there is no leaf
+            coords0, n_s, node_of_t = to(c_host), n, np.arange(n)
+            nbr0 = _lib.knn_prior(coords0, self.m) if nbr is None else nbr.to(dev)
+        # Z-order storage: slot s holds node perm[s], the reference nodes in the first n_s slots and the leaves
+        # behind them; neighbour sets relabelled into storage labels
+        n_nodes = coords0.shape[0]
+        self.n_nodes, self.n_s = n_nodes, n_s
+        self.node_of_t = node_of_t.astype(np.int64)  # node (reference points, then leaves) of each data row
+        parts = [_lib.row_order(coords0[:n_s])[0].long()]
+        if n_nodes > n_s:
+            parts.append(_lib.row_order(coords0[n_s:])[0].long() + n_s)
+        self.perm = torch.cat(parts)
         self.pos = torch.empty_like(self.perm)
-        self.pos[self.perm] = torch.arange(n, device=dev)
+        self.pos[self.perm] = torch.arange(n_nodes, device=dev)
+        self.perm_s = self.perm[:n_s].contiguous()  # reference point held by storage slot s < n_s
+        self.slot_of_ref = self.pos[:n_s].contiguous()
+        self.slot_of_t = self.pos[torch.from_numpy(self.node_of_t).to(dev)]
         self.coords = coords0[self.perm].contiguous()
         nb = nbr0[self.perm].long()
         self.nbr = torch.where(nb >= 0, self.pos[nb.clamp(min=0)], -1).to(torch.int32).contiguous()
         self.off, self.rev_j, self.rev_k = _lib.reverse_neighbors(self.nbr)
-        self.h = to(h_host)[self.perm].contiguous()
-        self.y = to(np.where(observed, y_host, 0.0))[self.perm].contiguous()
-        self.X = to(X_host)[self.perm].contiguous()
-        self.B = torch.empty((n, self.m), dtype=torch.float64, device=dev)
-        self.F = torch.empty(n, dtype=torch.float64, device=dev)
+        # a node's data: that of the data row it carries; none (h = 0) on a node without an observation
+        h_n, y_n, X_n = np.zeros(n_nodes), np.zeros(n_nodes), np.zeros((n_nodes, self.p))
+        h_n[node_of_t[observed]] = h_host[observed]
+        y_n[node_of_t[observed]] = y_host[observed]
+        X_n[node_of_t] = X_host
+        self.h = to(h_n)[self.perm].contiguous()
+        self.y = to(y_n)[self.perm].contiguous()
+        self.X = to(X_n)[self.perm].contiguous()
+        self.B = torch.empty((n_nodes, self.m), dtype=torch.float64, device=dev)
+        self.F = torch.empty(n_nodes, dtype=torch.float64, device=dev)
         self._prep = None
         self._ws_batch = None  # the operator's and solver's workspace, made on first use for the widest chunk so far
         self.update(cov)
 
-    def _init_ref(self, to, c_host, s_host, y_host, observed, h_host, X_host):
-        """The node DAG of a reference set, as ``SeqNNGP`` builds it (gibbs.py), in the storage order [S in
-        Z-order; leaves in Z-order]."""
-        dev, n_t, n_s = self.device, c_host.shape[0], s_host.shape[0]
-        t_dev, s_dev = to(c_host), to(s_host)
+    def _ref_nodes(self, t_dev, s_dev):
+        """The node DAG of a reference set, as ``SeqNNGP`` builds it (gibbs.py): ``(coords, nbr, n_s, node_of_t)``
+        over the nodes [S; the data locations outside S]."""
+        dev, n_s = self.device, s_dev.shape[0]
         nbr_s = _lib.knn_prior(s_dev, self.m)
         if n_s > 1:  # a repeated reference point makes C_N singular
             j1 = nbr_s[1:, 0].long()
@@ -211,37 +222,7 @@ class LatentPosterior:
         if k < self.m:
             nbr_t = torch.cat([nbr_t, torch.full((nbr_t.shape[0], self.m - k), -1, dtype=torch.int32, device=dev)],
                               dim=1)
-        nbr0 = torch.cat([nbr_s, nbr_t]).contiguous()
-        coords0 = torch.cat([s_dev, t_out]).contiguous()
-        n = coords0.shape[0]
-        self._ref = True
-        self.n_nodes, self.n_s = n, n_s
-        self.node_of_t = node_of_t.astype(np.int64)  # model node (reference points, then leaves) of each data row
-        h_n, y_n, X_n = np.zeros(n), np.zeros(n), np.zeros((n, self.p))
-        h_n[node_of_t[observed]] = h_host[observed]
-        y_n[node_of_t[observed]] = y_host[observed]
-        X_n[node_of_t] = X_host
-        # storage: slot s holds model node perm[s]; reference nodes keep the first n_s slots
-        parts = [_lib.row_order(s_dev)[0].long()]
-        if n > n_s:
-            parts.append(_lib.row_order(t_out)[0].long() + n_s)
-        self.perm = torch.cat(parts)
-        self.pos = torch.empty_like(self.perm)
-        self.pos[self.perm] = torch.arange(n, device=dev)
-        self.perm_s = self.perm[:n_s].contiguous()  # reference point held by storage slot s < n_s
-        self.slot_of_ref = self.pos[:n_s].contiguous()
-        self.slot_of_t = self.pos[torch.from_numpy(self.node_of_t).to(dev)]
-        self.coords = coords0[self.perm].contiguous()
-        nb = nbr0[self.perm].long()
-        self.nbr = torch.where(nb >= 0, self.pos[nb.clamp(min=0)], -1).to(torch.int32).contiguous()
-        self.off, self.rev_j, self.rev_k = _lib.reverse_neighbors(self.nbr)
-        self.h = to(h_n)[self.perm].contiguous()
-        self.y = to(y_n)[self.perm].contiguous()
-        self.X = to(X_n)[self.perm].contiguous()
-        self.B = torch.empty((n, self.m), dtype=torch.float64, device=dev)
-        self.F = torch.empty(n, dtype=torch.float64, device=dev)
-        self._prep = None
-        self._ws_batch = None
+        return torch.cat([s_dev, t_out]).contiguous(), torch.cat([nbr_s, nbr_t]).contiguous(), n_s, node_of_t
 
     # -- theta -----------------------------------------------------------------
     def update(self, cov) -> "LatentPosterior":
@@ -257,34 +238,25 @@ class LatentPosterior:
         return self
 
     # -- vectors in / out ------------------------------------------------------
-    # the solver's vectors: one entry per data location (S = T) or per reference point, in the caller's order
-    @property
-    def _vn(self):
-        return self.n_s if self._ref else self.n
-
-    @property
-    def _vperm(self):
-        return self.perm_s if self._ref else self.perm
-
-    @property
-    def _vpos(self):
-        return self.slot_of_ref if self._ref else self.pos
-
+    # The solver's vectors have one entry per reference point (S = T: per data location), in the caller's order.
+    # Everything below is written for a reference set; S = T is the one whose nodes are the data locations, without
+    # a leaf (n_nodes == n_s), which the library serves with the S = T launches.
     def _in(self, v, what="vector"):
         t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
-        if t.dtype != torch.float64 or tuple(t.shape) != (self._vn,):
-            raise ValueError(f"{what} must be float64 ({self._vn},), got {t.dtype} {tuple(t.shape)}")
-        return t.to(self.device)[self._vperm].contiguous()
+        if t.dtype != torch.float64 or tuple(t.shape) != (self.n_s,):
+            raise ValueError(f"{what} must be float64 ({self.n_s},), got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device)[self.perm_s].contiguous()
 
     def _out(self, t, like):
-        o = t[self._vpos]
+        o = t[self.slot_of_ref]
         return o if isinstance(like, torch.Tensor) else o.cpu().numpy()
-
-    def _geom(self):
-        return (self.nbr, self.B, self.off, self.rev_j, self.rev_k, self._prep, self.cov.sigma2)
 
     def _rgeom(self):
         return (self.nbr, self.B, self.off, self.rev_j, self.rev_k, self._prep, self.n_s, self.cov.sigma2)
+
+    def _geom(self):
+        """The geometry without n_s, as the S = T library calls take it: all nodes as one S = T system."""
+        return (self.nbr, self.B, self.off, self.rev_j, self.rev_k, self._prep, self.cov.sigma2)
 
     @staticmethod
     def _check_where(where):
@@ -292,16 +264,15 @@ class LatentPosterior:
             raise ValueError(f"where must be 'data' or 'ref', got {where!r}")
 
     def _rows_of(self, where):
-        """Storage slots of the rows a field-valued result reports."""
-        if not self._ref:
-            return self.pos  # S = T: the reference set is the data locations
+        """Storage slots of the rows a field-valued result reports (S = T: the same rows either way)."""
         return self.slot_of_t if where == "data" else self.slot_of_ref
 
+    def _has_leaves(self):
+        return self.n_nodes > self.n_s
+
     def _apply_cols(self, X):
-        """A X (S = T) or A_S X for storage-order columns."""
-        if self._ref:
-            return _lib.precision_ref_apply_batch(*self._rgeom(), X, d=self.d, workspace=self._batch_ws(X.shape[1]))
-        return _lib.precision_apply_batch(*self._geom(), X, d=self.d, workspace=self._batch_ws(X.shape[1]))
+        """A_S X for storage-order columns."""
+        return _lib.precision_ref_apply_batch(*self._rgeom(), X, d=self.d, workspace=self._batch_ws(X.shape[1]))
 
     def _leaf_cols(self, XS, V=None, Z=None):
         """The leaves given the storage-order columns XS on S: conditional means (+ noise for normals Z)."""
@@ -309,38 +280,32 @@ class LatentPosterior:
 
     def _node_cols(self, XS, V=None, Z=None):
         """(n_nodes, k) columns over all storage slots from the columns on S."""
-        return torch.cat([XS, self._leaf_cols(XS, V, Z)]) if self._ref and self.n_nodes > self.n_s else XS
+        return torch.cat([XS, self._leaf_cols(XS, V, Z)]) if self._has_leaves() else XS
 
     def _yres(self, beta):
         return self.y if self.p == 0 else self.y - self.X @ torch.as_tensor(beta, dtype=torch.float64,
                                                                            device=self.device)
 
     def _leaf_v(self, beta, k):
-        """The centred response on the leaves as k equal columns (the leaves kernel's v)."""
-        return self._yres(beta)[self.n_s:, None].expand(-1, k).contiguous()
+        """The centred response on the leaves as k equal columns (the leaves kernel's v); None without leaves."""
+        return self._yres(beta)[self.n_s:, None].expand(-1, k).contiguous() if self._has_leaves() else None
 
     # -- the operator and the solver -------------------------------------------
     def matvec(self, x):
         """A x (two gathers, bit-reproducible); with a reference set A_S x, x in the order of ``ref``."""
-        if self._ref:
-            return self._out(self._apply_cols(self._in(x, "x")[:, None].contiguous())[:, 0], x)
-        return self._out(_lib.precision_apply(*self._geom(), self._in(x, "x"), d=self.d, workspace=self._batch_ws(1)),
-                         x)
+        return self._out(self._apply_cols(self._in(x, "x")[:, None])[:, 0], x)
+
+    def _cg_args(self, rtol, max_iter):
+        """The iteration cap of a solve, after the check of its rtol."""
+        if not 0.0 < rtol < 1.0:
+            raise ValueError(f"rtol must be in (0, 1), got {rtol}")
+        return min(max(2 * self.n_s, 1000), 20000) if max_iter is None else max_iter
 
     def _solve(self, rhs, rtol, max_iter, x0=None):
         """Storage-order solve: (x, SolveInfo); raises on a breakdown, warns on non-convergence."""
-        if not 0.0 < rtol < 1.0:
-            raise ValueError(f"rtol must be in (0, 1), got {rtol}")
-        if max_iter is None:
-            max_iter = min(max(2 * self._vn, 1000), 20000)
-        if self._ref:
-            X, info = self._solve_cols(rhs[:, None].contiguous(), rtol, max_iter,
-                                       None if x0 is None else x0[:, None].contiguous())
-            x, info = X[:, 0].contiguous(), [float(v) for v in info[0]]
-        else:
-            x = torch.zeros_like(rhs) if x0 is None else x0.clone()
-            _, info = _lib.latent_cg(*self._geom(), rhs, x, d=self.d, rtol=rtol, max_iter=int(max_iter),
-                                     check_every=CHECK_EVERY, workspace=self._batch_ws(1))
+        X, info = self._solve_cols(rhs[:, None], rtol, self._cg_args(rtol, max_iter),
+                                   None if x0 is None else x0[:, None])
+        x, info = X[:, 0], [float(v) for v in info[0]]
         if info[1] < 0:
             raise NNGPNumericalError(f"CG breakdown after {int(info[0])} iterations: p.Ap is not positive and finite "
                                      "(NaN or inf in the factors or the right-hand side?)")
@@ -367,29 +332,23 @@ class LatentPosterior:
         return b
 
     def _batch_ws(self, nrhs):
-        if self._ref:
-            need = _lib.load().nngp_latent_ref_cg_batch_workspace_bytes(self.n_nodes, self.n_s, nrhs)
-        else:
-            need = _lib.load().nngp_latent_cg_batch_workspace_bytes(self.n, nrhs)
+        need = _lib.load().nngp_latent_ref_cg_batch_workspace_bytes(self.n_nodes, self.n_s, nrhs)
         if self._ws_batch is None or self._ws_batch.numel() < need:
             self._ws_batch = _lib._workspace(need, self.device)
         return self._ws_batch
 
     def _in_rows(self, v, what="rhs"):
-        """(K, N) rows in the order of ``coords`` -> (K, N) device rows in storage order."""
+        """(K, n_S) rows in the caller's order -> (K, n_S) device rows in storage order."""
         t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
-        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != self._vn:
-            raise ValueError(f"{what} must be float64 (K, {self._vn}), got {t.dtype} {tuple(t.shape)}")
-        return t.to(self.device)[:, self._vperm]
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != self.n_s:
+            raise ValueError(f"{what} must be float64 (K, {self.n_s}), got {t.dtype} {tuple(t.shape)}")
+        return t.to(self.device)[:, self.perm_s]
 
     def _solve_cols(self, R, rtol, max_iter, X0=None):
         """One batched solve of the storage-order columns R (n, k <= LATENT_MAX_RHS): (X, info (k, 4))."""
         X = torch.zeros_like(R) if X0 is None else X0.clone()
-        if self._ref:
-            return _lib.latent_ref_cg_batch(*self._rgeom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
-                                            check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
-        return _lib.latent_cg_batch(*self._geom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
-                                    check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
+        return _lib.latent_ref_cg_batch(*self._rgeom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
+                                        check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
 
     def _report(self, info, rtol, first=0):
         """[SolveInfo] of the (K, 4) info rows (of the right-hand sides first, first + 1, ...); raises on a
@@ -409,12 +368,9 @@ class LatentPosterior:
     def _solve_rows(self, rows, rtol, max_iter, batch, x0=None):
         """Storage-order rows (K, n) on the device -> (solutions (K, n), info (K, 4)), ``batch`` columns per
         solve; the transposes stay on the device."""
-        if not 0.0 < rtol < 1.0:
-            raise ValueError(f"rtol must be in (0, 1), got {rtol}")
-        if max_iter is None:
-            max_iter = min(max(2 * self._vn, 1000), 20000)
+        max_iter = self._cg_args(rtol, max_iter)
         K = rows.shape[0]
-        out = torch.empty((K, self._vn), dtype=torch.float64, device=self.device)
+        out = torch.empty((K, self.n_s), dtype=torch.float64, device=self.device)
         info = np.zeros((K, 4))
         for k0 in range(0, K, batch):
             k1 = min(K, k0 + batch)
@@ -436,42 +392,36 @@ class LatentPosterior:
             raise ValueError(f"x0 must have the shape of rhs {tuple(rows.shape)}, got {tuple(starts.shape)}")
         x, info = self._solve_rows(rows, rtol, max_iter, batch, starts)
         infos = self._report(info, rtol)
-        x = x[:, self._vpos]
+        x = x[:, self.slot_of_ref]
         return (x if isinstance(rhs, torch.Tensor) else x.cpu().numpy()), infos
 
     # -- posterior mean --------------------------------------------------------
     def _rhs(self, beta):
-        yres = self.y if self.p == 0 else self.y - self.X @ torch.as_tensor(beta, dtype=torch.float64,
-                                                                           device=self.device)
-        if self._ref:  # b_S = d_S v_S + B_L^T (g v_L)
-            return self._fold_cols(yres[:, None].contiguous())[:, 0].contiguous()
-        return (self.d * yres).contiguous()
+        return self._fold_cols(self._yres(beta)[:, None])[:, 0]
 
     def _fold_cols(self, V):
-        return _lib.precision_ref_fold_batch(*self._rgeom(), V, d=self.d, workspace=self._batch_ws(V.shape[1]))
+        """d_S V_S + B_L^T (g V_L) for storage-order columns V on all nodes: the right-hand sides on S.  Without
+        leaves it is the product d V (the fold kernel's values, with the product's sign of a zero where d = 0, and
+        two launches fewer)."""
+        if not self._has_leaves():
+            return (self.d[:, None] * V).contiguous()
+        return _lib.precision_ref_fold_batch(*self._rgeom(), V.contiguous(), d=self.d,
+                                             workspace=self._batch_ws(V.shape[1]))
 
     def gls_beta(self, rtol: float = 1e-8, max_iter: Optional[int] = None, batch=None) -> np.ndarray:
         """GLS beta under V = C~ + tau2 H^-1 (C~ the NNGP covariance): V^-1 v = H v / tau2 - H A^-1 H v / tau4,
         one solve per column of X, ``batch`` columns per batched solve; rows with h = 0 drop out."""
         if self.p == 0:
             return np.zeros(0)
-        if self._ref:
-            # A_aug^-1 (D v) = [x_S; leaf mean(x_S, v)] with x_S = A_S^-1 fold(v), per column v of X
-            batch = self._batch(batch)
-            if not 0.0 < rtol < 1.0:
-                raise ValueError(f"rtol must be in (0, 1), got {rtol}")
-            mi = min(max(2 * self.n_s, 1000), 20000) if max_iter is None else max_iter
-            S = torch.empty_like(self.X)
-            for k0 in range(0, self.p, batch):
-                V = self.X[:, k0:k0 + batch].contiguous()
-                XS, info = self._solve_cols(self._fold_cols(V), rtol, mi)
-                self._report(info, rtol, first=k0)
-                S[:, k0:k0 + batch] = self._node_cols(XS, V[self.n_s:].contiguous())
-        else:
-            rows = (self.d[:, None] * self.X).t()
-            S, info = self._solve_rows(rows, rtol, max_iter, self._batch(batch))
-            self._report(info, rtol)
-            S = S.t().contiguous()
+        # A_aug^-1 (D v) = [x_S; leaf mean(x_S, v)] with x_S = A_S^-1 fold(v), per column v of X
+        batch = self._batch(batch)
+        max_iter = self._cg_args(rtol, max_iter)
+        S = torch.empty_like(self.X)
+        for k0 in range(0, self.p, batch):
+            V = self.X[:, k0:k0 + batch].contiguous()
+            XS, info = self._solve_cols(self._fold_cols(V), rtol, max_iter)
+            self._report(info, rtol, first=k0)
+            S[:, k0:k0 + batch] = self._node_cols(XS, V[self.n_s:].contiguous())
         W = self.d[:, None] * (self.X - S)  # V^-1 X
         G = (self.X.t() @ W).cpu().numpy()
         g = (W.t() @ self.y).cpu().numpy()
@@ -489,8 +439,7 @@ class LatentPosterior:
         if beta.shape != (self.p,):
             raise ValueError(f"beta must hold {self.p} coefficients")
         w, _ = self._solve(self._rhs(beta), rtol, max_iter)
-        if self._ref:
-            w = self._node_cols(w[:, None].contiguous(), self._leaf_v(beta, 1))[:, 0]
+        w = self._node_cols(w[:, None], self._leaf_v(beta, 1))[:, 0]
         return w[self._rows_of(where)].cpu().numpy(), beta
 
     # -- exact draws -----------------------------------------------------------
@@ -499,30 +448,6 @@ class LatentPosterior:
             beta = self._beta_hat if self._beta_hat is not None else self.gls_beta(rtol, max_iter)
             self._beta_hat = beta
         return np.asarray(beta, dtype=np.float64).reshape(-1)
-
-    def _draw_chunks(self, n_draws, seed, z, b, rtol, max_iter, batch):
-        """Yields ``(k0, W)``: the draws k0 .. k0 + W.shape[1] - 1 as storage-order columns (n, k <= batch) on the
-        device.  Draw k takes the Philox streams of sweep indices 2k and 2k + 1, whatever the chunking."""
-        if self._ref:
-            yield from self._draw_chunks_ref(n_draws, seed, z, b, rtol, max_iter, batch)
-            return
-        if z is not None:
-            z1, z2 = (np.asarray(a, dtype=np.float64).reshape(n_draws, self.n) for a in z[:2])
-        zz = torch.empty(self.n, dtype=torch.float64, device=self.device)
-        for k0 in range(0, n_draws, batch):
-            kc = min(batch, n_draws - k0)
-            Z1 = torch.empty((self.n, kc), dtype=torch.float64, device=self.device)
-            Z2 = torch.empty_like(Z1)
-            for c in range(kc):
-                if z is None:
-                    Z1[:, c] = _lib.gibbs_normals(zz, seed, 2 * (k0 + c))
-                    Z2[:, c] = _lib.gibbs_normals(zz, seed, 2 * (k0 + c) + 1)
-                else:
-                    Z1[:, c], Z2[:, c] = self._in(z1[k0 + c], "z1"), self._in(z2[k0 + c], "z2")
-            eta = _lib.precision_sqrt_t_apply_batch(*self._geom(), Z1, Z2, d=self.d, workspace=self._batch_ws(kc))
-            W, info = self._solve_rows((b[:, None] + eta).t(), rtol, max_iter, kc)
-            self._report(info, rtol, first=k0)
-            yield k0, W.t().contiguous()
 
     LEAF_STREAM = 1 << 40   # sweep index of draw k's third Philox stream (the leaves' conditional noise)
     QUERY_STREAM = 1 << 41  # ... of predict's conditional noise
@@ -536,9 +461,10 @@ class LatentPosterior:
         idx = {"n": self.perm, "s": self.perm_s, "l": self.perm[self.n_s:] - self.n_s}[part]
         return t[:, idx]
 
-    def _draw_chunks_ref(self, n_draws, seed, z, b, rtol, max_iter, batch):
-        """:meth:`_draw_chunks` on a reference set: W holds draws of w_S, storage-order columns (n_s, k).  z1 has
-        one normal per node, z2 one per reference point."""
+    def _draw_chunks(self, n_draws, seed, z, b, rtol, max_iter, batch):
+        """Yields ``(k0, W)``: the draws k0 .. k0 + W.shape[1] - 1 of w_S as storage-order columns (n_s, k <= batch)
+        on the device.  Draw k takes the Philox streams of sweep indices 2k and 2k + 1, whatever the chunking; z1
+        has one normal per node, z2 one per reference point."""
         n, n_s = self.n_nodes, self.n_s
         if z is not None:
             z1, z2 = self._nodes_in(z[0], n_draws, "n"), self._nodes_in(z[1], n_draws, "s")
@@ -590,9 +516,10 @@ class LatentPosterior:
         b = self._rhs(beta)
         rows = self._rows_of(where)
         out = np.empty((n_draws, rows.shape[0]))
-        z3 = None if z is None or not self._ref else self._nodes_in(z[2], n_draws, "l")
+        leaves = where == "data" and self._has_leaves()
+        z3 = self._nodes_in(z[2], n_draws, "l") if z is not None and self._has_leaves() else None
         for k0, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
-            if self._ref and where == "data" and self.n_nodes > self.n_s:
+            if leaves:
                 kc = W.shape[1]
                 W = self._node_cols(W, self._leaf_v(beta, kc),
                                     self._leaf_normals(k0, kc, n_draws, seed, z3, self.LEAF_STREAM))
@@ -623,18 +550,16 @@ class LatentPosterior:
         self._check_where(where)
         beta = self._beta_for_draws(beta, rtol, max_iter)
         b = self._rhs(beta)
-        if self._ref:
-            aii = _lib.precision_ref_diag(*self._rgeom(), d=self.d, workspace=self._batch_ws(1))
+        base = aii = _lib.precision_ref_diag(*self._rgeom(), d=self.d, workspace=self._batch_ws(1))
+        if self._has_leaves():
             base = torch.cat([aii, self.d[self.n_s:] + 1.0 / (self.cov.sigma2 * self.F[self.n_s:])])
-        else:
-            base = aii = _lib.precision_diag(self._prep, self.n, self.m, self.cov.sigma2, d=self.d)
         shift = None
         s1 = torch.zeros(self.n_nodes, dtype=torch.float64, device=self.device)
         s2 = torch.zeros_like(s1)
         for _, W in self._draw_chunks(n_draws, seed, z, b, rtol, max_iter, batch):
             AW = self._apply_cols(W)
             C = W - (AW - b[:, None]) / aii[:, None]
-            if self._ref and self.n_nodes > self.n_s:  # a leaf's conditional mean given this draw of w_S
+            if self._has_leaves():  # a leaf's conditional mean given this draw of w_S
                 C = torch.cat([C, self._leaf_cols(W, self._leaf_v(beta, W.shape[1]))])
             if shift is None:
                 shift = C[:, 0].clone()

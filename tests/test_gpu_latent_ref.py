@@ -590,6 +590,35 @@ def test_reference_set_without_leaves(dev):
     assert mean.shape == (5,) and draws.shape == (3, 5) and np.all(var > 0)
 
 
+@pytest.mark.parametrize("n,m,dim", [(300, 7, 2), (40, 3, 1)], ids=["300-7-2d", "line-40-3"])
+def test_leafless_reference_set_is_s_equals_t_bit_for_bit(dev, n, m, dim):
+    """ref = the data locations themselves: the same nodes, neighbour sets and storage as without ref, so every
+    result of the class is the S = T one, bit for bit (the line: rows with -1 slots)."""
+    from pynngp_amd import Covariance, LatentPosterior
+
+    rng = np.random.default_rng(61)
+    t = rng.uniform(size=(n, dim)) if dim > 1 else np.linspace(0.0, 1.0, n)[:, None]
+    y = rng.standard_normal(n)
+    y[[2, n // 3, n - 5]] = np.nan
+    X = np.column_stack([np.ones(n), rng.standard_normal(n)])
+    eps = rng.uniform(0.5, 2.0, n)
+    q = rng.uniform(size=(5, dim))
+    cov = Covariance("exponential", SIGMA2, PHI, TAU2)
+    a = LatentPosterior(t, y, cov, m=m, X=X, eps=eps, device=dev)
+    b = LatentPosterior(t, y, cov, m=m, X=X, eps=eps, device=dev, ref=t)
+    assert not a._ref and b._ref
+    for lp in (a, b):
+        assert lp.n_s == lp.n_nodes == n
+    for ra, rb in zip(a.mean(), b.mean()):
+        np.testing.assert_array_equal(ra, rb)
+    np.testing.assert_array_equal(a.gls_beta(), b.gls_beta())
+    np.testing.assert_array_equal(a.sample(3, seed=5), b.sample(3, seed=5))
+    np.testing.assert_array_equal(a.sample(9, seed=5, batch=4)[:3], b.sample(9, seed=5, batch=4)[:3])
+    np.testing.assert_array_equal(a.marginal_variance(4, seed=5), b.marginal_variance(4, seed=5))
+    for ra, rb in zip(a.predict(q, n_draws=3, seed=5), b.predict(q, n_draws=3, seed=5)):
+        np.testing.assert_array_equal(ra, rb)
+
+
 def test_nngp_latent_posterior_on_a_random_reference_set(dev):
     from pynngp_amd import NNGP, Covariance
 

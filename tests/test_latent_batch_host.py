@@ -214,8 +214,9 @@ def _hollow_posterior(n=5):
 
     lp = LatentPosterior.__new__(LatentPosterior)
     lp.n, lp.p, lp.m = n, 0, 2
+    lp.n_nodes = lp.n_s = n  # S = T: every node is a reference node
     lp.device = torch.device("cpu")
-    lp.perm = lp.pos = torch.arange(n)
+    lp.perm = lp.pos = lp.perm_s = lp.slot_of_ref = torch.arange(n)
     return lp
 
 

@@ -193,6 +193,23 @@ def test_latent_posterior_refusals():
         LatentPosterior(c, np.full(20, np.nan), cov, m=4)
 
 
+@pytest.mark.gpu
+def test_s_equals_t_object_has_the_reference_set_maps(dev):
+    """S = T is the reference set without leaves: the object carries the reference-set maps like any other, and they
+    are perm / pos and the identity."""
+    from pynngp_amd import Covariance, LatentPosterior
+
+    rng = np.random.default_rng(3)
+    n = 37
+    lp = LatentPosterior(rng.uniform(size=(n, 2)), rng.standard_normal(n), Covariance("exponential", 1.0, 6.0, 0.1),
+                         m=4, device=dev)
+    assert not lp._ref and lp.n_s == lp.n_nodes == lp.n == n
+    ar = torch.arange(n, device=dev)
+    assert np.array_equal(lp.node_of_t, np.arange(n))
+    assert torch.equal(lp.pos[lp.perm], ar) and torch.equal(lp.perm.sort().values, ar)
+    assert torch.equal(lp.perm_s, lp.perm) and torch.equal(lp.slot_of_ref, lp.pos) and torch.equal(lp.slot_of_t, lp.pos)
+
+
 def test_nngp_latent_needs_s_equals_t():
     """The wrappers serve the field on the data locations only; the check comes before any device work."""
     from pynngp_amd import NNGP, Covariance
