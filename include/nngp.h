@@ -640,6 +640,19 @@ int nngp_precision_diag(const void *prep, int64_t n, int32_t m, double sigma2, c
  *   launches per iteration, per-column state, freezing, check_every and info_host (HOST, nrhs x 4).  workspace:
  *   nngp_latent_ref_cg_batch_workspace_bytes(n, n_s, nrhs) bytes: one (n, nrhs) and four (n_s, nrhs) vectors
  *   where the n-node system needs six (n, nrhs).
+ * nngp_latent_ref_cg_batch_trace: nngp_latent_ref_cg_batch that also records the solver's scalars (n_s = n: S = T;
+ *   nrhs = 1: the single call).  trace: NULL -- the call is then nngp_latent_ref_cg_batch, bit for bit -- or DEVICE
+ *   doubles (nrhs, trace_len, 2) with trace_len >= max_iter (else NNGP_EINVAL), not aliasing b or x.  After
+ *   iteration k of column c completes (the column was active and did not break down in it), trace[c][k] =
+ *   (alpha_k, beta_k), beta_k = r_k+1.z_k+1 / r_k.z_k.  Entries at k >= that column's final iteration count
+ *   (info_host row c, word 0) are never written: a frozen column writes nothing, a breakdown leaves no entry for the
+ *   breaking iteration, and the caller's fill of the array survives there.  One thread writes them, stream-ordered,
+ *   from the scalars the direction launch already holds; x, info_host and the workspace are the same bits with and
+ *   without a trace.  With M = diag(A_S) and the start x = 0 the scalars are the Lanczos tridiagonal T of A^ =
+ *   M^-1/2 A_S M^-1/2 for the start vector M^-1/2 b:
+ *     T[j,j] = 1 / alpha_j + beta_j-1 / alpha_j-1 (the second term absent at j = 0),  T[j,j+1] = sqrt(beta_j) / alpha_j,
+ *   and (M^-1/2 b)^T f(A^) (M^-1/2 b) ~ |M^-1/2 b|^2 e_1^T f(T_k) e_1 is the k-point Gauss quadrature: f = 1 / t gives
+ *   b^T x, f = log with probes b = M^1/2 z gives log det A_S = sum_i log M_ii + E_z[z^T log(A^) z].
  * nngp_latent_ref_leaves_batch: the leaves given x (n_s, nrhs) on S: out = (f a + d v) / (f + d) [+ z /
  *   sqrt(f + d)], a = B_L x summed as the row phase sums; v, z: (n - n_s, nrhs) or NULL (v NULL: 0; z NULL: the
  *   conditional mean, else a conditional draw for standard normal z).  d NULL: out = a [+ z / sqrt(f)], kriging
@@ -669,6 +682,12 @@ int nngp_latent_ref_cg_batch(const int32_t *nbr, const double *B, const int32_t 
                              const double *d, int32_t nrhs, const double *b, double *x, double rtol, int64_t max_iter,
                              int32_t check_every, double *info_host, void *workspace, size_t workspace_bytes,
                              void *stream);
+int nngp_latent_ref_cg_batch_trace(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                                   const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
+                                   double sigma2, const double *d, int32_t nrhs, const double *b, double *x,
+                                   double rtol, int64_t max_iter, int32_t check_every, double *info_host,
+                                   void *workspace, size_t workspace_bytes, double *trace, int64_t trace_len,
+                                   void *stream);
 int nngp_latent_ref_leaves_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
                                  const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
                                  double sigma2, const double *d, int32_t nrhs, const double *x, const double *v,

@@ -88,6 +88,7 @@ SYMBOLS = (
     "nngp_precision_ref_diag",
     "nngp_latent_ref_cg_batch_workspace_bytes",
     "nngp_latent_ref_cg_batch",
+    "nngp_latent_ref_cg_batch_trace",
     "nngp_latent_ref_leaves_batch",
     "nngp_polya_gamma",
     "nngp_gibbs_pg_update",
@@ -278,6 +279,9 @@ def load() -> ctypes.CDLL:
     lib.nngp_latent_ref_cg_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, D, I64, I32, P, P, SZ,
                                              P]
     lib.nngp_latent_ref_cg_batch.restype = ctypes.c_int
+    lib.nngp_latent_ref_cg_batch_trace.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, D, I64, I32, P, P,
+                                                   SZ, P, I64, P]
+    lib.nngp_latent_ref_cg_batch_trace.restype = ctypes.c_int
     lib.nngp_latent_ref_leaves_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, P, P]
     lib.nngp_latent_ref_leaves_batch.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
@@ -1337,10 +1341,11 @@ class _LatentCall:
         shape = (self.rows[kind], self.nrhs) if self.batched else (self.rows[kind],)
         return torch.empty(shape, dtype=torch.float64, device=self.dev)
 
-    def __call__(self, symbol, args, ws_symbol=None, workspace=None):
-        """``symbol``(geometry, n[, n_s], m, sigma2, d[, nrhs], *args[, workspace, its bytes], stream); tensors
-        among ``args`` go as pointers.  ``ws_symbol``: the call takes a workspace of that many bytes, made here
-        unless the caller's is large enough."""
+    def __call__(self, symbol, args, ws_symbol=None, workspace=None, trace=None):
+        """``symbol``(geometry, n[, n_s], m, sigma2, d[, nrhs], *args[, workspace, its bytes][, trace, its length],
+        stream); tensors among ``args`` go as pointers.  ``ws_symbol``: the call takes a workspace of that many
+        bytes, made here unless the caller's is large enough.  ``trace``: the call takes a trace argument -- a
+        checked (nrhs, trace_len, 2) tensor (:meth:`check_trace`), or ``()`` for the NULL trace."""
         lib = load()
         sizes = (self.n, self.n_s) if self.ref else (self.n,)
         k = (self.nrhs,) if self.batched else ()
@@ -1351,7 +1356,20 @@ class _LatentCall:
             if workspace is None or workspace.numel() < need:
                 workspace = _workspace(need, self.dev)
             argv += [_ptr(workspace), workspace.numel()]
+        if trace is not None:
+            argv += [_ptr(trace), trace.shape[1]] if isinstance(trace, torch.Tensor) else [None, 0]
         _check(getattr(lib, symbol)(*argv, _stream(self.dev)), symbol)
+
+    def check_trace(self, trace, max_iter):
+        """A CG trace: contiguous float64 (nrhs, trace_len >= max_iter, 2) on the call's device."""
+        if (not isinstance(trace, torch.Tensor) or trace.dtype != torch.float64 or trace.dim() != 3
+                or trace.shape[0] != self.nrhs or trace.shape[2] != 2 or not trace.is_contiguous()):
+            raise ValueError(f"trace must be a contiguous float64 ({self.nrhs}, trace_len, 2) tensor")
+        if trace.shape[1] < max_iter:
+            raise ValueError(f"trace_len={trace.shape[1]} is below max_iter={max_iter}")
+        if trace.device != self.dev:
+            raise ValueError(f"trace must be on {self.dev}, got {trace.device}")
+        return trace
 
 
 def _latent_apply(c, symbol, ws_symbol, x, out, workspace):
@@ -1366,10 +1384,10 @@ def _latent_sqrt_t_apply(c, symbol, ws_symbol, z1, z2, out, workspace):
     return out
 
 
-def _latent_cg(c, symbol, ws_symbol, b, x, rtol, max_iter, check_every, workspace):
+def _latent_cg(c, symbol, ws_symbol, b, x, rtol, max_iter, check_every, workspace, trace=None):
     info = np.zeros((c.nrhs, 4), dtype=np.float64)
     c(symbol, (b, x, float(rtol), int(max_iter), int(check_every), info.ctypes.data_as(ctypes.c_void_p)), ws_symbol,
-      workspace)
+      workspace, trace)
     return x, info
 
 
@@ -1513,6 +1531,21 @@ def latent_ref_cg_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float
     c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, b=(b, "s"), x=(x, "s"))
     return _latent_cg(c, "nngp_latent_ref_cg_batch", "nngp_latent_ref_cg_batch_workspace_bytes", b, x, rtol,
                       max_iter, check_every, workspace)
+
+
+def latent_ref_cg_batch_trace(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, b: torch.Tensor,
+                              x: torch.Tensor, d: Optional[torch.Tensor] = None, rtol: float = 1e-8,
+                              max_iter: int = 1000, check_every: int = 8, workspace: Optional[torch.Tensor] = None,
+                              trace: Optional[torch.Tensor] = None):
+    """:func:`latent_ref_cg_batch` that records each column's CG scalars (nngp_latent_ref_cg_batch_trace): ``trace``
+    a device float64 (nrhs, trace_len >= max_iter, 2) tensor, written in place: ``trace[c, k] = (alpha_k, beta_k)``
+    for every iteration k column c completed, nothing else (fill it with NaN to see which).  They are the Lanczos
+    tridiagonal of M^-1/2 A_S M^-1/2 (:func:`pynngp_amd.lanczos_quadrature`).  ``trace`` None: the NULL trace, the
+    same bits as :func:`latent_ref_cg_batch`.  n_s = n is S = T."""
+    c = _LatentCall((nbr, B, off, rev_j, rev_k, prep), n_s, sigma2, d, b=(b, "s"), x=(x, "s"))
+    tr = () if trace is None else c.check_trace(trace, int(max_iter))
+    return _latent_cg(c, "nngp_latent_ref_cg_batch_trace", "nngp_latent_ref_cg_batch_workspace_bytes", b, x, rtol,
+                      max_iter, check_every, workspace, tr)
 
 
 def latent_ref_leaves_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: float, x: torch.Tensor,

@@ -917,8 +917,9 @@ static int precision_sqrt_t_apply(const LatentArgs& a, const double* z1, const d
         nngp::latent_sqrt_t_apply_launch(g, a.nrhs, z1, z2, out, a.workspace, (hipStream_t)a.stream), a);
 }
 
+// trace: null, or the device (nrhs, trace_len, 2) record of each column's (alpha_k, beta_k)
 static int latent_cg(const LatentArgs& a, const double* b, double* x, double rtol, int64_t max_iter,
-                     int32_t check_every, double* info_host) {
+                     int32_t check_every, double* info_host, double* trace = nullptr, int64_t trace_len = 0) {
     if (b == nullptr || x == nullptr || info_host == nullptr)
         return fail(NNGP_EINVAL, "b, x and info_host must be non-null");
     if (b == x) return fail(NNGP_EINVAL, "b and x must not alias");
@@ -927,11 +928,15 @@ static int latent_cg(const LatentArgs& a, const double* b, double* x, double rto
     if (max_iter < 0 || check_every < 1)
         return fail(NNGP_EINVAL, "need max_iter >= 0 and check_every >= 1 (got %lld, %d)", (long long)max_iter,
                     check_every);
+    if (trace != nullptr && trace_len < max_iter)
+        return fail(NNGP_EINVAL, "trace needs trace_len >= max_iter (got %lld < %lld)", (long long)trace_len,
+                    (long long)max_iter);
+    if (trace != nullptr && (trace == b || trace == x)) return fail(NNGP_EINVAL, "trace must not alias b or x");
     nngp::LatentGeom g;
     const int rc = latent_common(a, true, &g);
     if (rc != NNGP_OK) return rc;
     return latent_launched(nngp::latent_cg_run(g, a.nrhs, b, x, rtol, max_iter, check_every, info_host, a.workspace,
-                                               (hipStream_t)a.stream), a);
+                                               (hipStream_t)a.stream, trace, trace_len), a);
 }
 
 int nngp_precision_apply(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
@@ -1014,6 +1019,17 @@ int nngp_latent_ref_cg_batch(const int32_t* nbr, const double* B, const int32_t*
     (void)rev_k;
     return latent_cg({nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes, stream, false,
                       "latent_ref_cg_batch"}, b, x, rtol, max_iter, check_every, info_host);
+}
+
+int nngp_latent_ref_cg_batch_trace(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                                   const int32_t* rev_k, const void* prep, int64_t n, int64_t n_s, int32_t m,
+                                   double sigma2, const double* d, int32_t nrhs, const double* b, double* x,
+                                   double rtol, int64_t max_iter, int32_t check_every, double* info_host,
+                                   void* workspace, size_t workspace_bytes, double* trace, int64_t trace_len,
+                                   void* stream) {
+    (void)rev_k;
+    return latent_cg({nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, workspace, workspace_bytes, stream, false,
+                      "latent_ref_cg_batch_trace"}, b, x, rtol, max_iter, check_every, info_host, trace, trace_len);
 }
 
 int nngp_precision_ref_fold_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,

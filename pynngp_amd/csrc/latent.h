@@ -61,8 +61,15 @@ hipError_t latent_diag_launch(LatentGeom g, double* out, void* workspace, hipStr
 // stopping; info_host: (nrhs, 4) rows of iterations, converged (1 / 0 / -1 breakdown), |r|^2, |b|^2.  A finished
 // column is frozen; the launches are no-ops once every column is finished.  Synchronises the stream once per
 // chunk of check_every iterations.
+// trace: null, or device (nrhs, trace_len, 2) with trace_len >= max_iter.  After iteration k of column c completes
+// (the column was active and did not break down in it) trace[c][k] = (alpha_k, beta_k), beta_k = r_k+1.z_k+1 /
+// r_k.z_k; entries at k >= the column's final iteration count are never written, a frozen column writes nothing.
+// One thread writes them from the scalars the direction launch holds; the solve is the same bits with or without.
+// They are the Lanczos tridiagonal T of M^-1/2 A M^-1/2 for the start M^-1/2 r_0: T[j,j] = 1 / alpha_j +
+// beta_j-1 / alpha_j-1 (the second term absent at j = 0), T[j,j+1] = sqrt(beta_j) / alpha_j.
 hipError_t latent_cg_run(LatentGeom g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s);
+                         int check_every, double* info_host, void* workspace, hipStream_t s, double* trace = nullptr,
+                         int64_t trace_len = 0);
 // the leaves given x on S: out = (f a + d v) / (f + d) [+ z / sqrt(f + d)], a = B_L x; v, z null or (n - n_s, nrhs);
 // g.d null: out = a [+ z / sqrt(f)]
 hipError_t latent_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,

@@ -481,12 +481,16 @@ __global__ __launch_bounds__(kBlock) void latent_cg_update_kernel(
 }
 
 // iteration k, last launch: per column beta = r.z' / r.z, p = z + beta p; block 0 moves the states on (the
-// scalars of iteration k + 1 live in the other slot, so no block reads a word this launch writes)
+// scalars of iteration k + 1 live in the other slot, so no block reads a word this launch writes).
+// trace: null, or (nrhs, trace_len, 2): the lead thread records (alpha_k, beta_k) of every column that completed
+// iteration k at trace[c][k] -- the Lanczos tridiagonal of M^-1/2 A M^-1/2 (latent.h).  A frozen column and one that
+// broke down in this iteration write nothing; nothing else of the launch depends on trace.
 template <int KP>
 __global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, int nrhs, int64_t k,
                                                                      const double* __restrict__ rec, int n_rec,
                                                                      const double* __restrict__ z,
-                                                                     double* __restrict__ p, double* __restrict__ st) {
+                                                                     double* __restrict__ p, double* __restrict__ st,
+                                                                     double* __restrict__ trace, int64_t trace_len) {
     __shared__ double sh4[4];
     nrhs = columns<KP>(nrhs);
     const int cur = (int)(k & 1), nxt = cur ^ 1;
@@ -521,6 +525,11 @@ __global__ __launch_bounds__(kBlock) void latent_cg_direction_kernel(int64_t n, 
                     sc[kBeta] = beta[c];
                     sc[kIter] = (double)(k + 1);
                     sc[kFlag0 + nxt] = sc[kStatus] = done ? 1.0 : 0.0;
+                    if (trace != nullptr && k < trace_len) {
+                        double* tr = trace + ((size_t)c * (size_t)trace_len + (size_t)k) * 2;
+                        tr[0] = sc[kAlpha];  // the update launch of this iteration left it there
+                        tr[1] = beta[c];
+                    }
                 }
             }
         }
@@ -743,7 +752,8 @@ CgLayout ref_cg_layout(void* workspace, int64_t n, int64_t n_s, int nrhs) {
 // the recurrences on a geometry whose workspace is laid out (and, for a reference-set system, whose s and
 // diag(A_S) are in place); vectors have vec_rows(g) rows
 hipError_t cg_iterate(const LatentGeom& g, const CgLayout& L, int nrhs, const double* b, double* x, double rtol,
-                      int64_t max_iter, int check_every, double* info_host, hipStream_t s) {
+                      int64_t max_iter, int check_every, double* info_host, double* trace, int64_t trace_len,
+                      hipStream_t s) {
     const int64_t nr = vec_rows(g);
     const int nv = vec_blocks(nr), nt = tile_blocks(nr, kColRows);
     const double inv_s2 = 1.0 / g.sigma2;
@@ -776,7 +786,7 @@ hipError_t cg_iterate(const LatentGeom& g, const CgLayout& L, int nrhs, const do
                                                     L.st));
             NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL(latent_cg_direction_kernel<KP>, dim3(nv), dim3(kBlock), 0, s,
                                                     nr, nrhs, k, (const double*)L.rec, nv, (const double*)L.z, L.p,
-                                                    L.st));
+                                                    L.st, trace, trace_len));
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = hipMemcpyAsync(st, L.st, sizeof st, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
@@ -883,16 +893,18 @@ hipError_t latent_diag_launch(LatentGeom g, double* out, void* workspace, hipStr
 }
 
 hipError_t latent_cg_run(LatentGeom g, int nrhs, const double* b, double* x, double rtol, int64_t max_iter,
-                         int check_every, double* info_host, void* workspace, hipStream_t s) {
+                         int check_every, double* info_host, void* workspace, hipStream_t s, double* trace,
+                         int64_t trace_len) {
     cg_info_clear(nrhs, info_host);
     if (g.n_s == 0) return hipSuccess;
     if (leafless(g))
-        return cg_iterate(g, cg_layout(workspace, g.n, nrhs), nrhs, b, x, rtol, max_iter, check_every, info_host, s);
+        return cg_iterate(g, cg_layout(workspace, g.n, nrhs), nrhs, b, x, rtol, max_iter, check_every, info_host,
+                          trace, trace_len, s);
     const CgLayout L = ref_cg_layout(workspace, g.n, g.n_s, nrhs);
     ref_s_launch(g, L.s, s);
     g.s = L.s;
     ref_diag_launch(g, L.diag, s);
-    return cg_iterate(g, L, nrhs, b, x, rtol, max_iter, check_every, info_host, s);
+    return cg_iterate(g, L, nrhs, b, x, rtol, max_iter, check_every, info_host, trace, trace_len, s);
 }
 
 hipError_t latent_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,

@@ -19,6 +19,8 @@
 #include <c10/core/DeviceGuard.h>
 #include <torch/library.h>
 
+#include <limits>
+
 #include "../../include/nngp.h"
 
 namespace {
@@ -454,6 +456,35 @@ std::tuple<at::Tensor, at::Tensor> latent_cg_batch(const at::Tensor& nbr, const 
     return {x, info};
 }
 
+// latent_cg_batch with the solver's scalars recorded (nngp_latent_ref_cg_batch_trace at n_s = n): (x, info, trace),
+// trace a device float64 (nrhs, max_iter, 2) filled with NaN, trace[c][k] = (alpha_k, beta_k) for every iteration
+// k column c completed -- the Lanczos tridiagonal of M^-1/2 A M^-1/2.  x and info are latent_cg_batch's, bit for bit
+std::tuple<at::Tensor, at::Tensor, at::Tensor> latent_cg_batch_trace(
+    const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off, const at::Tensor& rev_j,
+    const at::Tensor& rev_k, const at::Tensor& prep, double sigma2, const c10::optional<at::Tensor>& d,
+    const at::Tensor& b, const c10::optional<at::Tensor>& x0, double rtol, int64_t max_iter, int64_t check_every) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(d, {n}, nbr, "d");
+    const int64_t nrhs = check_batch(b, nbr, "b");
+    check_f64(x0, {n, nrhs}, nbr, "x0");
+    TORCH_CHECK(max_iter >= 0, "max_iter must be >= 0");
+    at::Tensor x = x0.has_value() ? x0->clone() : at::zeros_like(b);
+    auto info = at::empty({nrhs, 4}, at::TensorOptions().dtype(at::kDouble));
+    auto trace = at::full({nrhs, max_iter, 2}, std::numeric_limits<double>::quiet_NaN(), b.options());
+    auto ws = at::empty({(int64_t)nngp_latent_ref_cg_batch_workspace_bytes(n, n, (int32_t)nrhs)},
+                        nbr.options().dtype(at::kByte));
+    check_rc(nngp_latent_ref_cg_batch_trace(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                                            rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), n,
+                                            n, (int32_t)m, sigma2, ptr<double>(d), (int32_t)nrhs,
+                                            b.data_ptr<double>(), x.data_ptr<double>(), rtol, max_iter,
+                                            (int32_t)check_every, info.data_ptr<double>(), ws.data_ptr(),
+                                            (size_t)ws.nbytes(), trace.data_ptr<double>(), max_iter, stream(nbr)),
+             "nngp_latent_ref_cg_batch_trace");
+    return {x, info, trace};
+}
+
 // ---------------------------------------------------------------- Polya-Gamma draws (binomial model)
 // omega ~ PG(trials, c) per location and the status word (0 = clean, else the smallest index + 1 whose draw is
 // NaN: a non-finite c, trials outside [0, NNGP_PG_MAX_TRIALS] or a loop cap -- faults are data, the op does not
@@ -484,6 +515,9 @@ TORCH_LIBRARY(nngp, m) {
     m.def("latent_cg_batch(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
           "Tensor? d, Tensor b, Tensor? x0=None, float rtol=1e-08, int max_iter=1000, int check_every=8) -> "
           "(Tensor, Tensor)");
+    m.def("latent_cg_batch_trace(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, "
+          "float sigma2, Tensor? d, Tensor b, Tensor? x0=None, float rtol=1e-08, int max_iter=1000, "
+          "int check_every=8) -> (Tensor, Tensor, Tensor)");
     m.def("precision_apply(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
           "Tensor? d, Tensor x) -> Tensor");
     m.def("latent_cg(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
@@ -526,4 +560,5 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("latent_cg", &latent_cg);
     m.impl("precision_apply_batch", &precision_apply_batch);
     m.impl("latent_cg_batch", &latent_cg_batch);
+    m.impl("latent_cg_batch_trace", &latent_cg_batch_trace);
 }

@@ -26,6 +26,13 @@ Every CG vector has n_S entries however many data locations hang off S (``nngp_p
 ``nngp_latent_ref_cg_batch``, ``nngp_latent_ref_leaves_batch``).  A prediction point is an unobserved leaf of the
 same kind: :meth:`LatentPosterior.predict` gives the latent mean, its variance and draws at new locations for
 both S = T and S != T.
+
+How plausible theta is: :meth:`LatentPosterior.log_marginal` is log p(y | theta) of this latent model (not the
+response model of ``NNGP.loglik``), for S = T and S != T alike.  Its quadratic form is one more solve, log det Q_S a
+sum over F, and log det A_S comes from the solver itself: the Jacobi-PCG's alpha_k, beta_k are the Lanczos
+tridiagonal of M^-1/2 A_S M^-1/2 (``nngp_latent_ref_cg_batch_trace`` records them), which turns every solve into a
+Gauss quadrature (:func:`lanczos_quadrature`) and a handful of probe solves into log det A_S with a standard error
+(stochastic Lanczos quadrature, :meth:`LatentPosterior.logdet`).  :meth:`LatentPosterior.fit` maximises it.
 """
 from __future__ import annotations
 
@@ -53,6 +60,44 @@ class SolveInfo:
     converged: bool
     residual2: float
     rhs2: float
+
+
+@dataclasses.dataclass(frozen=True)
+class LogDet:
+    """log det A_S by stochastic Lanczos quadrature: ``value`` = sum log diag(A_S) + the mean of ``per_probe``, its
+    standard error ``se`` (the probes' sample standard deviation / sqrt(P); inf for one probe), the P estimates of
+    z^T log(M^-1/2 A_S M^-1/2) z and the CG iterations each probe's quadrature rests on."""
+
+    value: float
+    se: float
+    per_probe: np.ndarray
+    iterations: np.ndarray
+
+
+def lanczos_quadrature(alpha, beta, f=np.log) -> float:
+    """e_1^T f(T) e_1 for the Lanczos tridiagonal T of a Jacobi-PCG solve's scalars alpha_0 .. alpha_k-1 and beta_0 ..
+    (at least k - 1 of them; ``nngp_latent_ref_cg_batch_trace``):
+
+        T[j, j] = 1 / alpha_j + beta_j-1 / alpha_j-1 (the second term absent at j = 0),  T[j, j+1] = sqrt(beta_j) / alpha_j.
+
+    For the solve of A x = b from x = 0 with M = diag(A), |M^-1/2 b|^2 times this is the k-point Gauss quadrature of
+    (M^-1/2 b)^T f(M^-1/2 A M^-1/2) (M^-1/2 b): f = 1 / t gives b^T x, f = log the log-determinant's probe term.  Host
+    fp64 (``scipy.linalg.eigh_tridiagonal``); ``f`` maps an array of eigenvalues to an array."""
+    a = np.asarray(alpha, dtype=np.float64).reshape(-1)
+    b = np.asarray(beta, dtype=np.float64).reshape(-1)
+    k = a.size
+    if k < 1 or b.size < k - 1:
+        raise ValueError(f"need k >= 1 alphas and at least k - 1 betas, got {k} and {b.size}")
+    if not (np.all(np.isfinite(a)) and np.all(a > 0) and np.all(np.isfinite(b[:k - 1])) and np.all(b[:k - 1] >= 0)):
+        raise ValueError("alpha must be positive and beta non-negative, all finite (an unwritten trace entry?)")
+    diag = 1.0 / a
+    diag[1:] += b[:k - 1] / a[:k - 1]
+    if k == 1:
+        return float(np.asarray(f(diag))[0])
+    from scipy.linalg import eigh_tridiagonal
+
+    w, V = eigh_tridiagonal(diag, np.sqrt(b[:k - 1]) / a[:k - 1])
+    return float(np.sum(V[0] ** 2 * f(w)))
 
 
 def _check_cov(cov) -> Covariance:
@@ -344,9 +389,14 @@ class LatentPosterior:
             raise ValueError(f"{what} must be float64 (K, {self.n_s}), got {t.dtype} {tuple(t.shape)}")
         return t.to(self.device)[:, self.perm_s]
 
-    def _solve_cols(self, R, rtol, max_iter, X0=None):
-        """One batched solve of the storage-order columns R (n, k <= LATENT_MAX_RHS): (X, info (k, 4))."""
+    def _solve_cols(self, R, rtol, max_iter, X0=None, trace=None):
+        """One batched solve of the storage-order columns R (n, k <= LATENT_MAX_RHS): (X, info (k, 4)).  ``trace``:
+        a device (k, >= max_iter, 2) tensor that receives each column's (alpha, beta)."""
         X = torch.zeros_like(R) if X0 is None else X0.clone()
+        if trace is not None:
+            return _lib.latent_ref_cg_batch_trace(*self._rgeom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
+                                                  check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]),
+                                                  trace=trace)
         return _lib.latent_ref_cg_batch(*self._rgeom(), R, X, d=self.d, rtol=rtol, max_iter=int(max_iter),
                                         check_every=CHECK_EVERY, workspace=self._batch_ws(R.shape[1]))
 
@@ -452,6 +502,7 @@ class LatentPosterior:
     LEAF_STREAM = 1 << 40   # sweep index of draw k's third Philox stream (the leaves' conditional noise)
     QUERY_STREAM = 1 << 41  # ... of predict's conditional noise
     RESPONSE_STREAM = 3 << 40  # ... of predict's response noise (every stream is keyed by the draw's k alone)
+    PROBE_STREAM = 1 << 42  # ... of logdet's probe k (its signs); no draw's stream
 
     def _nodes_in(self, a, n_draws, part):
         """Given test normals (n_draws, len) in model order -> storage-order device rows; part: "n" all nodes
@@ -651,3 +702,145 @@ class LatentPosterior:
         if n_draws >= 2:
             var = (cov.sigma2 * F_q + (s2 - s1 * s1 / n_draws) / (n_draws - 1)).cpu().numpy()
         return mean, var, draws
+
+    # -- the marginal likelihood of theta ------------------------------------------
+    def _probe_rows(self, n_probes, seed, z):
+        """(P, n_S) storage-order probes on the device: the given rows ``z`` (model order), else Rademacher signs --
+        those of the Philox normals of stream ``PROBE_STREAM + k``, so probe k depends on (seed, k) alone."""
+        if z is not None:
+            return self._in_rows(z, "z").contiguous()
+        n_probes = int(n_probes)
+        if n_probes < 1:
+            raise ValueError("n_probes must be >= 1")
+        Z = torch.empty((n_probes, self.n_s), dtype=torch.float64, device=self.device)
+        zz = torch.empty(self.n_s, dtype=torch.float64, device=self.device)
+        one = torch.ones((), dtype=torch.float64, device=self.device)
+        for k in range(n_probes):
+            Z[k] = torch.where(_lib.gibbs_normals(zz, seed, self.PROBE_STREAM + k) < 0, -one, one)
+        return Z
+
+    def logdet(self, n_probes: int = 32, seed: int = 0, z=None, rtol: float = 1e-6, max_iter: Optional[int] = None,
+               batch=None) -> LogDet:
+        """log det A_S by stochastic Lanczos quadrature on the solver's own scalars (:class:`LogDet`).  With M =
+        diag(A_S) and A^ = M^-1/2 A_S M^-1/2,
+
+            log det A_S = sum_i log M_ii + E_z[z^T log(A^) z]      for probes with E z z^T = I,
+
+        and one Jacobi-PCG solve of A_S x = M^1/2 z from x = 0 yields z^T log(A^) z ~ z^T z e_1^T log(T) e_1, T the
+        Lanczos tridiagonal its alpha_k, beta_k spell (:func:`lanczos_quadrature`; the solution itself is not used).
+        The probes go through the batched solver ``batch`` at a time (default ``LATENT_MAX_RHS``) with a trace;
+        the quadrature uses the iterations a column completed, to ``rtol`` -- a Gauss quadrature's error is of the
+        order of the squared residual, hence the loose default.  Probes: Rademacher signs from the Philox stream of
+        (``seed``, probe index) alone, so the result depends neither on ``batch`` nor on the run; or the rows of
+        ``z`` (P, n_S) in the order of ``ref`` (S = T: of ``coords``), each weighted by its z^T z -- the n_S rows of
+        sqrt(n_S) I give the trace exactly.  A breakdown raises, a probe that ran out of ``max_iter`` is named in a
+        ``RuntimeWarning`` (its quadrature then rests on ``max_iter`` points)."""
+        batch = self._batch(batch)
+        max_iter = int(self._cg_args(rtol, max_iter))
+        Z = self._probe_rows(n_probes, seed, z)
+        P = Z.shape[0]
+        if P < 1:
+            raise ValueError("logdet needs at least one probe")
+        diag = _lib.precision_ref_diag(*self._rgeom(), d=self.d, workspace=self._batch_ws(1))
+        root = torch.sqrt(diag)
+        weight = (Z * Z).sum(dim=1).cpu().numpy()
+        per, info = np.zeros(P), np.zeros((P, 4))
+        trace = torch.empty((min(batch, P), max_iter, 2), dtype=torch.float64, device=self.device)
+        for k0 in range(0, P, batch):
+            k1 = min(P, k0 + batch)
+            tr = trace[:k1 - k0]
+            tr.fill_(float("nan"))
+            _, info[k0:k1] = self._solve_cols((Z[k0:k1] * root).t().contiguous(), rtol, max_iter, trace=tr)
+            self._report(info[k0:k1], rtol, first=k0)
+            its = info[k0:k1, 0].astype(np.int64)
+            host = tr[:, :max(int(its.max()), 1)].cpu().numpy()
+            for c, it in enumerate(its):
+                if it > 0:  # no iteration: a zero probe, whose term is 0
+                    per[k0 + c] = weight[k0 + c] * lanczos_quadrature(host[c, :it, 0], host[c, :it, 1])
+        se = float(per.std(ddof=1) / math.sqrt(P)) if P > 1 else math.inf
+        return LogDet(float(torch.log(diag).sum()) + float(per.mean()), se, per, info[:, 0].astype(np.int64))
+
+    def log_marginal(self, beta=None, n_probes: int = 32, seed: int = 0, z=None, rtol: float = 1e-8,
+                     max_iter: Optional[int] = None, batch=None, logdet_rtol: float = 1e-6):
+        """``(value, se)``: log p(y | theta) of the latent model y = X beta + w + e at this theta, the field on S
+        and the leaves integrated out.  With v the centred response, f = 1 / (sigma2 F), d = h / tau2 (0 where
+        unobserved), g_j = f_j d_j / (f_j + d_j) per leaf and n_obs the nodes with d > 0,
+
+            -2 log p = n_obs log 2 pi - sum_{S, d>0} log d_i - sum_{L, d>0} log g_j - sum_S log f_i + log det A_S
+                       + (sum_S d_i v_i^2 + sum_L g_j v_j^2) - b_S^T A_S^-1 b_S,
+
+        for S = T the dense log N(v; 0, Q^-1 + diag(1 / d)) on the observed rows.  The quadratic form is one solve
+        to ``rtol``; log det A_S is :meth:`logdet` (``n_probes``, ``seed``, ``z``, ``batch``, ``logdet_rtol``), whose
+        standard error, halved, is ``se`` -- everything else is exact to rounding.  With covariates and no ``beta``,
+        v = y - X beta_hat with the GLS estimate (:meth:`gls_beta`): a plug-in (profiled) likelihood, not one with
+        beta integrated out."""
+        beta = self._beta_for_draws(beta, rtol, max_iter)
+        if beta.shape != (self.p,):
+            raise ValueError(f"beta must hold {self.p} coefficients")
+        n_s = self.n_s
+        v = self._yres(beta)
+        b = self._rhs(beta)
+        x, _ = self._solve(b, rtol, max_iter)
+        d, f = self.d, 1.0 / (self.cov.sigma2 * self.F)
+        obs = d > 0
+        one = torch.ones_like(d)
+        terms = -torch.log(torch.where(obs[:n_s], d[:n_s], one[:n_s])).sum() - torch.log(f[:n_s]).sum()
+        quad = (d[:n_s] * v[:n_s] * v[:n_s]).sum() - torch.dot(b, x)
+        if self._has_leaves():
+            fl, dl, ol = f[n_s:], d[n_s:], obs[n_s:]
+            g = torch.where(ol, fl * dl / (fl + dl), torch.zeros_like(dl))
+            terms = terms - torch.log(torch.where(ol, g, one[n_s:])).sum()
+            quad = quad + (g * v[n_s:] * v[n_s:]).sum()
+        ld = self.logdet(n_probes, seed, z, logdet_rtol, max_iter, batch)
+        m2 = int(obs.sum()) * math.log(2.0 * math.pi) + float(terms) + ld.value + float(quad)
+        return -0.5 * m2, 0.5 * ld.se
+
+    def fit(self, x0=None, fix_tau2: Optional[float] = None, n_probes: int = 32, seed: int = 0,
+            method: str = "Nelder-Mead", maxiter: int = 200, z=None, rtol: float = 1e-8, batch=None):
+        """Empirical-Bayes theta: maximise :meth:`log_marginal` over log (sigma2, phi, tau2) (``fix_tau2``: over log
+        (sigma2, phi) at that nugget) from ``x0`` -- a :class:`Covariance` of this kind or (sigma2, phi, tau2),
+        default the current ``cov``.  Every evaluation uses the same probes (common random numbers), so the
+        objective is a deterministic function of theta; theta moves by :meth:`update` on the same neighbour sets,
+        and beta, with covariates, is re-estimated by GLS at each theta.  Derivative-free (``scipy.optimize.minimize``,
+        ``method``, at most ``maxiter`` iterations).  Leaves the object at the best theta seen and returns ``(cov,
+        result)``: the fitted :class:`Covariance` and the optimiser's result (``result.fun`` = -log_marginal there)."""
+        from scipy.optimize import minimize
+
+        base = self.cov
+        if isinstance(x0, Covariance):
+            th0 = x0.theta
+        else:
+            th0 = tuple(float(t) for t in x0) if x0 is not None else base.theta
+        if len(th0) != 3 or not all(t > 0 and math.isfinite(t) for t in th0[:2]):
+            raise ValueError(f"x0 must be (sigma2, phi, tau2) with positive sigma2 and phi, got {th0}")
+        free_tau = fix_tau2 is None
+        if not free_tau and not float(fix_tau2) > 0:
+            raise ValueError("fix_tau2 must be positive (tau2 = 0 leaves nothing to solve)")
+        z0 = [math.log(th0[0]), math.log(th0[1])] + ([math.log(max(th0[2], 1e-6))] if free_tau else [])
+        Z = None if z is None else np.array(z, dtype=np.float64)
+        best = {"ll": -math.inf, "cov": None}
+
+        def obj(lz):
+            try:
+                cov = base.replace(sigma2=math.exp(lz[0]), phi=math.exp(lz[1]),
+                                   tau2=math.exp(lz[2]) if free_tau else float(fix_tau2))
+                self.update(cov)
+                ll, _ = self.log_marginal(n_probes=n_probes, seed=seed, z=Z, rtol=rtol, batch=batch)
+            except (NNGPNumericalError, OverflowError):
+                return 1e300
+            if not math.isfinite(ll):
+                return 1e300
+            if ll > best["ll"]:
+                best.update(ll=ll, cov=cov)
+            return -ll
+
+        opts = {"maxiter": int(maxiter)}
+        if method == "Nelder-Mead":
+            opts.update(xatol=1e-4, fatol=1e-6)
+        res = minimize(obj, np.array(z0), method=method, options=opts)
+        if best["cov"] is None:
+            self.update(base)
+            raise NNGPNumericalError("log_marginal could not be evaluated at any theta the optimiser tried")
+        self.update(best["cov"])
+        res.x, res.fun = np.log([getattr(best["cov"], k) for k in ("sigma2", "phi", "tau2")][:len(z0)]), -best["ll"]
+        return best["cov"], res

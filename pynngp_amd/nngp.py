@@ -896,6 +896,24 @@ class NNGP:
         self._latent_ref = (mean, self.s, lp)
         return lp
 
+    def latent_loglik(self, cov: Optional[Covariance] = None, mean: str = "constant", **kw):
+        """``(value, se)``: log p(y | theta) of the LATENT model y = mu + w + e, w the NNGP on S, at ``cov`` (default
+        ``self.cov``), for every ``refType`` -- :meth:`pynngp_amd.LatentPosterior.log_marginal` of
+        :meth:`latent_posterior`, which takes ``**kw`` (``n_probes``, ``seed``, ``rtol``, ...).  ``se`` is the
+        standard error of the stochastic log-determinant term.  Not :meth:`loglik`, which puts the NNGP on y itself
+        and serves S = T only.  ``mean="constant"`` plugs in the GLS intercept (a profiled likelihood)."""
+        return self.latent_posterior(cov, mean).log_marginal(**kw)
+
+    def latent_fit(self, mean: str = "constant", **kw):
+        """Empirical-Bayes (sigma2, phi, tau2) of the latent model, for every ``refType``:
+        :meth:`pynngp_amd.LatentPosterior.fit` (derivative-free, common random numbers; ``**kw`` as there: ``x0``,
+        ``fix_tau2``, ``n_probes``, ``seed``, ``method``, ``maxiter``) from ``self.cov``.  Sets ``cov`` to the
+        estimate and returns ``(cov, result)``."""
+        cov, res = self.latent_posterior(None, mean).fit(**kw)
+        self.cov = cov
+        self._B = self._F = None
+        return cov, res
+
     def latent_mean(self, cov: Optional[Covariance] = None, rtol: float = 1e-8, mean: str = "constant"):
         """Posterior mean of the latent field w on the data locations at a fixed ``cov`` (default ``self.cov``,
         e.g. after :meth:`fit`): ``(w_hat, beta_hat)`` from a conjugate-gradient solve with the NNGP posterior

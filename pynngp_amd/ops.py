@@ -27,6 +27,9 @@ for tracing.
     torch.ops.nngp.precision_apply_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # x (n, nrhs <= 8)
     torch.ops.nngp.latent_cg_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
                                    check_every=8) -> (x, info)           # nrhs solves in lock step, info (nrhs, 4)
+    torch.ops.nngp.latent_cg_batch_trace(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8,
+                                         max_iter=1000, check_every=8) -> (x, info, trace)   # and the CG scalars:
+        # trace (nrhs, max_iter, 2), NaN but for trace[c, k] = (alpha_k, beta_k) of the iterations column c completed
     torch.ops.nngp.polya_gamma(trials, c, seed, sweep) -> (omega, status)   # omega_i ~ PG(trials_i, c_i); status (1,)
         # int32: 0, or the smallest index + 1 whose draw is NaN (non-finite c, trials outside [0, 1024])
 
@@ -136,6 +139,11 @@ def _register_fakes() -> None:
     def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
         raise RuntimeError("latent_cg_batch is a solver call (it synchronises once per chunk of iterations): run it "
                            "eagerly")
+
+    @fake("latent_cg_batch_trace")
+    def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
+        raise RuntimeError("latent_cg_batch_trace is a solver call (it synchronises once per chunk of iterations): "
+                           "run it eagerly")
 
     @fake("polya_gamma")
     def _(trials, c, seed, sweep):

@@ -23,9 +23,13 @@ the reference-set forms were added).  Both run in this
 process in alternating rounds: ms per application, iterations and wall time of the posterior mean to --rtol, 8
 draws at every data location, and the solver's workspace bytes; the gate is the mean solve, eliminated against
 augmented beyond three times the larger max - min spread of the pair.
+With --logdet it measures log det A by stochastic Lanczos quadrature (LatentPosterior.logdet: --probes Rademacher
+probes, eight per batched solve with a trace, to --logdet-rtol): the wall time of --rounds calls after one warm-up
+call, the iterations per probe, the value and its standard error, and the wall time of log_marginal beside it.
 Synthetic data as bench.py (uniform coordinates, standard-normal values, seed 0); prints one JSON line.
     python tools/bench_latent.py [--n 1000000 --m 15 --reps 1000 --warmup 100] [--nrhs 1,2,4,8 --rounds 3]
     python tools/bench_latent.py --ref 100000 [--rounds 3 --reps 200]
+    python tools/bench_latent.py --logdet [--probes 32 --rounds 3]
 """
 import argparse
 import json
@@ -229,6 +233,30 @@ def bench_ref(coords, y, args, dev):
                           "eliminated_no_slower": bool(margin >= -worst)}}
 
 
+def bench_logdet(lp, args, res):
+    """The --logdet measurement (see the module docstring); fills res."""
+    lp.logdet(n_probes=8, seed=1, rtol=args.logdet_rtol)  # warm-up: the workspace and the trace's first allocation
+    out = {}
+
+    def run():
+        out["ld"] = lp.logdet(n_probes=args.probes, seed=0, rtol=args.logdet_rtol)
+
+    walls = wall_ms(run, args.rounds)
+    ld = out["ld"]
+    its = [int(v) for v in ld.iterations]
+
+    def run_lm():
+        out["lm"] = lp.log_marginal(n_probes=args.probes, seed=0, rtol=args.rtol, logdet_rtol=args.logdet_rtol)
+
+    lm_walls = wall_ms(run_lm, args.rounds)
+    res.update(probes=args.probes, logdet_rtol=args.logdet_rtol, rounds=args.rounds, logdet_wall_ms_rounds=walls,
+               logdet_wall_ms_median=statistics.median(walls), logdet_wall_ms_spread=max(walls) - min(walls),
+               logdet_wall_ms_per_probe=statistics.median(walls) / args.probes, iterations_per_probe=its,
+               iterations_min=min(its), iterations_max=max(its), logdet_value=ld.value, logdet_se=ld.se,
+               logdet_se_relative=ld.se / abs(ld.value), log_marginal_value=out["lm"][0], log_marginal_se=out["lm"][1],
+               log_marginal_wall_ms_rounds=lm_walls, log_marginal_wall_ms_median=statistics.median(lm_walls))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -247,6 +275,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="alternating rounds per variant (--nrhs, --ref)")
     ap.add_argument("--ref", type=int, default=None,
                     help="reference-set size: measure the eliminated system against the augmented one instead")
+    ap.add_argument("--logdet", action="store_true",
+                    help="measure log det A by stochastic Lanczos quadrature (and log_marginal) instead")
+    ap.add_argument("--probes", type=int, default=32, help="probes of the --logdet run")
+    ap.add_argument("--logdet-rtol", type=float, default=1e-6, help="tolerance of the probe solves (--logdet)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_latent needs a ROCm GPU (a timing without one says nothing)")
@@ -261,6 +293,14 @@ def main():
     lp = LatentPosterior(coords, y, Covariance("exponential", args.sigma2, args.phi, args.tau2), m=m, device=dev)
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t0
+
+    if args.logdet:
+        res = {"workload": f"latent posterior, log det A by stochastic Lanczos quadrature, N={n}, m={m}, exponential, "
+                           f"sigma2={args.sigma2}, phi={args.phi}, tau2={args.tau2}",
+               "setup_s": setup_s}
+        bench_logdet(lp, args, res)
+        print(json.dumps(res))
+        return
 
     if args.nrhs:
         res = {"workload": f"latent posterior, batched operator, N={n}, m={m}, exponential, sigma2={args.sigma2}, "
