@@ -200,6 +200,27 @@ int nngp_bf_grad(const double *coords, int64_t n_points, int32_t dim, const int3
                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,
+ * order and i0 as nngp_bf_sweep).  With D_ab = sigma2 d_ab rho'(phi d_ab) and u = [-B_i; 1]:
+ *   B  (n_rows, m), F (n_rows,): the factors of nngp_bf_sweep at this theta, equal to that sweep's to its own
+ *                                tolerance (another elimination order: not bit for bit)
+ *   dB (n_rows, m) = d B_i / d phi = C_N^-1 (D u)[:m]
+ *   dF (n_rows,)   = d F_i / d phi = u^T D u
+ *   partials[4]    = sum_i log F_i, sum_i dF_i / F_i, and the two flags of nngp_bf_sweep, folded in that sweep's
+ *                    fixed order: bit-reproducible run to run
+ * Slots without a point (-1 padding) and out-of-range indices hold exactly 0 in B and dB and add exactly 0 to
+ * dF; rows flagged in partials[2] get NaN in all four arrays (nngp_check_partials reads the flags).
+ * kind: NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL (the general-nu Matern kind: NNGP_EUNSUP); 1 <= m <= 32
+ * (else NNGP_EUNSUP); 1 <= dim <= 3.  workspace: nngp_bf_dphi_workspace_bytes(n_rows, m) bytes (0 for an
+ * unsupported m or n_rows < 0), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_dphi_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_dphi(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                 int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                 double *B, double *F, double *dB, double *dF, double *partials, void *workspace,
+                 size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Wave pair plans: the same sweep with every covariance a wavefront's locations share evaluated once.
  * The pair kernel (NNGP_ALGO_PAIRB) sweeps 32 consecutive rows per wavefront; in a spatial visiting
  * order neighbouring locations share most of their neighbours, so only ~46 % of a wave's joint-block
@@ -692,6 +713,15 @@ int nngp_latent_ref_leaves_batch(const int32_t *nbr, const double *B, const int3
                                  const int32_t *rev_k, const void *prep, int64_t n, int64_t n_s, int32_t m,
                                  double sigma2, const double *d, int32_t nrhs, const double *x, const double *v,
                                  const double *z, double *out, void *stream);
+
+/* Two weighted gathers over every node row of a reference-set DAG in one pass (the gradient of the latent
+ * marginal likelihood in phi): for x (n_s, nrhs) on S and every row i < n, reference rows and leaves alike,
+ *   p[i, c] = sum_s B[i,s] x[nbr[i,s], c],   q[i, c] = sum_s dB[i,s] x[nbr[i,s], c]      (both (n, nrhs))
+ * with B and dB (n, m), e.g. those of nngp_bf_dphi.  An index is read once for both weights and all columns, the
+ * sums run in the row phase's order, column c is bit-identical to the nrhs = 1 call on it, and a slot that is -1
+ * or names a node >= n_s adds exactly 0.  One launch, no workspace; 1 <= nrhs <= NNGP_LATENT_MAX_RHS. */
+int nngp_latent_rows_dot2_batch(const int32_t *nbr, const double *B, const double *dB, int64_t n, int64_t n_s,
+                                int32_t m, int32_t nrhs, const double *x, double *p, double *q, void *stream);
 
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident

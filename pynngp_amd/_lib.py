@@ -70,6 +70,8 @@ SYMBOLS = (
     "nngp_bf_sweep_cert",
     "nngp_bf_grad_workspace_bytes",
     "nngp_bf_grad",
+    "nngp_bf_dphi_workspace_bytes",
+    "nngp_bf_dphi",
     "nngp_precision_workspace_bytes",
     "nngp_precision_apply",
     "nngp_precision_sqrt_t_apply",
@@ -90,6 +92,7 @@ SYMBOLS = (
     "nngp_latent_ref_cg_batch",
     "nngp_latent_ref_cg_batch_trace",
     "nngp_latent_ref_leaves_batch",
+    "nngp_latent_rows_dot2_batch",
     "nngp_polya_gamma",
     "nngp_gibbs_pg_update",
     "nngp_gibbs_pg_stats_workspace_bytes",
@@ -149,6 +152,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_grad_workspace_bytes.restype = SZ
     lib.nngp_bf_grad.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad.restype = ctypes.c_int
+    lib.nngp_bf_dphi_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_dphi_workspace_bytes.restype = SZ
+    lib.nngp_bf_dphi.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_dphi.restype = ctypes.c_int
     lib.nngp_bf_cross.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, P, SZ,
                                   I32, P]
     lib.nngp_bf_cross.restype = ctypes.c_int
@@ -284,6 +291,8 @@ def load() -> ctypes.CDLL:
     lib.nngp_latent_ref_cg_batch_trace.restype = ctypes.c_int
     lib.nngp_latent_ref_leaves_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, P, I32, P, P, P, P, P]
     lib.nngp_latent_ref_leaves_batch.restype = ctypes.c_int
+    lib.nngp_latent_rows_dot2_batch.argtypes = [P, P, P, I64, I64, I32, I32, P, P, P, P]
+    lib.nngp_latent_rows_dot2_batch.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -657,6 +666,53 @@ def bf_grad(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2:
                             _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_grad")
     return partials, grad, G
+
+
+def bf_dphi(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,
+            order: Optional[torch.Tensor] = None, B: Optional[torch.Tensor] = None, F: Optional[torch.Tensor] = None,
+            dB: Optional[torch.Tensor] = None, dF: Optional[torch.Tensor] = None,
+            workspace: Optional[torch.Tensor] = None):
+    """The factors and their phi-derivatives in one sweep (``nngp_bf_dphi``, include/nngp.h) over rows ``i0 .. i0 +
+    len(nbr)``: ``(B, F, dB, dF, partials)`` with dB = d B / d phi (rows, m), dF = d F / d phi (rows,) and partials
+    = (sum log F, sum dF / F, first bad-pivot row or -1, first bad-index row or -1).  B and F equal
+    :func:`bf_sweep`'s to that sweep's tolerance, not bit for bit.  ``B`` / ``F`` / ``dB`` / ``dF``: contiguous
+    float64 outputs to write in place, or None.  Stream-ordered on torch's current stream; no host
+    synchronisation.  Kinds exponential .. spherical, 1 <= m <= 32; ``order`` as in :func:`bf_sweep`."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    rows, m = nbr.shape
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "matern":
+        raise NotImplementedError("the phi-derivative sweep serves the kinds exponential .. spherical, not the "
+                                  "general-nu matern kind")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the phi-derivative sweep serves 1 <= m <= {GRAD_MAX_M} (m={m})")
+    dev = _require_gpu(coords, nbr, order, B, F, dB, dF)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    outs = []
+    for t, shape, name in ((B, (rows, m), "B"), (F, (rows,), "F"), (dB, (rows, m), "dB"), (dF, (rows,), "dF")):
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float64, device=dev)
+        elif t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous float64 {shape}, got {t.dtype} {tuple(t.shape)}")
+        outs.append(t)
+    B, F, dB, dF = outs
+    lib = load()
+    need = lib.nngp_bf_dphi_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    if workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the sweep's device")
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_dphi(_ptr(coords), coords.shape[0], coords.shape[1], _ptr(nbr), _ptr(order), rows, m, i0,
+                            KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(B), _ptr(F), _ptr(dB),
+                            _ptr(dF), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_dphi")
+    return B, F, dB, dF, partials
 
 
 def nbr_cert(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, order: Optional[torch.Tensor] = None):
@@ -1559,3 +1615,30 @@ def latent_ref_leaves_batch(nbr, B, off, rev_j, rev_k, prep, n_s: int, sigma2: f
     out = c.empty("l") if out is None else out
     c("nngp_latent_ref_leaves_batch", (x, v, z, out))
     return out
+
+
+def latent_rows_dot2_batch(nbr: torch.Tensor, B: torch.Tensor, dB: torch.Tensor, n_s: int, x: torch.Tensor):
+    """Two weighted gathers over every node row in one pass (nngp_latent_rows_dot2_batch): ``(P, Q)``, both (n,
+    nrhs), P[i, c] = sum_k B[i, k] x[nbr[i, k], c] and Q the same with ``dB``, for ``x`` (n_s, nrhs) on the
+    reference nodes, 1 <= nrhs <= LATENT_MAX_RHS.  A slot that is -1 or names a node >= n_s adds exactly 0; column c
+    is bit-identical to the one-column call on it."""
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not nbr.is_contiguous():
+        raise ValueError(f"nbr must be contiguous int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    n, m = nbr.shape
+    n_s = int(n_s)
+    if not 0 <= n_s <= n:
+        raise ValueError(f"need 0 <= n_s <= n (got n_s={n_s}, n={n})")
+    for t, name in ((B, "B"), (dB, "dB")):
+        if t.dtype != torch.float64 or tuple(t.shape) != (n, m) or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous float64 ({n}, {m}), got {t.dtype} {tuple(t.shape)}")
+    if (x.dtype != torch.float64 or x.dim() != 2 or x.shape[0] != n_s or not 1 <= x.shape[1] <= LATENT_MAX_RHS
+            or not x.is_contiguous()):
+        raise ValueError(f"x must be contiguous float64 ({n_s}, nrhs) with 1 <= nrhs <= {LATENT_MAX_RHS}, got "
+                         f"{x.dtype} {tuple(x.shape)}")
+    dev = _require_gpu(nbr, B, dB, x)
+    nrhs = x.shape[1]
+    p = torch.empty((n, nrhs), dtype=torch.float64, device=dev)
+    q = torch.empty((n, nrhs), dtype=torch.float64, device=dev)
+    _check(load().nngp_latent_rows_dot2_batch(_ptr(nbr), _ptr(B), _ptr(dB), n, n_s, m, nrhs, _ptr(x), _ptr(p), _ptr(q),
+                                              _stream(dev)), "nngp_latent_rows_dot2_batch")
+    return p, q

@@ -11,6 +11,7 @@
 #include "bf_pairb.h"
 #include "nbr_cert.h"
 #include "bf_grad.h"
+#include "bf_dphi.h"
 #include "latent.h"
 
 namespace {
@@ -211,6 +212,45 @@ int nngp_bf_grad(const double* coords, int64_t n_points, int32_t dim, const int3
                      (double*)workspace};
     hipError_t e = nngp::bf_grad_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_dphi_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    // at least one record, so the size is never 0 for a supported call
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * 4 * sizeof(double));
+}
+
+int nngp_bf_dphi(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                 int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2, double* B,
+                 double* F, double* dB, double* dF, double* partials, void* workspace, size_t workspace_bytes,
+                 void* stream) {
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (partials == nullptr) return fail(NNGP_EINVAL, "partials must be non-null");
+    if (n_rows > 0 && (B == nullptr || F == nullptr || dB == nullptr || dF == nullptr))
+        return fail(NNGP_EINVAL, "B, F, dB and dF must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the phi-derivative sweep serves 1 <= m <= 32 (m=%d)", m);
+    if (kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the phi-derivative sweep serves kinds exponential .. spherical, not the general-nu "
+                                 "matern");
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EINVAL, "unknown kind %d", kind);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (!(sigma2 > 0.0) || !(phi > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(phi) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, phi > 0, tau2 >= 0 (finite)");
+    if (B == dB || F == dF || (const void*)B == (const void*)F)
+        if (n_rows > 0) return fail(NNGP_EINVAL, "B, F, dB and dF must not alias");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_dphi_workspace_bytes(n_rows, m);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    nngp::DphiArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, phi, tau2, B, F, dB, dF,
+                     (double*)workspace};
+    hipError_t e = nngp::bf_dphi_launch(a, partials, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_dphi launch");
     return NNGP_OK;
 }
 
@@ -1090,6 +1130,20 @@ int nngp_latent_ref_leaves_batch(const int32_t* nbr, const double* B, const int3
     const LatentArgs a{nbr, B, off, rev_j, prep, n, n_s, m, sigma2, d, nrhs, nullptr, 0, stream, false,
                        "latent_ref_leaves_batch launch"};
     return latent_launched(nngp::latent_leaves_launch(latent_geom(a), nrhs, x, v, z, out, (hipStream_t)stream), a);
+}
+
+int nngp_latent_rows_dot2_batch(const int32_t* nbr, const double* B, const double* dB, int64_t n, int64_t n_s,
+                                int32_t m, int32_t nrhs, const double* x, double* p, double* q, void* stream) {
+    if (nbr == nullptr || B == nullptr || dB == nullptr) return fail(NNGP_EINVAL, "nbr, B and dB must be non-null");
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    if (n < 0 || n_s < 0 || n_s > n) return fail_n_s(n, n_s);
+    const int rc = latent_sizes(n, m, 1.0);
+    if (rc != NNGP_OK) return rc;
+    if (n > 0 && (p == nullptr || q == nullptr || (n_s > 0 && x == nullptr)))
+        return fail(NNGP_EINVAL, "x, p and q must be non-null");
+    if (p != nullptr && (p == q || p == x || q == x)) return fail(NNGP_EINVAL, "p, q and x must not alias");
+    hipError_t e = nngp::latent_rows_dot2_launch(nbr, B, dB, n, n_s, m, nrhs, x, p, q, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, "latent_rows_dot2_batch launch") : NNGP_OK;
 }
 
 size_t nngp_row_order_workspace_bytes(int64_t n_rows) { return nngp::row_order_workspace_bytes(n_rows); }

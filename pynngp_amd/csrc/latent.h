@@ -74,5 +74,9 @@ hipError_t latent_cg_run(LatentGeom g, int nrhs, const double* b, double* x, dou
 // g.d null: out = a [+ z / sqrt(f)]
 hipError_t latent_leaves_launch(const LatentGeom& g, int nrhs, const double* x, const double* v, const double* z,
                                 double* out, hipStream_t s);
+// two weighted gathers over every node row in one pass: p = B x, q = dB x, both (n, nrhs), x (n_s, nrhs); a slot that
+// is -1 or names a node >= n_s counts 0.  The summation order is the row phase's.
+hipError_t latent_rows_dot2_launch(const int32_t* nbr, const double* B, const double* dB, int64_t n, int64_t n_s,
+                                   int m, int nrhs, const double* x, double* p, double* q, hipStream_t s);
 
 }  // namespace nngp

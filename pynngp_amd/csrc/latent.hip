@@ -164,6 +164,65 @@ __global__ __launch_bounds__(kBlock) void latent_row_kernel(const int32_t* __res
     }
 }
 
+// The row phase's gather with two weights and no scale: for every node row i (reference rows and leaves alike)
+//   p[i, c] = sum_s B[i,s] x[nbr[i,s], c],   q[i, c] = sum_s dB[i,s] x[nbr[i,s], c]
+// with x on the n_s reference nodes.  An index is read once for both weights and all columns; lanes, slots and
+// the butterfly are latent_row_kernel's, so each sum has that kernel's order and a column's bits depend on
+// neither KP nor the other columns.  A slot that is -1 or names a node >= n_s: exactly 0.
+template <int G, int KP>
+__global__ __launch_bounds__(kBlock) void latent_row_dot2_kernel(const int32_t* __restrict__ nbr,
+                                                                 const double* __restrict__ B,
+                                                                 const double* __restrict__ dB,
+                                                                 const double* __restrict__ x, double* __restrict__ p,
+                                                                 double* __restrict__ q, int64_t n, int64_t n_s, int m,
+                                                                 int nrhs) {
+    nrhs = columns<KP>(nrhs);
+    constexpr int kRows = kBlock / G;
+    const int g = threadIdx.x / G, l = threadIdx.x % G;
+    int cc[KP];
+#pragma unroll
+    for (int c = 0; c < KP; ++c) cc[c] = column_of(c, nrhs);
+    int64_t lo, hi;
+    tile_range((n + kRows - 1) / kRows, &lo, &hi);
+    for (int64_t tile = lo; tile < hi; ++tile) {
+        const int64_t i = tile * kRows + g;
+        double ap[KP], aq[KP];
+#pragma unroll
+        for (int c = 0; c < KP; ++c) ap[c] = aq[c] = 0.0;
+        if (i < n) {
+            const int32_t* nb = nbr + i * m;
+            const double* bb = B + i * m;
+            const double* db = dB + i * m;
+            for (int s = l; s < m; s += G) {
+                const int32_t j = nb[s];
+                if (j >= 0 && (int64_t)j < n_s) {
+                    const double b = bb[s], d = db[s];
+                    const double* xj = x + (int64_t)j * nrhs;
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) {
+                        const double xv = xj[cc[c]];
+                        ap[c] = fma(b, xv, ap[c]);
+                        aq[c] = fma(d, xv, aq[c]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KP; ++c) {
+            ap[c] = lane_group_sum<G>(ap[c]);
+            aq[c] = lane_group_sum<G>(aq[c]);
+        }
+        if (i < n && l == 0) {
+#pragma unroll
+            for (int c = 0; c < KP; ++c)
+                if (c < nrhs) {
+                    p[i * nrhs + c] = ap[c];
+                    q[i * nrhs + c] = aq[c];
+                }
+        }
+    }
+}
+
 // u[i, c] = z1[i, c] sqrt(invF_i / sigma2): the column phase's input for the square-root operator
 __global__ __launch_bounds__(kBlock) void latent_scale_kernel(const double* __restrict__ invF,
                                                               const double* __restrict__ z1, double* __restrict__ u,
@@ -924,6 +983,21 @@ hipError_t latent_leaves_launch(const LatentGeom& g, int nrhs, const double* x, 
         NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_leaf_kernel<16, KP>), dim3(tile_blocks(n_l, kBlock / 16)),
                                                 dim3(kBlock), 0, s, g.nbr, g.B, g.prep.invF, g.d, x, v, z, out, g.n,
                                                 g.n_s, g.m, nrhs, inv_s2));
+    return hipGetLastError();
+}
+
+hipError_t latent_rows_dot2_launch(const int32_t* nbr, const double* B, const double* dB, int64_t n, int64_t n_s,
+                                   int m, int nrhs, const double* x, double* p, double* q, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (m <= 4)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_row_dot2_kernel<4, KP>), dim3(tile_blocks(n, kBlock / 4)),
+                                                dim3(kBlock), 0, s, nbr, B, dB, x, p, q, n, n_s, m, nrhs));
+    else if (m <= 8)
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_row_dot2_kernel<8, KP>), dim3(tile_blocks(n, kBlock / 8)),
+                                                dim3(kBlock), 0, s, nbr, B, dB, x, p, q, n, n_s, m, nrhs));
+    else
+        NNGP_LATENT_KP(nrhs, hipLaunchKernelGGL((latent_row_dot2_kernel<16, KP>), dim3(tile_blocks(n, kBlock / 16)),
+                                                dim3(kBlock), 0, s, nbr, B, dB, x, p, q, n, n_s, m, nrhs));
     return hipGetLastError();
 }
 

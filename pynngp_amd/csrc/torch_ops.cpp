@@ -224,6 +224,32 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad(const at::Tensor& coords,
     return {p, g, G};
 }
 
+// the factors and their phi-derivatives (nngp_bf_dphi): (B (rows, m), F (rows,), dB (rows, m), dF (rows,), partials (4,))
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_dphi(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    double sigma2, double phi, double tau2) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == rows &&
+                        order->is_contiguous(), "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(coords, *order, "order");
+    }
+    auto f64 = coords.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64);
+    at::Tensor dB = at::empty({rows, m}, f64), dF = at::empty({rows}, f64), p = at::empty({4}, f64);
+    const int64_t need = (int64_t)nngp_bf_dphi_workspace_bytes(rows, (int32_t)m);
+    auto ws = at::empty({need > 256 ? need : 256}, f64.dtype(at::kByte));
+    check_rc(nngp_bf_dphi(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                          ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2,
+                          B.data_ptr<double>(), F.data_ptr<double>(), dB.data_ptr<double>(), dF.data_ptr<double>(),
+                          p.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(), stream(coords)),
+             "nngp_bf_dphi");
+    return {B, F, dB, dF, p};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross(const at::Tensor& ref, const at::Tensor& query,
                                                         const at::Tensor& nbr, int64_t kind, double sigma2, double phi,
                                                         double tau2, const c10::optional<at::Tensor>& ref_values,
@@ -535,6 +561,8 @@ TORCH_LIBRARY(nngp, m) {
           "Tensor? cert=None, Tensor? cert_info=None) -> ()");
     m.def("bf_grad(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2, "
           "Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_dphi(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2) "
+          "-> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("nbr_cert(Tensor coords, Tensor nbr, Tensor? order, int i0) -> (Tensor, Tensor)");
     m.def("pair_plan(Tensor nbr, Tensor? order, int i0, int n_points, int dim) -> (Tensor, Tensor)");
     m.def("bf_cross(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
@@ -552,6 +580,7 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_out", &bf_sweep_out);
     m.impl("bf_cross", &bf_cross);
     m.impl("bf_grad", &bf_grad);
+    m.impl("bf_dphi", &bf_dphi);
     m.impl("row_order", &row_order);
     m.impl("pair_plan", &pair_plan);
     m.impl("nbr_cert", &nbr_cert);

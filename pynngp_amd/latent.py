@@ -735,6 +735,13 @@ class LatentPosterior:
         ``z`` (P, n_S) in the order of ``ref`` (S = T: of ``coords``), each weighted by its z^T z -- the n_S rows of
         sqrt(n_S) I give the trace exactly.  A breakdown raises, a probe that ran out of ``max_iter`` is named in a
         ``RuntimeWarning`` (its quadrature then rests on ``max_iter`` points)."""
+        return self._logdet_run(n_probes, seed, z, rtol, max_iter, batch)
+
+    def _logdet_run(self, n_probes, seed, z, rtol, max_iter, batch, visit=None):
+        """:meth:`logdet`'s loop.  ``visit(k0, Zc, root, X)``, when given, sees every chunk after its solve: the
+        probes Zc (k, n_S) of rows k0 .. k0 + k - 1, root = diag(A_S)^1/2 and the solutions X (n_S, k) of A_S x =
+        M^1/2 z -- the vectors a Hutchinson estimate of tr(A_S^-1 dA_S) needs (:meth:`log_marginal_grad`).  It takes
+        no part in the log-determinant: the result is the same bits with or without it."""
         batch = self._batch(batch)
         max_iter = int(self._cg_args(rtol, max_iter))
         Z = self._probe_rows(n_probes, seed, z)
@@ -750,8 +757,10 @@ class LatentPosterior:
             k1 = min(P, k0 + batch)
             tr = trace[:k1 - k0]
             tr.fill_(float("nan"))
-            _, info[k0:k1] = self._solve_cols((Z[k0:k1] * root).t().contiguous(), rtol, max_iter, trace=tr)
+            X, info[k0:k1] = self._solve_cols((Z[k0:k1] * root).t().contiguous(), rtol, max_iter, trace=tr)
             self._report(info[k0:k1], rtol, first=k0)
+            if visit is not None:
+                visit(k0, Z[k0:k1], root, X)
             its = info[k0:k1, 0].astype(np.int64)
             host = tr[:, :max(int(its.max()), 1)].cpu().numpy()
             for c, it in enumerate(its):
@@ -774,6 +783,11 @@ class LatentPosterior:
         standard error, halved, is ``se`` -- everything else is exact to rounding.  With covariates and no ``beta``,
         v = y - X beta_hat with the GLS estimate (:meth:`gls_beta`): a plug-in (profiled) likelihood, not one with
         beta integrated out."""
+        return self._log_marginal_run(beta, n_probes, seed, z, rtol, max_iter, batch, logdet_rtol)[:2]
+
+    def _log_marginal_run(self, beta, n_probes, seed, z, rtol, max_iter, batch, logdet_rtol, visit=None, mean=None):
+        """:meth:`log_marginal`: ``(value, se)``.  ``mean(v, x)`` sees the centred response and the mean solve's
+        solution before the probes run, ``visit`` is :meth:`_logdet_run`'s; neither changes a bit of the value."""
         beta = self._beta_for_draws(beta, rtol, max_iter)
         if beta.shape != (self.p,):
             raise ValueError(f"beta must hold {self.p} coefficients")
@@ -781,6 +795,8 @@ class LatentPosterior:
         v = self._yres(beta)
         b = self._rhs(beta)
         x, _ = self._solve(b, rtol, max_iter)
+        if mean is not None:
+            mean(v, x)
         d, f = self.d, 1.0 / (self.cov.sigma2 * self.F)
         obs = d > 0
         one = torch.ones_like(d)
@@ -791,22 +807,146 @@ class LatentPosterior:
             g = torch.where(ol, fl * dl / (fl + dl), torch.zeros_like(dl))
             terms = terms - torch.log(torch.where(ol, g, one[n_s:])).sum()
             quad = quad + (g * v[n_s:] * v[n_s:]).sum()
-        ld = self.logdet(n_probes, seed, z, logdet_rtol, max_iter, batch)
+        ld = self._logdet_run(n_probes, seed, z, logdet_rtol, max_iter, batch, visit)
         m2 = int(obs.sum()) * math.log(2.0 * math.pi) + float(terms) + ld.value + float(quad)
         return -0.5 * m2, 0.5 * ld.se
 
+    GRAD_MAX_M = _lib.GRAD_MAX_M  # the phi-derivative sweep's range of m
+
+    def _check_grad(self, cov):
+        """The gradient's coverage, checked before any device work."""
+        if cov.kind == "matern":
+            raise ValueError("the gradient of the latent marginal likelihood serves the kinds exponential .. "
+                             "spherical, not the general-nu matern kind")
+        if self.m > self.GRAD_MAX_M:
+            raise ValueError(f"the gradient of the latent marginal likelihood serves m <= {self.GRAD_MAX_M} "
+                             f"(m={self.m})")
+
+    def _grad_rows(self):
+        """Per-row derivatives of (f_S, d_S, g_L) in (sigma2, phi, tau2) at the current theta, the phi-derivative
+        of B, and the log terms' derivative: one ``nngp_bf_dphi`` sweep plus elementwise work."""
+        cov, n_s = self.cov, self.n_s
+        _, _, dB, dF, p = _lib.bf_dphi(self.coords, self.nbr, 0, cov.kind, 1.0, cov.phi, 0.0)
+        _raise_on_bad(p.cpu().numpy())
+        d, f = self.d, 1.0 / (cov.sigma2 * self.F)
+        obs = d > 0
+        zero, one = torch.zeros_like(d), torch.ones_like(d)
+        df_all = (-f / cov.sigma2, -f * dF / self.F, zero)  # d f / d (sigma2, phi, tau2), every node
+        dd_all = (zero, zero, -d / cov.tau2)
+        rows = []
+        for df, dd in zip(df_all, dd_all):
+            fl, dl, ol = f[n_s:], d[n_s:], obs[n_s:]
+            den = (fl + dl) * (fl + dl)
+            dg = torch.where(ol, (df[n_s:] * dl * dl + dd[n_s:] * fl * fl) / den, zero[n_s:])
+            g = torch.where(ol, fl * dl / (fl + dl), zero[n_s:])
+            logs = (torch.where(obs[:n_s], dd[:n_s] / torch.where(obs[:n_s], d[:n_s], one[:n_s]), zero[:n_s]).sum()
+                    + (df[:n_s] / f[:n_s]).sum() + torch.where(ol, dg / torch.where(ol, g, one[n_s:]), zero[n_s:]).sum())
+            rows.append({"df": df[:n_s].contiguous(), "dd": dd[:n_s].contiguous(), "dg": dg, "logs": logs})
+        fl, dl, ol = f[n_s:], d[n_s:], obs[n_s:]
+        return dB, f[:n_s].contiguous(), torch.where(ol, fl * dl / (fl + dl), zero[n_s:]), rows
+
+    def _grad_bilinear(self, dB, fS, g, rows, X, Y):
+        """(3, k): column c holds X[:, c]^T (dA_S / d theta) Y[:, c] for theta = sigma2, phi, tau2 (module docstring
+        of the gradient: DESIGN 4.6d), X and Y storage-order columns (n_S, k).  Also returns the two gathers of X."""
+        n_s = self.n_s
+        PX, QX = _lib.latent_rows_dot2_batch(self.nbr, self.B, dB, n_s, X.contiguous())
+        if Y is X:
+            PY, QY = PX, QX
+        else:
+            PY, QY = _lib.latent_rows_dot2_batch(self.nbr, self.B, dB, n_s, Y.contiguous())
+        eX, eY = X - PX[:n_s], Y - PY[:n_s]
+        pX, pY, qX, qY = PX[n_s:], PY[n_s:], QX[n_s:], QY[n_s:]
+        out = []
+        for k, r in enumerate(rows):
+            tS = r["df"][:, None] * eX * eY + r["dd"][:, None] * X * Y
+            tL = r["dg"][:, None] * pX * pY
+            if k == 1:  # phi moves B as well
+                tS = tS - fS[:, None] * (QX[:n_s] * eY + eX * QY[:n_s])
+                tL = tL + g[:, None] * (qX * pY + pX * qY)
+            out.append(self._col_sums(tS) + self._col_sums(tL))
+        return torch.stack(out), (pX, qX)
+
+    @staticmethod
+    def _col_sums(T):
+        """(k,) column sums of T (rows, k), each column summed on its own as a fresh contiguous vector: a column's
+        sum then depends on neither k nor the other columns (a reduction over dim 0 picks its order by shape)."""
+        return torch.stack([T[:, c].clone().sum() for c in range(T.shape[1])])
+
+    def log_marginal_grad(self, beta=None, n_probes: int = 32, seed: int = 0, z=None, rtol: float = 1e-8,
+                          max_iter: Optional[int] = None, batch=None, logdet_rtol: float = 1e-6):
+        """``(value, se, grad, grad_se)``: :meth:`log_marginal` and its gradient in (sigma2, phi, tau2).  ``value`` and
+        ``se`` are that method's at the same arguments, bit for bit, from the same solves: the gradient adds one
+        ``nngp_bf_dphi`` sweep (dB / dphi, dF / dphi per row) and a few two-weight gathers
+        (``nngp_latent_rows_dot2_batch``), no solve.  With x = A_S^-1 b_S and the row derivatives of f, d, g and B,
+
+            d(-2 log p) = - sum dlog d - sum dlog g - sum_S dlog f + tr(A_S^-1 dA_S)
+                          + sum_S dd v^2 + sum_L dg v^2 - 2 db_S^T x + x^T dA_S x,
+
+        every term but the trace exact to rounding.  The trace is a Hutchinson estimate on the log-determinant's own
+        probes: the solutions s_k of A_S s = M^1/2 z_k that :meth:`logdet` computes give s_k^T dA_S (M^-1/2 z_k), whose
+        mean over the probes is the estimate and whose sample standard deviation / sqrt(P), halved, is ``grad_se``
+        (inf for one probe).  The n_S rows of sqrt(n_S) I as ``z`` make it exact.  ``grad`` and ``grad_se`` are numpy
+        (3,) arrays.  The probes are solved to ``logdet_rtol``, which bounds the trace's solver error.
+
+        With covariates and no ``beta``, beta_hat is the GLS estimate, which maximises this likelihood in beta at
+        theta: the gradient of the profiled value is the partial gradient at beta_hat held fixed (the envelope
+        theorem), so no d beta_hat / d theta term appears.  Kinds exponential .. spherical, m <= 32 (``ValueError``
+        otherwise, before any device work)."""
+        self._check_grad(self.cov)
+        n_s = self.n_s
+        dB, fS, g, rows = self._grad_rows()
+        acc = {"tr": []}
+
+        def mean(v, x):
+            X = x[:, None]
+            bil, (pX, qX) = self._grad_bilinear(dB, fS, g, rows, X, X)
+            vS, vL = v[:n_s], v[n_s:]
+            fixed = []
+            for k, r in enumerate(rows):
+                db_x = (r["dd"] * vS * x).sum() + (vL * r["dg"] * pX[:, 0]).sum()
+                if k == 1:
+                    db_x = db_x + (vL * g * qX[:, 0]).sum()
+                fixed.append(-r["logs"] + (r["dd"] * vS * vS).sum() + (r["dg"] * vL * vL).sum() - 2.0 * db_x
+                             + bil[k, 0])
+            acc["fixed"] = torch.stack(fixed)
+
+        def visit(k0, Zc, root, X):
+            W = (Zc / root).t().contiguous()
+            acc["tr"].append(self._grad_bilinear(dB, fS, g, rows, X, W)[0])
+
+        value, se = self._log_marginal_run(beta, n_probes, seed, z, rtol, max_iter, batch, logdet_rtol, visit, mean)
+        per = torch.cat(acc["tr"], dim=1).cpu().numpy()  # (3, P)
+        P = per.shape[1]
+        tr = per.mean(axis=1)
+        tr_se = per.std(axis=1, ddof=1) / math.sqrt(P) if P > 1 else np.full(3, math.inf)
+        grad = -0.5 * (acc["fixed"].cpu().numpy() + tr)
+        return value, se, grad, 0.5 * tr_se
+
     def fit(self, x0=None, fix_tau2: Optional[float] = None, n_probes: int = 32, seed: int = 0,
-            method: str = "Nelder-Mead", maxiter: int = 200, z=None, rtol: float = 1e-8, batch=None):
+            method: Optional[str] = None, maxiter: int = 200, z=None, rtol: float = 1e-8, batch=None,
+            gradient: bool = False):
         """Empirical-Bayes theta: maximise :meth:`log_marginal` over log (sigma2, phi, tau2) (``fix_tau2``: over log
         (sigma2, phi) at that nugget) from ``x0`` -- a :class:`Covariance` of this kind or (sigma2, phi, tau2),
         default the current ``cov``.  Every evaluation uses the same probes (common random numbers), so the
         objective is a deterministic function of theta; theta moves by :meth:`update` on the same neighbour sets,
-        and beta, with covariates, is re-estimated by GLS at each theta.  Derivative-free (``scipy.optimize.minimize``,
-        ``method``, at most ``maxiter`` iterations).  Leaves the object at the best theta seen and returns ``(cov,
-        result)``: the fitted :class:`Covariance` and the optimiser's result (``result.fun`` = -log_marginal there)."""
+        and beta, with covariates, is re-estimated by GLS at each theta.  Derivative-free by default
+        (``scipy.optimize.minimize``, ``method`` -- Nelder-Mead unless given --, at most ``maxiter`` iterations).
+        Leaves the object at the best theta seen and returns ``(cov, result)``: the fitted :class:`Covariance` and the
+        optimiser's result (``result.fun`` = -log_marginal there).
+
+        ``gradient=True``: every evaluation is :meth:`log_marginal_grad`, chain-ruled to log theta (d / d log theta_i
+        = theta_i d / d theta_i), and the default method is L-BFGS-B.  With Rademacher probes the value is a
+        stochastic-Lanczos-quadrature estimate and the gradient a Hutchinson estimate on the same probes: both are
+        deterministic functions of theta, but they agree only up to probe noise, so the line search may stop on
+        noise of the order of ``se``.  With basis probes (``z`` = the rows of sqrt(n_S) I) they agree exactly.  The
+        general-nu ``matern`` kind (and m > 32) has no gradient: ``ValueError`` before any device work."""
         from scipy.optimize import minimize
 
         base = self.cov
+        if gradient:
+            self._check_grad(base)
+        if method is None:
+            method = "L-BFGS-B" if gradient else "Nelder-Mead"
         if isinstance(x0, Covariance):
             th0 = x0.theta
         else:
@@ -821,23 +961,30 @@ class LatentPosterior:
         best = {"ll": -math.inf, "cov": None}
 
         def obj(lz):
+            g = None
+            fail = (1e300, np.zeros(len(z0))) if gradient else 1e300
             try:
                 cov = base.replace(sigma2=math.exp(lz[0]), phi=math.exp(lz[1]),
                                    tau2=math.exp(lz[2]) if free_tau else float(fix_tau2))
                 self.update(cov)
-                ll, _ = self.log_marginal(n_probes=n_probes, seed=seed, z=Z, rtol=rtol, batch=batch)
+                if gradient:
+                    ll, _, g, _ = self.log_marginal_grad(n_probes=n_probes, seed=seed, z=Z, rtol=rtol, batch=batch)
+                else:
+                    ll, _ = self.log_marginal(n_probes=n_probes, seed=seed, z=Z, rtol=rtol, batch=batch)
             except (NNGPNumericalError, OverflowError):
-                return 1e300
-            if not math.isfinite(ll):
-                return 1e300
+                return fail
+            if not math.isfinite(ll) or (gradient and not np.all(np.isfinite(g))):
+                return fail
             if ll > best["ll"]:
                 best.update(ll=ll, cov=cov)
+            if gradient:
+                return -ll, -(g * np.array(cov.theta))[:len(z0)]
             return -ll
 
         opts = {"maxiter": int(maxiter)}
         if method == "Nelder-Mead":
             opts.update(xatol=1e-4, fatol=1e-6)
-        res = minimize(obj, np.array(z0), method=method, options=opts)
+        res = minimize(obj, np.array(z0), method=method, jac=True if gradient else None, options=opts)
         if best["cov"] is None:
             self.update(base)
             raise NNGPNumericalError("log_marginal could not be evaluated at any theta the optimiser tried")

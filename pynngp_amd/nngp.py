@@ -904,11 +904,18 @@ class NNGP:
         and serves S = T only.  ``mean="constant"`` plugs in the GLS intercept (a profiled likelihood)."""
         return self.latent_posterior(cov, mean).log_marginal(**kw)
 
+    def latent_loglik_grad(self, cov: Optional[Covariance] = None, mean: str = "constant", **kw):
+        """``(value, se, grad, grad_se)``: :meth:`latent_loglik` with its gradient in (sigma2, phi, tau2) and the
+        gradient's standard errors -- :meth:`pynngp_amd.LatentPosterior.log_marginal_grad` of
+        :meth:`latent_posterior` (``**kw`` as there).  The fused kinds exponential .. spherical, m <= 32."""
+        return self.latent_posterior(cov, mean).log_marginal_grad(**kw)
+
     def latent_fit(self, mean: str = "constant", **kw):
         """Empirical-Bayes (sigma2, phi, tau2) of the latent model, for every ``refType``:
-        :meth:`pynngp_amd.LatentPosterior.fit` (derivative-free, common random numbers; ``**kw`` as there: ``x0``,
-        ``fix_tau2``, ``n_probes``, ``seed``, ``method``, ``maxiter``) from ``self.cov``.  Sets ``cov`` to the
-        estimate and returns ``(cov, result)``."""
+        :meth:`pynngp_amd.LatentPosterior.fit` (derivative-free by default, ``gradient=True``: L-BFGS-B on the
+        analytic gradient; common random numbers; ``**kw`` as there: ``x0``, ``fix_tau2``, ``n_probes``, ``seed``,
+        ``method``, ``maxiter``, ``gradient``) from ``self.cov``.  Sets ``cov`` to the estimate and returns ``(cov,
+        result)``."""
         cov, res = self.latent_posterior(None, mean).fit(**kw)
         self.cov = cov
         self._B = self._F = None
