@@ -97,6 +97,10 @@ SYMBOLS = (
     "nngp_gibbs_pg_update",
     "nngp_gibbs_pg_stats_workspace_bytes",
     "nngp_gibbs_pg_stats",
+    "nngp_binomial_newton_step_workspace_bytes",
+    "nngp_binomial_newton_step",
+    "nngp_binomial_check_partials",
+    "nngp_logistic_normal",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -220,6 +224,14 @@ def load() -> ctypes.CDLL:
     lib.nngp_gibbs_pg_stats_workspace_bytes.restype = SZ
     lib.nngp_gibbs_pg_stats.argtypes = [I64, P, P, P, P, P, I32, P, P, P, P]
     lib.nngp_gibbs_pg_stats.restype = ctypes.c_int
+    lib.nngp_binomial_newton_step_workspace_bytes.argtypes = [I64]
+    lib.nngp_binomial_newton_step_workspace_bytes.restype = SZ
+    lib.nngp_binomial_newton_step.argtypes = [I64, P, P, P, P, P, P, P, P, P, SZ, P]
+    lib.nngp_binomial_newton_step.restype = ctypes.c_int
+    lib.nngp_binomial_check_partials.argtypes = [P, P, P]
+    lib.nngp_binomial_check_partials.restype = ctypes.c_int
+    lib.nngp_logistic_normal.argtypes = [I64, P, P, P, P]
+    lib.nngp_logistic_normal.restype = ctypes.c_int
     lib.nngp_bf_sweep.restype = ctypes.c_int
     lib.nngp_color_moral_graph_dev.argtypes = [P, P, P, I64, I32, P, P, SZ, P]
     lib.nngp_color_moral_graph_dev.restype = I64
@@ -1307,6 +1319,63 @@ def gibbs_pg_update(trials: torch.Tensor, kappa: torch.Tensor, xb: torch.Tensor,
                                        _pg_sweep(sweep), _ptr(omega), _ptr(yres), _ptr(status), _stream(dev)),
            "nngp_gibbs_pg_update")
     return omega, yres, status
+
+
+# ---------------------------------------------------------------------------- binomial latent posterior (Laplace)
+def binomial_newton_step(trials: torch.Tensor, successes: torch.Tensor, offset: torch.Tensor, w: torch.Tensor,
+                         d: Optional[torch.Tensor] = None, rhs: Optional[torch.Tensor] = None,
+                         g: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None):
+    """One Newton step's link quantities per node (nngp_binomial_newton_step): ``(d, rhs, g, partials)`` with d = W =
+    b p (1 - p), g = s - b p, rhs = W w + g at eta = offset + w, and partials (4,) on the device = (sum of the
+    log-likelihood terms, max |g|, first node with a non-finite eta + 1 or 0, first node with negative trials + 1 or
+    0).  Faults are data: nothing is read back here (:func:`binomial_check_partials` does that)."""
+    if not (trials.is_cuda and successes.is_cuda and offset.is_cuda and w.is_cuda):
+        raise NotImplementedError("pynngp_amd has no CPU path: binomial_newton_step needs ROCm GPU tensors")
+    dev = _require_gpu(trials, successes, offset, w, d, rhs, g, partials)
+    n = trials.shape[0] if trials.dim() == 1 else -1
+    _pg_vec(trials, n, "trials", torch.int32)
+    for t, name in ((successes, "successes"), (offset, "offset"), (w, "w")):
+        _pg_vec(t, n, name)
+    d = torch.empty(n, dtype=torch.float64, device=dev) if d is None else d
+    rhs = torch.empty(n, dtype=torch.float64, device=dev) if rhs is None else rhs
+    g = torch.empty(n, dtype=torch.float64, device=dev) if g is None else g
+    partials = torch.empty(4, dtype=torch.float64, device=dev) if partials is None else partials
+    for t, name in ((d, "d"), (rhs, "rhs"), (g, "g")):
+        _pg_vec(t, n, name)
+    _pg_vec(partials, 4, "partials")
+    lib = load()
+    need = lib.nngp_binomial_newton_step_workspace_bytes(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    _check(lib.nngp_binomial_newton_step(n, _ptr(trials), _ptr(successes), _ptr(offset), _ptr(w), _ptr(d), _ptr(rhs),
+                                         _ptr(g), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_binomial_newton_step")
+    return d, rhs, g, partials
+
+
+def binomial_check_partials(partials_host) -> Tuple[int, int]:
+    """``(first_nonfinite, first_negative_trials)`` of host-resident partials of :func:`binomial_newton_step`
+    (nngp_binomial_check_partials), -1 = none."""
+    p = (ctypes.c_double * 4)(*[float(v) for v in partials_host])
+    a, b = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    load().nngp_binomial_check_partials(ctypes.cast(p, ctypes.c_void_p), ctypes.cast(ctypes.byref(a), ctypes.c_void_p),
+                                        ctypes.cast(ctypes.byref(b), ctypes.c_void_p))
+    return int(a.value), int(b.value)
+
+
+def logistic_normal(mu: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = E[logistic(mu[i] + s[i] Z)], Z ~ N(0, 1) (nngp_logistic_normal; s = 0: logistic(mu))."""
+    if not (mu.is_cuda and s.is_cuda):
+        raise NotImplementedError("pynngp_amd has no CPU path: logistic_normal needs ROCm GPU tensors")
+    dev = _require_gpu(mu, s, out)
+    n = mu.shape[0] if mu.dim() == 1 else -1
+    _pg_vec(mu, n, "mu")
+    _pg_vec(s, n, "s")
+    out = torch.empty(n, dtype=torch.float64, device=dev) if out is None else out
+    _pg_vec(out, n, "out")
+    _check(load().nngp_logistic_normal(n, _ptr(mu), _ptr(s), _ptr(out), _stream(dev)), "nngp_logistic_normal")
+    return out
 
 
 def gibbs_pg_stats(r: torch.Tensor, Ft: torch.Tensor, omega: torch.Tensor, kappa: torch.Tensor,

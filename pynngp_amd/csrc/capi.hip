@@ -13,6 +13,7 @@
 #include "bf_grad.h"
 #include "bf_dphi.h"
 #include "latent.h"
+#include "latent_binomial.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -831,6 +832,43 @@ int nngp_gibbs_pg_update(int64_t n, const int32_t* trials, const double* kappa, 
                                             (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "gibbs_pg_update launch");
     return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- binomial latent posterior (latent_binomial.hip)
+size_t nngp_binomial_newton_step_workspace_bytes(int64_t n) {
+    if (n < 0 || n >= INT32_MAX) return 0;
+    return nngp::binomial_newton_step_workspace_bytes(n);
+}
+
+int nngp_binomial_newton_step(int64_t n, const int32_t* trials, const double* successes, const double* offset,
+                              const double* w, double* d, double* rhs, double* g, double* partials, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (n < 0 || n >= INT32_MAX) return fail(NNGP_EINVAL, "bad n=%lld (0 <= n < 2^31 - 1)", (long long)n);
+    if (partials == nullptr || (n > 0 && (trials == nullptr || successes == nullptr || offset == nullptr ||
+                                          w == nullptr || d == nullptr || rhs == nullptr || g == nullptr ||
+                                          workspace == nullptr)))
+        return fail(NNGP_EINVAL, "null pointer argument");
+    const size_t need = nngp::binomial_newton_step_workspace_bytes(n);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    hipError_t e = nngp::binomial_newton_step_launch(n, trials, successes, offset, w, d, rhs, g, partials, workspace,
+                                                     (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, "binomial_newton_step launch") : NNGP_OK;
+}
+
+int nngp_binomial_check_partials(const double* p, int64_t* first_nonfinite, int64_t* first_negative_trials) {
+    if (p == nullptr) return fail(NNGP_EINVAL, "partials must be non-null");
+    if (first_nonfinite != nullptr) *first_nonfinite = p[2] > 0.0 ? (int64_t)p[2] - 1 : -1;
+    if (first_negative_trials != nullptr) *first_negative_trials = p[3] > 0.0 ? (int64_t)p[3] - 1 : -1;
+    if (p[3] > 0.0) return fail(NNGP_EINVAL, "negative trials at node %lld", (long long)p[3] - 1);
+    if (p[2] > 0.0) return fail(NNGP_EINVAL, "offset + w is not finite at node %lld", (long long)p[2] - 1);
+    return NNGP_OK;
+}
+
+int nngp_logistic_normal(int64_t n, const double* mu, const double* s, double* out, void* stream) {
+    if (n < 0 || n >= INT32_MAX) return fail(NNGP_EINVAL, "bad n=%lld (0 <= n < 2^31 - 1)", (long long)n);
+    if (n > 0 && (mu == nullptr || s == nullptr || out == nullptr)) return fail(NNGP_EINVAL, "null pointer argument");
+    hipError_t e = nngp::logistic_normal_launch(n, mu, s, out, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, "logistic_normal launch") : NNGP_OK;
 }
 
 size_t nngp_gibbs_pg_stats_workspace_bytes(int64_t n, int32_t p) {

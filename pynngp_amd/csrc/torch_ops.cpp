@@ -533,9 +533,54 @@ std::tuple<at::Tensor, at::Tensor> polya_gamma(const at::Tensor& trials, const a
     return {omega, status};
 }
 
+// ---------------------------------------------------------------- binomial latent posterior (Laplace)
+// One Newton step's link quantities per node: (d, rhs, g, partials); partials = (sum l, max |g|, first node with a
+// non-finite offset + w, + 1, or 0; first node with negative trials, + 1, or 0) -- faults are data, no synchronisation
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> binomial_newton_step(const at::Tensor& trials,
+                                                                                const at::Tensor& successes,
+                                                                                const at::Tensor& offset,
+                                                                                const at::Tensor& w) {
+    TORCH_CHECK(trials.is_cuda() && successes.is_cuda() && offset.is_cuda() && w.is_cuda(),
+                "trials, successes, offset and w must be ROCm GPU tensors (there is no CPU fallback)");
+    const at::OptionalDeviceGuard guard(w.device());
+    check_same_device(w, trials, "trials");
+    TORCH_CHECK(trials.scalar_type() == at::kInt && trials.dim() == 1 && trials.is_contiguous(),
+                "trials must be a contiguous int32 (n,) tensor");
+    const int64_t n = trials.size(0);
+    check_f64(successes, {n}, w, "successes");
+    check_f64(offset, {n}, w, "offset");
+    check_f64(w, {n}, w, "w");
+    auto d = at::empty_like(w), rhs = at::empty_like(w), g = at::empty_like(w);
+    auto partials = at::empty({4}, w.options());
+    auto ws = workspace((int64_t)nngp_binomial_newton_step_workspace_bytes(n), w);
+    check_rc(nngp_binomial_newton_step(n, trials.data_ptr<int32_t>(), successes.data_ptr<double>(),
+                                       offset.data_ptr<double>(), w.data_ptr<double>(), d.data_ptr<double>(),
+                                       rhs.data_ptr<double>(), g.data_ptr<double>(), partials.data_ptr<double>(),
+                                       ws.data_ptr(), (size_t)ws.nbytes(), stream(w)),
+             "nngp_binomial_newton_step");
+    return {d, rhs, g, partials};
+}
+
+// E[logistic(mu + s Z)], Z ~ N(0, 1), per element
+at::Tensor logistic_normal(const at::Tensor& mu, const at::Tensor& s) {
+    TORCH_CHECK(mu.is_cuda() && s.is_cuda(), "mu and s must be ROCm GPU tensors (there is no CPU fallback)");
+    const at::OptionalDeviceGuard guard(mu.device());
+    TORCH_CHECK(mu.scalar_type() == at::kDouble && mu.dim() == 1 && mu.is_contiguous(),
+                "mu must be a contiguous float64 (n,) tensor");
+    check_f64(s, {mu.size(0)}, mu, "s");
+    auto out = at::empty_like(mu);
+    check_rc(nngp_logistic_normal(mu.size(0), mu.data_ptr<double>(), s.data_ptr<double>(), out.data_ptr<double>(),
+                                  stream(mu)),
+             "nngp_logistic_normal");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
+    m.def("binomial_newton_step(Tensor trials, Tensor successes, Tensor offset, Tensor w) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
+    m.def("logistic_normal(Tensor mu, Tensor s) -> Tensor");
     m.def("precision_apply_batch(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, "
           "float sigma2, Tensor? d, Tensor x) -> Tensor");
     m.def("latent_cg_batch(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, float sigma2, "
@@ -573,6 +618,8 @@ TORCH_LIBRARY(nngp, m) {
 
 TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("polya_gamma", &polya_gamma);
+    m.impl("binomial_newton_step", &binomial_newton_step);
+    m.impl("logistic_normal", &logistic_normal);
     m.impl("knn_prior", &knn_prior);
     m.impl("knn_prior_rows", &knn_prior_rows);
     m.impl("knn_query", &knn_query);

@@ -32,6 +32,10 @@ for tracing.
         # trace (nrhs, max_iter, 2), NaN but for trace[c, k] = (alpha_k, beta_k) of the iterations column c completed
     torch.ops.nngp.polya_gamma(trials, c, seed, sweep) -> (omega, status)   # omega_i ~ PG(trials_i, c_i); status (1,)
         # int32: 0, or the smallest index + 1 whose draw is NaN (non-finite c, trials outside [0, 1024])
+    torch.ops.nngp.binomial_newton_step(trials, successes, offset, w) -> (d, rhs, g, partials)   # the binomial
+        # Laplace mode's link step: d = b p (1 - p), g = s - b p, rhs = d w + g at eta = offset + w; partials (4,) =
+        # (sum log-lik terms, max |g|, first non-finite node + 1 or 0, first negative-trials node + 1 or 0)
+    torch.ops.nngp.logistic_normal(mu, s) -> E[logistic(mu + s Z)], Z ~ N(0, 1)   # s = 0: logistic(mu)
 
 ``kind`` / ``algo`` are the integer codes of include/nngp.h (:func:`kind_code`, :func:`algo_code`);
 ``nu`` is the smoothness of the ``matern`` kind (0 < nu <= 50; ignored by the other kinds).
@@ -148,6 +152,14 @@ def _register_fakes() -> None:
     @fake("polya_gamma")
     def _(trials, c, seed, sweep):
         return torch.empty_like(c), c.new_empty((1,), dtype=torch.int32)
+
+    @fake("binomial_newton_step")
+    def _(trials, successes, offset, w):
+        return torch.empty_like(w), torch.empty_like(w), torch.empty_like(w), w.new_empty((4,))
+
+    @fake("logistic_normal")
+    def _(mu, s):
+        return torch.empty_like(mu)
 
 
 def kind_code(kind: str) -> int:
