@@ -763,6 +763,60 @@ int nngp_binomial_check_partials(const double *partials_host, int64_t *first_non
                                  int64_t *first_negative_trials);
 int nngp_logistic_normal(int64_t n, const double *mu, const double *s, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Solves with the NNGP factor, and what is composed from them (pynngp_amd/factor.py; the reference simulates its
+ * fields with a dense Cholesky and has no such call).  With B (n, m) and F the factors of nngp_bf_sweep,
+ *   forward     (I - B) x = b:     x_i = b_i + sum_{k = 0 .. m-1} B[i,k] x[nbr[i,k]]
+ *   transposed  (I - B)^T x = b:   x_j = b_j + sum over j's reverse list of B[i,k] x_i   (B in reverse-list order
+ *                                  from prep, as the second phase of nngp_precision_apply reads it)
+ * over any neighbour array whose valid indices are smaller than their row's index: S = T, and the reference-set
+ * layout whose leaves n_s .. n - 1 point into 0 .. n_s - 1.  A slot that is negative or >= its row's index is
+ * ignored as -1 (a reverse entry whose child is not above its node likewise).  Added within ABI revision 4
+ * (nothing earlier moved).
+ * nngp_factor_levels (HOST arrays, no GPU, once per neighbour set: the schedule does not depend on theta):
+ *   trans = 0: level(i) = 0 without a valid neighbour, else 1 + max level(nbr[i,k]); trans = 1: level(j) = 0 when
+ *   no row lists j, else 1 + max level(i) over the rows i that list j.  level_host (n,): each row's level;
+ *   rows_host (n,): the rows sorted by (level, index); level_off_host (n + 1 entries of room, n_levels + 1
+ *   written): level l is rows_host[level_off_host[l] .. level_off_host[l + 1]); *n_levels: the depth (0 for n = 0).
+ *   The same shape of record as nngp_gibbs_w_sweep's member_rows / color_off_host.  NNGP_EINVAL for trans outside
+ *   {0, 1}, m outside 1 .. NNGP_MAX_M, n < 0.
+ * nngp_factor_solve_batch: x = (I - B)^-1 b (trans = 0) or (I - B)^-T b (trans = 1); b, x (n, nrhs) row-major,
+ *   1 <= nrhs <= NNGP_LATENT_MAX_RHS, and b and x may be the same buffer.  rows (DEVICE (n,)) and level_off (DEVICE
+ *   (n_levels + 1,)) are copies of nngp_factor_levels' outputs for the same trans; level_off_host is the host
+ *   copy, which steers the launches.  A level of more than fuse_width rows is one launch; a run of consecutive
+ *   levels of at most fuse_width rows each is one launch of a single workgroup that walks them with a workgroup
+ *   barrier in between (0 <= fuse_width <= NNGP_FACTOR_MAX_FUSE_WIDTH; 0: one launch per level).  Stream-ordered
+ *   launches only, no atomics, no graph, no workspace; nngp_factor_launch_counts (host) gives their number.
+ *   Every sum runs in slot order (reverse-list order), b first, one fused multiply-add per slot, in every
+ *   column: x is bit-identical for every fuse_width and column c for every nrhs, whatever the other columns hold.
+ *   off, rev_j and prep are read by the transposed solve only (NULL otherwise); rev_k is accepted for symmetry.
+ * nngp_factor_cov_apply_batch: out = sigma2 (I - B)^-1 F (I - B)^-T v, the covariance of the NNGP prior (the
+ *   inverse of nngp_precision_apply's matrix with d = NULL): a transposed solve, a scaling by sigma2 F, a forward
+ *   solve, all in out; v and out may alias.  Both schedules are passed (suffix _f: trans = 0, _t: trans = 1).
+ * nngp_factor_prior_draw_batch: out = (I - B)^-1 (sigma2 F)^1/2 z, nrhs draws from the prior.  z: (n, nrhs)
+ *   standard normals, or NULL: column c is nngp_gibbs_normals(n, seed, sweep = draw0 + c), so draw number k is the
+ *   same field in whatever batch it is drawn.  z and out may alias.
+ * ------------------------------------------------------------------------- */
+#define NNGP_FACTOR_MAX_FUSE_WIDTH 1024
+int nngp_factor_levels(const int32_t *nbr_host, int64_t n, int32_t m, int32_t trans, int32_t *level_host,
+                       int32_t *rows_host, int32_t *level_off_host, int64_t *n_levels);
+int nngp_factor_launch_counts(const int32_t *level_off_host, int64_t n_levels, int32_t fuse_width, int64_t *n_wide,
+                              int64_t *n_runs);
+int nngp_factor_solve_batch(const int32_t *nbr, const double *B, const int32_t *off, const int32_t *rev_j,
+                            const int32_t *rev_k, const void *prep, const int32_t *rows, const int32_t *level_off,
+                            const int32_t *level_off_host, int64_t n_levels, int64_t n, int32_t m, int32_t nrhs,
+                            int32_t trans, int32_t fuse_width, const double *b, double *x, void *stream);
+int nngp_factor_cov_apply_batch(const int32_t *nbr, const double *B, const double *F, const int32_t *off,
+                                const int32_t *rev_j, const int32_t *rev_k, const void *prep, const int32_t *rows_f,
+                                const int32_t *level_off_f, const int32_t *level_off_f_host, int64_t n_levels_f,
+                                const int32_t *rows_t, const int32_t *level_off_t, const int32_t *level_off_t_host,
+                                int64_t n_levels_t, int64_t n, int32_t m, double sigma2, int32_t nrhs,
+                                int32_t fuse_width, const double *v, double *out, void *stream);
+int nngp_factor_prior_draw_batch(const int32_t *nbr, const double *B, const double *F, const int32_t *rows,
+                                 const int32_t *level_off, const int32_t *level_off_host, int64_t n_levels, int64_t n,
+                                 int32_t m, double sigma2, int32_t nrhs, int32_t fuse_width, const double *z,
+                                 uint64_t seed, uint64_t draw0, double *out, void *stream);
+
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident
  * partials of a finished sweep, returns NNGP_OK, NNGP_ENOTPD with *first_bad_row = the

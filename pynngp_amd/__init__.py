@@ -14,6 +14,7 @@ from .gibbs_sharded import ShardedSeqNNGP  # noqa: F401
 from .latent import LatentPosterior, LogDet, SolveInfo, lanczos_quadrature  # noqa: F401
 from .gibbs_binomial import BinomialSeqNNGP, polya_gamma  # noqa: F401
 from .latent_binomial import BinomialLatentPosterior, ModeInfo  # noqa: F401
+from .factor import NNGPFactor  # noqa: F401
 
 __version__ = "0.3.0"
 

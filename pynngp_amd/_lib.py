@@ -101,6 +101,11 @@ SYMBOLS = (
     "nngp_binomial_newton_step",
     "nngp_binomial_check_partials",
     "nngp_logistic_normal",
+    "nngp_factor_levels",
+    "nngp_factor_launch_counts",
+    "nngp_factor_solve_batch",
+    "nngp_factor_cov_apply_batch",
+    "nngp_factor_prior_draw_batch",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -114,6 +119,7 @@ CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
 BLOCKS_MAX_M = 32  # nngp_bf_sweep_blocks: 1 <= m <= 32
 LATENT_MAX_RHS = 8  # NNGP_LATENT_MAX_RHS: right-hand sides per batched latent call
 PG_MAX_TRIALS = 1024  # NNGP_PG_MAX_TRIALS: binomial trials per location of a Polya-Gamma draw
+FACTOR_MAX_FUSE_WIDTH = 1024  # NNGP_FACTOR_MAX_FUSE_WIDTH: rows per level the factor solve's narrow-run kernel takes
 
 
 class NNGPExtensionError(RuntimeError):
@@ -305,6 +311,17 @@ def load() -> ctypes.CDLL:
     lib.nngp_latent_ref_leaves_batch.restype = ctypes.c_int
     lib.nngp_latent_rows_dot2_batch.argtypes = [P, P, P, I64, I64, I32, I32, P, P, P, P]
     lib.nngp_latent_rows_dot2_batch.restype = ctypes.c_int
+    lib.nngp_factor_levels.argtypes = [P, I64, I32, I32, P, P, P, P]
+    lib.nngp_factor_levels.restype = ctypes.c_int
+    lib.nngp_factor_launch_counts.argtypes = [P, I64, I32, P, P]
+    lib.nngp_factor_launch_counts.restype = ctypes.c_int
+    lib.nngp_factor_solve_batch.argtypes = [P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I32, P, P, P]
+    lib.nngp_factor_solve_batch.restype = ctypes.c_int
+    lib.nngp_factor_cov_apply_batch.argtypes = [P, P, P, P, P, P, P, P, P, P, I64, P, P, P, I64, I64, I32, D, I32, I32,
+                                                P, P, P]
+    lib.nngp_factor_cov_apply_batch.restype = ctypes.c_int
+    lib.nngp_factor_prior_draw_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, I32, I32, P, U64, U64, P, P]
+    lib.nngp_factor_prior_draw_batch.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1711,3 +1728,138 @@ def latent_rows_dot2_batch(nbr: torch.Tensor, B: torch.Tensor, dB: torch.Tensor,
     _check(load().nngp_latent_rows_dot2_batch(_ptr(nbr), _ptr(B), _ptr(dB), n, n_s, m, nrhs, _ptr(x), _ptr(p), _ptr(q),
                                               _stream(dev)), "nngp_latent_rows_dot2_batch")
     return p, q
+
+
+# -- solves with the NNGP factor (nngp_factor_*) ------------------------------------------------------------
+class FactorSchedule:
+    """One level schedule of :func:`factor_levels` with its device copies: ``level`` (n,) each row's level,
+    ``rows`` (n,) the rows sorted by (level, index), ``level_off`` (depth + 1,) the levels' offsets into it (host
+    numpy int32), ``rows_dev`` / ``level_off_dev`` the device tensors the solve reads, ``depth`` the level count."""
+
+    def __init__(self, level, rows, level_off, device):
+        self.level, self.rows, self.level_off = level, rows, level_off
+        self.depth = level_off.shape[0] - 1
+        self.rows_dev = torch.from_numpy(rows).to(device)
+        self.level_off_dev = torch.from_numpy(level_off).to(device)
+
+    def launch_counts(self, fuse_width: int):
+        """``(wide levels, narrow runs)``: the launches of one solve at ``fuse_width`` (nngp_factor_launch_counts)."""
+        wide, runs = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(load().nngp_factor_launch_counts(self.level_off.ctypes.data_as(ctypes.c_void_p), self.depth,
+                                                int(fuse_width), ctypes.byref(wide), ctypes.byref(runs)),
+               "nngp_factor_launch_counts")
+        return int(wide.value), int(runs.value)
+
+    def _args(self):
+        return [_ptr(self.rows_dev), _ptr(self.level_off_dev), self.level_off.ctypes.data_as(ctypes.c_void_p),
+                self.depth]
+
+
+def factor_levels(nbr_host, trans: bool = False, device=None):
+    """The level schedule of the factor's forward (``trans`` False) or transposed solve for the HOST neighbour array
+    ``nbr_host`` (int32 (n, m), -1 padded; a slot that is negative or >= its row's index counts as -1)
+    (nngp_factor_levels; no GPU).  Returns ``(level, rows, level_off)`` as numpy int32 arrays, or, with ``device``,
+    a :class:`FactorSchedule` holding them and their device copies."""
+    nb = np.ascontiguousarray(nbr_host, dtype=np.int32)
+    if nb.ndim != 2:
+        raise ValueError(f"nbr_host must be int32 (n, m), got {nb.shape}")
+    n, m = nb.shape
+    level, rows = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    level_off = np.empty(n + 1, dtype=np.int32)
+    depth = ctypes.c_int64(0)
+    as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    _check(load().nngp_factor_levels(as_p(nb), n, m, int(trans), as_p(level), as_p(rows), as_p(level_off),
+                                     ctypes.byref(depth)), "nngp_factor_levels")
+    level_off = np.ascontiguousarray(level_off[:depth.value + 1])
+    if device is None:
+        return level, rows, level_off
+    return FactorSchedule(level, rows, level_off, device)
+
+
+def _factor_cols(t, name, n):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != n
+            or not 1 <= t.shape[1] <= LATENT_MAX_RHS or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float64 ({n}, nrhs) tensor with 1 <= nrhs <= {LATENT_MAX_RHS}")
+    return t.shape[1]
+
+
+def _factor_geom(nbr, B, F=None):
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not nbr.is_contiguous():
+        raise ValueError(f"nbr must be contiguous int32 (n, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    n, m = nbr.shape
+    if B.dtype != torch.float64 or tuple(B.shape) != (n, m) or not B.is_contiguous():
+        raise ValueError(f"B must be contiguous float64 ({n}, {m}), got {B.dtype} {tuple(B.shape)}")
+    if F is not None and (F.dtype != torch.float64 or tuple(F.shape) != (n,) or not F.is_contiguous()):
+        raise ValueError(f"F must be contiguous float64 ({n},), got {F.dtype} {tuple(F.shape)}")
+    return n, m
+
+
+def _factor_sched(s, n, dev):
+    if not isinstance(s, FactorSchedule) or s.rows.shape[0] != n or s.rows_dev.device != dev:
+        raise ValueError(f"a FactorSchedule of {n} rows on {dev} is needed (factor_levels(..., device=))")
+    return s._args()
+
+
+def factor_solve_batch(nbr: torch.Tensor, B: torch.Tensor, off, rev_j, rev_k, prep, sched: FactorSchedule,
+                       b: torch.Tensor, trans: bool = False, fuse_width: int = 0,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x = (I - B)^-1 b (``trans`` False) or (I - B)^-T b for ``b`` (n, nrhs) (nngp_factor_solve_batch).  ``sched``:
+    :func:`factor_levels` of the same ``trans``.  ``out`` may be ``b``.  The transposed solve reads the reverse
+    lists and ``prep`` (:func:`reverse_neighbors`, :func:`gibbs_prepare`); the forward solve takes None for them."""
+    n, m = _factor_geom(nbr, B)
+    nrhs = _factor_cols(b, "b", n)
+    dev = _require_gpu(nbr, B, b, out, off, rev_j, rev_k, prep)
+    if trans and (off is None or rev_j is None or prep is None):
+        raise ValueError("the transposed solve needs off, rev_j and prep")
+    if out is None:
+        out = torch.empty_like(b)
+    elif _factor_cols(out, "out", n) != nrhs:
+        raise ValueError("out must have b's shape")
+    _check(load().nngp_factor_solve_batch(_ptr(nbr), _ptr(B), _ptr(off), _ptr(rev_j), _ptr(rev_k), _ptr(prep),
+                                          *_factor_sched(sched, n, dev), n, m, nrhs, int(bool(trans)),
+                                          int(fuse_width), _ptr(b), _ptr(out), _stream(dev)),
+           "nngp_factor_solve_batch")
+    return out
+
+
+def factor_cov_apply_batch(nbr: torch.Tensor, B: torch.Tensor, F: torch.Tensor, off, rev_j, rev_k, prep,
+                           sched_f: FactorSchedule, sched_t: FactorSchedule, sigma2: float, v: torch.Tensor,
+                           fuse_width: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = sigma2 (I - B)^-1 F (I - B)^-T v for ``v`` (n, nrhs) (nngp_factor_cov_apply_batch): the covariance of the
+    NNGP prior whose precision :func:`precision_apply_batch` applies with ``d`` None."""
+    n, m = _factor_geom(nbr, B, F)
+    nrhs = _factor_cols(v, "v", n)
+    dev = _require_gpu(nbr, B, F, off, rev_j, rev_k, prep, v, out)
+    if out is None:
+        out = torch.empty_like(v)
+    elif _factor_cols(out, "out", n) != nrhs:
+        raise ValueError("out must have v's shape")
+    _check(load().nngp_factor_cov_apply_batch(_ptr(nbr), _ptr(B), _ptr(F), _ptr(off), _ptr(rev_j), _ptr(rev_k),
+                                              _ptr(prep), *_factor_sched(sched_f, n, dev),
+                                              *_factor_sched(sched_t, n, dev), n, m, float(sigma2), nrhs,
+                                              int(fuse_width), _ptr(v), _ptr(out), _stream(dev)),
+           "nngp_factor_cov_apply_batch")
+    return out
+
+
+def factor_prior_draw_batch(nbr: torch.Tensor, B: torch.Tensor, F: torch.Tensor, sched_f: FactorSchedule,
+                            sigma2: float, nrhs: int, fuse_width: int = 0, z: Optional[torch.Tensor] = None,
+                            seed: int = 0, draw0: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n, nrhs) draws w = (I - B)^-1 (sigma2 F)^1/2 z from the NNGP prior (nngp_factor_prior_draw_batch); ``z``
+    (n, nrhs) standard normals, or None: column c is :func:`gibbs_normals` of (seed, sweep = draw0 + c)."""
+    n, m = _factor_geom(nbr, B, F)
+    nrhs = int(nrhs)
+    if not 1 <= nrhs <= LATENT_MAX_RHS:
+        raise ValueError(f"nrhs={nrhs} outside [1, {LATENT_MAX_RHS}]")
+    if z is not None and _factor_cols(z, "z", n) != nrhs:
+        raise ValueError(f"z must have {nrhs} columns")
+    dev = _require_gpu(nbr, B, F, z, out)
+    if out is None:
+        out = torch.empty((n, nrhs), dtype=torch.float64, device=dev)
+    elif _factor_cols(out, "out", n) != nrhs:
+        raise ValueError(f"out must be ({n}, {nrhs})")
+    _check(load().nngp_factor_prior_draw_batch(_ptr(nbr), _ptr(B), _ptr(F), *_factor_sched(sched_f, n, dev), n, m,
+                                               float(sigma2), nrhs, int(fuse_width), _ptr(z),
+                                               int(seed) & (2 ** 64 - 1), int(draw0), _ptr(out), _stream(dev)),
+           "nngp_factor_prior_draw_batch")
+    return out

@@ -14,6 +14,8 @@
 #include "bf_dphi.h"
 #include "latent.h"
 #include "latent_binomial.h"
+#include "factor.h"
+#include "factor_levels.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1271,6 +1273,131 @@ int nngp_knn_query(const double* ref, int64_t n_ref, int32_t dim, const double* 
     hipError_t e = nngp::knn_launch(false, ref, n_ref, k, query, 0, n_query, nullptr, nbr, workspace, plan,
                                     (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "knn_query launch");
+    return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- NNGP factor solves (factor_solve.hip)
+int nngp_factor_levels(const int32_t* nbr_host, int64_t n, int32_t m, int32_t trans, int32_t* level_host,
+                       int32_t* rows_host, int32_t* level_off_host, int64_t* n_levels) {
+    if (trans != 0 && trans != 1) return fail(NNGP_EINVAL, "trans must be 0 or 1 (got %d)", trans);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
+    if (n > INT32_MAX || n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    if (level_off_host == nullptr || n_levels == nullptr ||
+        (n > 0 && (nbr_host == nullptr || level_host == nullptr || rows_host == nullptr)))
+        return fail(NNGP_EINVAL, "nbr_host, level_host, rows_host, level_off_host and n_levels must be non-null");
+    *n_levels = nngp::factor_levels_build(nbr_host, n, m, trans, level_host, rows_host, level_off_host);
+    return NNGP_OK;
+}
+
+static int factor_schedule(const int32_t* rows, const int32_t* level_off, const int32_t* level_off_host,
+                           int64_t n_levels, int64_t n, int32_t fuse_width, nngp::FactorSchedule* sc) {
+    if (fuse_width < 0 || fuse_width > NNGP_FACTOR_MAX_FUSE_WIDTH)
+        return fail(NNGP_EINVAL, "fuse_width=%d outside [0, %d]", fuse_width, NNGP_FACTOR_MAX_FUSE_WIDTH);
+    if (n_levels < 0 || n_levels > n) return fail(NNGP_EINVAL, "need 0 <= n_levels <= n (got %lld)", (long long)n_levels);
+    if (level_off_host == nullptr || (n > 0 && (rows == nullptr || level_off == nullptr)))
+        return fail(NNGP_EINVAL, "rows, level_off and level_off_host must be non-null");
+    if (level_off_host[0] != 0 || level_off_host[n_levels] != n)
+        return fail(NNGP_EINVAL, "level_off_host must run from 0 to n over n_levels levels");
+    *sc = nngp::FactorSchedule{rows, level_off, level_off_host, n_levels};
+    return NNGP_OK;
+}
+
+static int factor_sizes(int64_t n, int32_t m, int32_t nrhs) {
+    if (bad_nrhs(nrhs)) return fail_nrhs(nrhs);
+    if (n < 0) return fail(NNGP_EINVAL, "bad n=%lld", (long long)n);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n * (int64_t)m > INT32_MAX) return fail(NNGP_EUNSUP, "n*m must be < 2^31");
+    return NNGP_OK;
+}
+
+static int factor_geom(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                       const void* prep, int64_t n, int32_t m, bool trans, nngp::FactorGeom* g) {
+    if (n > 0 && (nbr == nullptr || B == nullptr)) return fail(NNGP_EINVAL, "nbr and B must be non-null");
+    if (trans && n > 0 && (off == nullptr || rev_j == nullptr || prep == nullptr))
+        return fail(NNGP_EINVAL, "the transposed solve needs off, rev_j and prep");
+    if (trans && ((uintptr_t)prep & 255) != 0) return fail(NNGP_EINVAL, "prep must be 256-byte aligned");
+    *g = nngp::FactorGeom{nbr, B, off, rev_j, trans && prep != nullptr ? nngp::latent_prep_view(prep, n, m).Brev : nullptr,
+                          n, m};
+    return NNGP_OK;
+}
+
+int nngp_factor_launch_counts(const int32_t* level_off_host, int64_t n_levels, int32_t fuse_width, int64_t* n_wide,
+                              int64_t* n_runs) {
+    if (level_off_host == nullptr || n_wide == nullptr || n_runs == nullptr || n_levels < 0)
+        return fail(NNGP_EINVAL, "level_off_host, n_wide and n_runs must be non-null and n_levels >= 0");
+    if (fuse_width < 0 || fuse_width > NNGP_FACTOR_MAX_FUSE_WIDTH)
+        return fail(NNGP_EINVAL, "fuse_width=%d outside [0, %d]", fuse_width, NNGP_FACTOR_MAX_FUSE_WIDTH);
+    nngp::factor_launch_counts(nngp::FactorSchedule{nullptr, nullptr, level_off_host, n_levels}, fuse_width, n_wide,
+                               n_runs);
+    return NNGP_OK;
+}
+
+int nngp_factor_solve_batch(const int32_t* nbr, const double* B, const int32_t* off, const int32_t* rev_j,
+                            const int32_t* rev_k, const void* prep, const int32_t* rows, const int32_t* level_off,
+                            const int32_t* level_off_host, int64_t n_levels, int64_t n, int32_t m, int32_t nrhs,
+                            int32_t trans, int32_t fuse_width, const double* b, double* x, void* stream) {
+    (void)rev_k;
+    if (trans != 0 && trans != 1) return fail(NNGP_EINVAL, "trans must be 0 or 1 (got %d)", trans);
+    int rc = factor_sizes(n, m, nrhs);
+    if (rc != NNGP_OK) return rc;
+    if (n > 0 && (b == nullptr || x == nullptr)) return fail(NNGP_EINVAL, "b and x must be non-null");
+    nngp::FactorSchedule sc;
+    if ((rc = factor_schedule(rows, level_off, level_off_host, n_levels, n, fuse_width, &sc)) != NNGP_OK) return rc;
+    nngp::FactorGeom g;
+    if ((rc = factor_geom(nbr, B, off, rev_j, prep, n, m, trans != 0, &g)) != NNGP_OK) return rc;
+    hipError_t e = nngp::factor_solve_launch(g, sc, nrhs, trans, fuse_width, b, x, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "factor_solve_batch launch");
+    return NNGP_OK;
+}
+
+static int factor_sigma2(double sigma2) {
+    if (!(sigma2 > 0.0) || !(sigma2 <= 1.7976931348623157e308))
+        return fail(NNGP_EINVAL, "sigma2 must be positive and finite (got %g)", sigma2);
+    return NNGP_OK;
+}
+
+int nngp_factor_cov_apply_batch(const int32_t* nbr, const double* B, const double* F, const int32_t* off,
+                                const int32_t* rev_j, const int32_t* rev_k, const void* prep, const int32_t* rows_f,
+                                const int32_t* level_off_f, const int32_t* level_off_f_host, int64_t n_levels_f,
+                                const int32_t* rows_t, const int32_t* level_off_t, const int32_t* level_off_t_host,
+                                int64_t n_levels_t, int64_t n, int32_t m, double sigma2, int32_t nrhs,
+                                int32_t fuse_width, const double* v, double* out, void* stream) {
+    (void)rev_k;
+    int rc = factor_sizes(n, m, nrhs);
+    if (rc != NNGP_OK) return rc;
+    if ((rc = factor_sigma2(sigma2)) != NNGP_OK) return rc;
+    if (n > 0 && (F == nullptr || v == nullptr || out == nullptr))
+        return fail(NNGP_EINVAL, "F, v and out must be non-null");
+    nngp::FactorSchedule sf, st;
+    if ((rc = factor_schedule(rows_f, level_off_f, level_off_f_host, n_levels_f, n, fuse_width, &sf)) != NNGP_OK) return rc;
+    if ((rc = factor_schedule(rows_t, level_off_t, level_off_t_host, n_levels_t, n, fuse_width, &st)) != NNGP_OK) return rc;
+    nngp::FactorGeom g;
+    if ((rc = factor_geom(nbr, B, off, rev_j, prep, n, m, true, &g)) != NNGP_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = nngp::factor_solve_launch(g, st, nrhs, 1, fuse_width, v, out, s);
+    if (e == hipSuccess) e = nngp::factor_scale_launch(F, sigma2, false, n, nrhs, out, 0, 0, out, s);
+    if (e == hipSuccess) e = nngp::factor_solve_launch(g, sf, nrhs, 0, fuse_width, out, out, s);
+    if (e != hipSuccess) return hip_fail(e, "factor_cov_apply_batch launch");
+    return NNGP_OK;
+}
+
+int nngp_factor_prior_draw_batch(const int32_t* nbr, const double* B, const double* F, const int32_t* rows,
+                                 const int32_t* level_off, const int32_t* level_off_host, int64_t n_levels, int64_t n,
+                                 int32_t m, double sigma2, int32_t nrhs, int32_t fuse_width, const double* z,
+                                 uint64_t seed, uint64_t draw0, double* out, void* stream) {
+    int rc = factor_sizes(n, m, nrhs);
+    if (rc != NNGP_OK) return rc;
+    if ((rc = factor_sigma2(sigma2)) != NNGP_OK) return rc;
+    if (n > 0 && (F == nullptr || out == nullptr)) return fail(NNGP_EINVAL, "F and out must be non-null");
+    nngp::FactorSchedule sc;
+    if ((rc = factor_schedule(rows, level_off, level_off_host, n_levels, n, fuse_width, &sc)) != NNGP_OK) return rc;
+    nngp::FactorGeom g;
+    if ((rc = factor_geom(nbr, B, nullptr, nullptr, nullptr, n, m, false, &g)) != NNGP_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = nngp::factor_scale_launch(F, sigma2, true, n, nrhs, z, seed, draw0, out, s);
+    if (e == hipSuccess) e = nngp::factor_solve_launch(g, sc, nrhs, 0, fuse_width, out, out, s);
+    if (e != hipSuccess) return hip_fail(e, "factor_prior_draw_batch launch");
     return NNGP_OK;
 }
 

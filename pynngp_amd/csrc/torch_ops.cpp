@@ -575,9 +575,85 @@ at::Tensor logistic_normal(const at::Tensor& mu, const at::Tensor& s) {
     return out;
 }
 
+// ---------------------------------------------------------------- solves with the NNGP factor
+// one level schedule of nngp_factor_levels: rows / level_off on the device, level_off_host a CPU copy
+struct FactorSched {
+    const int32_t *rows, *level_off, *level_off_host;
+    int64_t n_levels;
+};
+FactorSched check_sched(const at::Tensor& nbr, const at::Tensor& rows, const at::Tensor& level_off,
+                        const at::Tensor& level_off_host) {
+    const int64_t n = nbr.size(0);
+    TORCH_CHECK(rows.scalar_type() == at::kInt && rows.dim() == 1 && rows.size(0) == n && rows.is_contiguous(),
+                "rows must be a contiguous int32 (n,) tensor");
+    check_same_device(nbr, rows, "rows");
+    TORCH_CHECK(level_off_host.device().is_cpu() && level_off_host.scalar_type() == at::kInt &&
+                    level_off_host.dim() == 1 && level_off_host.size(0) >= 1 && level_off_host.is_contiguous(),
+                "level_off_host must be a contiguous CPU int32 (n_levels + 1,) tensor");
+    TORCH_CHECK(level_off.scalar_type() == at::kInt && level_off.dim() == 1 &&
+                    level_off.size(0) == level_off_host.size(0) && level_off.is_contiguous(),
+                "level_off must be a contiguous int32 tensor of level_off_host's length");
+    check_same_device(nbr, level_off, "level_off");
+    return {rows.data_ptr<int32_t>(), level_off.data_ptr<int32_t>(), level_off_host.data_ptr<int32_t>(),
+            level_off_host.size(0) - 1};
+}
+
+// x = (I - B)^-1 b, or (I - B)^-T b for trans (nngp_factor_solve_batch); b (n, nrhs)
+at::Tensor factor_solve(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& off, const at::Tensor& rev_j,
+                        const at::Tensor& rev_k, const at::Tensor& prep, const at::Tensor& rows,
+                        const at::Tensor& level_off, const at::Tensor& level_off_host, bool trans, int64_t fuse_width,
+                        const at::Tensor& b) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    const FactorSched sc = check_sched(nbr, rows, level_off, level_off_host);
+    const int64_t nrhs = check_batch(b, nbr, "b");
+    TORCH_CHECK(fuse_width >= 0 && fuse_width <= NNGP_FACTOR_MAX_FUSE_WIDTH, "fuse_width outside [0, ",
+                NNGP_FACTOR_MAX_FUSE_WIDTH, "]");
+    auto x = at::empty_like(b);
+    check_rc(nngp_factor_solve_batch(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), off.data_ptr<int32_t>(),
+                                     rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(), prep.data_ptr(), sc.rows,
+                                     sc.level_off, sc.level_off_host, sc.n_levels, n, (int32_t)m, (int32_t)nrhs,
+                                     trans ? 1 : 0, (int32_t)fuse_width, b.data_ptr<double>(), x.data_ptr<double>(),
+                                     stream(nbr)),
+             "nngp_factor_solve_batch");
+    return x;
+}
+
+// out = sigma2 (I - B)^-1 F (I - B)^-T v (nngp_factor_cov_apply_batch); v (n, nrhs)
+at::Tensor factor_cov_apply(const at::Tensor& nbr, const at::Tensor& B, const at::Tensor& F, const at::Tensor& off,
+                            const at::Tensor& rev_j, const at::Tensor& rev_k, const at::Tensor& prep,
+                            const at::Tensor& rows_f, const at::Tensor& level_off_f, const at::Tensor& level_off_f_host,
+                            const at::Tensor& rows_t, const at::Tensor& level_off_t, const at::Tensor& level_off_t_host,
+                            double sigma2, int64_t fuse_width, const at::Tensor& v) {
+    check_latent(nbr, B, off, rev_j, rev_k, prep);
+    const at::OptionalDeviceGuard guard(nbr.device());
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(F, {n}, nbr, "F");
+    const FactorSched sf = check_sched(nbr, rows_f, level_off_f, level_off_f_host);
+    const FactorSched st = check_sched(nbr, rows_t, level_off_t, level_off_t_host);
+    const int64_t nrhs = check_batch(v, nbr, "v");
+    TORCH_CHECK(fuse_width >= 0 && fuse_width <= NNGP_FACTOR_MAX_FUSE_WIDTH, "fuse_width outside [0, ",
+                NNGP_FACTOR_MAX_FUSE_WIDTH, "]");
+    auto out = at::empty_like(v);
+    check_rc(nngp_factor_cov_apply_batch(nbr.data_ptr<int32_t>(), B.data_ptr<double>(), F.data_ptr<double>(),
+                                         off.data_ptr<int32_t>(), rev_j.data_ptr<int32_t>(), rev_k.data_ptr<int32_t>(),
+                                         prep.data_ptr(), sf.rows, sf.level_off, sf.level_off_host, sf.n_levels,
+                                         st.rows, st.level_off, st.level_off_host, st.n_levels, n, (int32_t)m, sigma2,
+                                         (int32_t)nrhs, (int32_t)fuse_width, v.data_ptr<double>(),
+                                         out.data_ptr<double>(), stream(nbr)),
+             "nngp_factor_cov_apply_batch");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
+    m.def("factor_solve(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, Tensor rows, "
+          "Tensor level_off, Tensor level_off_host, bool trans, int fuse_width, Tensor b) -> Tensor");
+    m.def("factor_cov_apply(Tensor nbr, Tensor B, Tensor F, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, "
+          "Tensor rows_f, Tensor level_off_f, Tensor level_off_f_host, Tensor rows_t, Tensor level_off_t, "
+          "Tensor level_off_t_host, float sigma2, int fuse_width, Tensor v) -> Tensor");
     m.def("binomial_newton_step(Tensor trials, Tensor successes, Tensor offset, Tensor w) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("logistic_normal(Tensor mu, Tensor s) -> Tensor");
@@ -635,6 +711,8 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("precision_apply", &precision_apply);
     m.impl("latent_cg", &latent_cg);
     m.impl("precision_apply_batch", &precision_apply_batch);
+    m.impl("factor_solve", &factor_solve);
+    m.impl("factor_cov_apply", &factor_cov_apply);
     m.impl("latent_cg_batch", &latent_cg_batch);
     m.impl("latent_cg_batch_trace", &latent_cg_batch_trace);
 }

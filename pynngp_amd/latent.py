@@ -202,6 +202,8 @@ class LatentPosterior:
         self.n, self.p = n, X_host.shape[1]
         to = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731
         self._ref = s_host is not None  # the caller gave ref=: nothing below the constructor depends on it
+        self._prior_in = (c_host, s_host, nbr)  # what sample_prior's NNGPFactor is built from, on first use
+        self._prior = None
         if self._ref:
             coords0, nbr0, n_s, node_of_t = self._ref_nodes(to(c_host), to(s_host))
         else:  # S = T: the reference set is the data locations, and there is no leaf
@@ -576,6 +578,24 @@ class LatentPosterior:
                                     self._leaf_normals(k0, kc, n_draws, seed, z3, self.LEAF_STREAM))
             out[k0:k0 + W.shape[1]] = W[rows].t().cpu().numpy()
         return out
+
+    def sample_prior(self, n_draws: int, seed: int = 0, where: str = "data") -> np.ndarray:
+        """``(n_draws, N)`` draws of w from the NNGP PRIOR at ``cov`` (no data enter): w = (I - B)^-1 (sigma2 F)^1/2 z
+        by the level-scheduled triangular solve of :class:`pynngp_amd.NNGPFactor`, built on first use on the same
+        locations, neighbour-set rule and reference set, in the caller's order (not the Z-order storage, whose
+        neighbours do not precede their rows).  With a reference set the leaves are drawn through the same DAG;
+        ``where`` as :meth:`mean`.  Philox normals keyed by (``seed``, draw, node)."""
+        self._check_where(where)
+        from .factor import NNGPFactor
+
+        c_host, s_host, nbr = self._prior_in
+        if self._prior is None:
+            self._prior = NNGPFactor(c_host, self.cov, m=self.m, nbr=nbr, device=self.device, ref=s_host)
+        elif self._prior.cov != self.cov:
+            self._prior.update(self.cov)
+        if where == "data":
+            return self._prior.sample_prior_at_data(n_draws, seed=seed)
+        return self._prior.sample_prior(n_draws, seed=seed)[:, :self.n_s]
 
     # -- posterior uncertainty ---------------------------------------------------
     def marginal_variance(self, n_draws: int = 64, seed: int = 0, z=None, beta=None, rtol: float = 1e-8,

@@ -946,6 +946,68 @@ class NNGP:
         :meth:`latent_posterior`); arguments as :meth:`latent_mean`."""
         return np.sqrt(self._latent_posterior(cov, mean).marginal_variance(n_draws, seed=seed))
 
+    # -- simulation from the prior ------------------------------------------------
+    NOISE_STREAM = 1 << 41  # Philox sweep index of simulate's noise for draw k: NOISE_STREAM + k (no draw's stream)
+
+    def prior_factor(self, cov: Optional[Covariance] = None):
+        """The :class:`pynngp_amd.NNGPFactor` of this instance at ``cov`` (default ``self.cov``): the factor of the
+        NNGP prior on ``s`` with the data locations outside it as leaves, for triangular solves, covariance
+        products and prior draws.  'S=T' reuses the neighbour sets held here.  Kept between calls: a new theta is
+        one ``update``."""
+        from .factor import NNGPFactor, _check_cov
+
+        cv = _check_cov(self.cov if cov is None else cov)
+        held = getattr(self, "_factor", None)
+        key = self.nbr if self._same_sets() else self.s
+        if held is not None and held[0] is key:
+            if held[1].cov != cv:
+                held[1].update(cv)
+            return held[1]
+        if self._same_sets():
+            f = NNGPFactor(self.t, cv, m=self.m, nbr=self.nbr, device=self.device)
+        else:
+            f = NNGPFactor(self.t, cv, m=self.m, device=self.device, ref=self.s)
+        self._factor = (key, f)
+        return f
+
+    def simulate(self, n_draws: int = 1, seed: int = 0, cov: Optional[Covariance] = None, beta=None, X=None,
+                 noise: bool = True) -> np.ndarray:
+        """``(n_draws, N)`` simulated responses y = X beta + w + e on this instance's own locations ``t``: w a draw
+        from the NNGP prior at ``cov`` (default ``self.cov``) by :meth:`pynngp_amd.NNGPFactor.sample_prior` -- a
+        level-scheduled triangular solve, no dense Cholesky, so it serves the sizes the sweeps serve -- and
+        e_i ~ N(0, tau2 eps_i^2) (``eps`` when it is one positive sigma per location, else 1; ``noise=False`` or
+        tau2 = 0: none).  ``X`` (N, p) with ``beta`` (p,), or a scalar ``beta`` as the constant mean; default 0.
+        Philox normals keyed by ``seed``: one seed repeats bit for bit, and draw k does not depend on ``n_draws``."""
+        f = self.prior_factor(cov)
+        n_draws = int(n_draws)
+        W = f._draws(n_draws, seed, None)[f._node_of_t_dev]  # (N, n_draws) on the device
+        n = W.shape[0]
+        if noise and f.cov.tau2 > 0:
+            sd = torch.full((n,), math.sqrt(f.cov.tau2), dtype=torch.float64, device=self.device)
+            if self.eps is not None:
+                ev = np.asarray(self.eps, dtype=np.float64)
+                if ev.shape == (n,) and np.all(np.isfinite(ev)) and np.all(ev > 0):
+                    sd = sd * torch.from_numpy(ev).to(self.device)
+            z = torch.empty(n, dtype=torch.float64, device=self.device)
+            for k in range(n_draws):
+                W[:, k] += sd * _lib.gibbs_normals(z, seed, self.NOISE_STREAM + k)
+        out = W.t().cpu().numpy()
+        if beta is not None:
+            bv = np.asarray(beta, dtype=np.float64)
+            if X is None:
+                if bv.ndim != 0:
+                    raise ValueError("beta without X must be a scalar (the constant mean)")
+                out = out + float(bv)
+            else:
+                Xh = np.asarray(X, dtype=np.float64)
+                Xh = Xh[:, None] if Xh.ndim == 1 else Xh
+                if Xh.shape[0] != n or bv.reshape(-1).shape != (Xh.shape[1],):
+                    raise ValueError(f"X must be ({n}, p) and beta (p,), got {Xh.shape} and {bv.shape}")
+                out = out + (Xh @ bv.reshape(-1))[None, :]
+        elif X is not None:
+            raise ValueError("X needs beta")
+        return out
+
     def oneSample(self, seed: int = 0, X=None, **sampler_kw):
         """One Gibbs iteration of the response model y = X beta + w + eps: the reference's
         ``update_wt`` / ``update_ws`` / ``update_y_unobserved`` (nngp.py:98-101, which do not

@@ -25,6 +25,11 @@ for tracing.
     torch.ops.nngp.latent_cg(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
                              check_every=8) -> (x, info)                 # Jacobi-PCG for A x = b (a solver call)
     torch.ops.nngp.precision_apply_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # x (n, nrhs <= 8)
+    torch.ops.nngp.factor_solve(nbr, B, off, rev_j, rev_k, prep, rows, level_off, level_off_host, trans, fuse_width,
+                                b) -> x          # (I - B) x = b, or (I - B)^T x = b for trans; b (n, nrhs <= 8); the
+        # schedule (rows, level_off on the device, level_off_host a CPU copy) from pynngp_amd._lib.factor_levels
+    torch.ops.nngp.factor_cov_apply(nbr, B, F, off, rev_j, rev_k, prep, rows_f, level_off_f, level_off_f_host, rows_t,
+                                    level_off_t, level_off_t_host, sigma2, fuse_width, v) -> sigma2 (I-B)^-1 F (I-B)^-T v
     torch.ops.nngp.latent_cg_batch(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
                                    check_every=8) -> (x, info)           # nrhs solves in lock step, info (nrhs, 4)
     torch.ops.nngp.latent_cg_batch_trace(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8,
@@ -138,6 +143,15 @@ def _register_fakes() -> None:
     @fake("precision_apply_batch")
     def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x):
         return torch.empty_like(x)
+
+    @fake("factor_solve")
+    def _(nbr, B, off, rev_j, rev_k, prep, rows, level_off, level_off_host, trans, fuse_width, b):
+        return torch.empty_like(b)
+
+    @fake("factor_cov_apply")
+    def _(nbr, B, F, off, rev_j, rev_k, prep, rows_f, level_off_f, level_off_f_host, rows_t, level_off_t,
+          level_off_t_host, sigma2, fuse_width, v):
+        return torch.empty_like(v)
 
     @fake("latent_cg_batch")
     def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
