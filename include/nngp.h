@@ -817,6 +817,39 @@ int nngp_factor_prior_draw_batch(const int32_t *nbr, const double *B, const doub
                                  int32_t m, double sigma2, int32_t nrhs, int32_t fuse_width, const double *z,
                                  uint64_t seed, uint64_t draw0, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Whitening of several columns by a stored factor, and the Gram matrix of the result: the response-model
+ * regression y = X beta + w + eps (pynngp_amd/regression.py; the reference has no mean model).  With
+ * Q = (I - B)^T F^-1 (I - B) the NNGP precision and V = [y, X], G = U^T U for U = F^-1/2 (I - B) V holds y'Qy, X'Qy
+ * and X'QX: GLS beta and its covariance, the profile and restricted likelihoods, universal kriging and the
+ * conjugate NNGP (spNNGP's spConjNNGP) follow from it on the host.  Added within ABI revision 4 (nothing earlier
+ * moved).
+ *   U[t, c] = (self[t, c] - sum_s B[t,s] V[nbr[t,s], c]) / sqrt(F[t]),     G[a, b] = sum_t U[t,a] U[t,b]
+ * nbr (n_rows, m), B (n_rows, m), F (n_rows,): exactly as nngp_bf_sweep, nngp_bf_cross or nngp_bf_sweep_blocks wrote
+ * them (any kind, 1 <= m <= NNGP_MAX_M).  order: NULL, or the nngp_row_order layout -- row t of nbr is then local row
+ * order[t], whose B, F, Vq and U rows are at order[t] (the sweeps write B and F at their natural rows); an order[t]
+ * outside [0, n_rows) is skipped.  V (n_points, ncol) row-major: the columns being gathered.  Vq: NULL -- the S = T
+ * sweep, the row's own values are V[i0 + row] (needs i0 + n_rows <= n_points) -- or (n_rows, ncol), the values at
+ * query rows against a reference set (i0 unused).  U (n_rows, ncol): required; must not alias V or Vq.  gram: NULL
+ * (whiten only) or (ncol, ncol) row-major, both triangles written.  1 <= ncol <= NNGP_WHITEN_MAX_COLS.
+ * The sum runs in slot order, one fused multiply-add per slot, from 0; a slot that is negative or >= n_points adds
+ * exactly 0; a row whose F is NaN or not positive gets NaN in U (numerical outcomes are data).  G is summed over
+ * tiles of 1,024 rows -- in each, four chains over the rows = 0..3 mod 4 in row order, one fused multiply-add per
+ * row, folded ((0 + 1) + (2 + 3)) -- and the tile records are folded in tile order by one block: an order that
+ * depends on n_rows alone, no atomics.
+ * THE CONTRACT: column c of U is bit-identical to the ncol = 1 call on that column; G[a, b] is bit-identical to the
+ * entry of the ncol = 2 call on columns (a, b) alone, whatever the other columns hold (a NaN in column c touches
+ * row c and column c of G only); every output is the same bits run to run, and U the same with or without gram.
+ * workspace: nngp_whiten_gram_workspace_bytes(n_rows, ncol) bytes (0 for bad arguments), 256-B aligned, no
+ * initialisation needed.  n_rows = 0: nothing is launched and gram is zeroed.  One stream-ordered launch with
+ * gram = NULL, three otherwise.
+ * ------------------------------------------------------------------------- */
+#define NNGP_WHITEN_MAX_COLS 16
+size_t nngp_whiten_gram_workspace_bytes(int64_t n_rows, int32_t ncol);
+int nngp_whiten_gram(const int32_t *nbr, const int32_t *order, const double *B, const double *F, int64_t n_rows,
+                     int32_t m, int64_t i0, int64_t n_points, int32_t ncol, const double *V, const double *Vq,
+                     double *U, double *gram, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Host helper for callers that synchronise ("-2 means a non-positive
  * pivot; report the first bad index through an out-param"): given host-resident
  * partials of a finished sweep, returns NNGP_OK, NNGP_ENOTPD with *first_bad_row = the

@@ -106,6 +106,8 @@ SYMBOLS = (
     "nngp_factor_solve_batch",
     "nngp_factor_cov_apply_batch",
     "nngp_factor_prior_draw_batch",
+    "nngp_whiten_gram_workspace_bytes",
+    "nngp_whiten_gram",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -119,6 +121,7 @@ CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
 BLOCKS_MAX_M = 32  # nngp_bf_sweep_blocks: 1 <= m <= 32
 LATENT_MAX_RHS = 8  # NNGP_LATENT_MAX_RHS: right-hand sides per batched latent call
 PG_MAX_TRIALS = 1024  # NNGP_PG_MAX_TRIALS: binomial trials per location of a Polya-Gamma draw
+WHITEN_MAX_COLS = 16  # NNGP_WHITEN_MAX_COLS: columns per nngp_whiten_gram call
 FACTOR_MAX_FUSE_WIDTH = 1024  # NNGP_FACTOR_MAX_FUSE_WIDTH: rows per level the factor solve's narrow-run kernel takes
 
 
@@ -322,6 +325,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_factor_cov_apply_batch.restype = ctypes.c_int
     lib.nngp_factor_prior_draw_batch.argtypes = [P, P, P, P, P, P, I64, I64, I32, D, I32, I32, P, U64, U64, P, P]
     lib.nngp_factor_prior_draw_batch.restype = ctypes.c_int
+    lib.nngp_whiten_gram_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_whiten_gram_workspace_bytes.restype = SZ
+    lib.nngp_whiten_gram.argtypes = [P, P, P, P, I64, I32, I64, I64, I32, P, P, P, P, P, SZ, P]
+    lib.nngp_whiten_gram.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1728,6 +1735,48 @@ def latent_rows_dot2_batch(nbr: torch.Tensor, B: torch.Tensor, dB: torch.Tensor,
     _check(load().nngp_latent_rows_dot2_batch(_ptr(nbr), _ptr(B), _ptr(dB), n, n_s, m, nrhs, _ptr(x), _ptr(p), _ptr(q),
                                               _stream(dev)), "nngp_latent_rows_dot2_batch")
     return p, q
+
+
+def whiten_gram(nbr: torch.Tensor, B: torch.Tensor, F: torch.Tensor, V: torch.Tensor, i0: int = 0,
+                order: Optional[torch.Tensor] = None, Vq: Optional[torch.Tensor] = None, want_gram: bool = True,
+                U: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Whiten the columns ``V`` (n_points, ncol), 1 <= ncol <= WHITEN_MAX_COLS, by the stored factor and form their
+    Gram matrix (nngp_whiten_gram): ``(U, G)`` with U (n_rows, ncol) = F^-1/2 (I - B) V and G (ncol, ncol) = U^T U
+    (``want_gram=False``: G is None).  ``nbr`` / ``B`` / ``F`` as the sweeps wrote them; ``order``: the
+    nngp_row_order layout when ``nbr`` holds the sorted rows; ``Vq`` (n_rows, ncol): the rows' own values for query
+    rows against a reference set (default: S = T, row r is point ``i0 + r`` of V).  Column c of U is bit-identical
+    to the one-column call and G[a, b] to the two-column call on (a, b)."""
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or not nbr.is_contiguous():
+        raise ValueError(f"nbr must be contiguous int32 (n_rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    n, m = nbr.shape
+    if not 1 <= m <= MAX_M:
+        raise ValueError(f"m={m} outside [1, {MAX_M}]")
+    dev = _require_gpu(nbr, B, F, V, order, Vq, U, workspace)
+    _check_out(B, "B", (n, m), dev)
+    _check_out(F, "F", (n,), dev)
+    if (V.dtype != torch.float64 or V.dim() != 2 or not 1 <= V.shape[1] <= WHITEN_MAX_COLS or not V.is_contiguous()
+            or V.shape[0] < 1):
+        raise ValueError(f"V must be contiguous float64 (n_points, ncol) with 1 <= ncol <= {WHITEN_MAX_COLS}, got "
+                         f"{V.dtype} {tuple(V.shape)}")
+    n_points, ncol = V.shape
+    i0 = int(i0)
+    _check_out(Vq, "Vq", (n, ncol), dev)
+    if Vq is None and not 0 <= i0 <= n_points - n:
+        raise ValueError(f"rows [{i0}, {i0 + n}) outside [0, {n_points})")
+    if order is not None and (order.dtype != torch.int32 or tuple(order.shape) != (n,) or not order.is_contiguous()):
+        raise ValueError(f"order must be contiguous int32 ({n},)")
+    _check_out(U, "U", (n, ncol), dev)
+    if U is None:
+        U = torch.empty((n, ncol), dtype=torch.float64, device=dev)
+    lib = load()
+    need = lib.nngp_whiten_gram_workspace_bytes(n, ncol)
+    ws = _workspace(need, dev) if workspace is None else workspace
+    if ws.numel() < need:
+        raise ValueError(f"workspace too small: {ws.numel()} < {need} bytes")
+    G = torch.empty((ncol, ncol), dtype=torch.float64, device=dev) if want_gram else None
+    _check(lib.nngp_whiten_gram(_ptr(nbr), _ptr(order), _ptr(B), _ptr(F), n, m, i0, n_points, ncol, _ptr(V), _ptr(Vq),
+                                _ptr(U), _ptr(G), _ptr(ws), ws.numel(), _stream(dev)), "nngp_whiten_gram")
+    return U, G
 
 
 # -- solves with the NNGP factor (nngp_factor_*) ------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include "latent_binomial.h"
 #include "factor.h"
 #include "factor_levels.h"
+#include "whiten_gram.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1184,6 +1185,35 @@ int nngp_latent_rows_dot2_batch(const int32_t* nbr, const double* B, const doubl
     if (p != nullptr && (p == q || p == x || q == x)) return fail(NNGP_EINVAL, "p, q and x must not alias");
     hipError_t e = nngp::latent_rows_dot2_launch(nbr, B, dB, n, n_s, m, nrhs, x, p, q, (hipStream_t)stream);
     return e != hipSuccess ? hip_fail(e, "latent_rows_dot2_batch launch") : NNGP_OK;
+}
+
+size_t nngp_whiten_gram_workspace_bytes(int64_t n_rows, int32_t ncol) {
+    return nngp::whiten_gram_workspace_bytes(n_rows, ncol);
+}
+
+int nngp_whiten_gram(const int32_t* nbr, const int32_t* order, const double* B, const double* F, int64_t n_rows,
+                     int32_t m, int64_t i0, int64_t n_points, int32_t ncol, const double* V, const double* Vq,
+                     double* U, double* gram, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ncol < 1 || ncol > NNGP_WHITEN_MAX_COLS)
+        return fail(NNGP_EINVAL, "ncol=%d outside [1, %d]", ncol, NNGP_WHITEN_MAX_COLS);
+    if (m < 1 || m > NNGP_MAX_M) return fail(NNGP_EINVAL, "m=%d outside [1, %d]", m, NNGP_MAX_M);
+    if (n_rows < 0 || n_rows > INT32_MAX || n_points < 1 || n_points > INT32_MAX || i0 < 0)
+        return fail(NNGP_EINVAL, "need 0 <= n_rows < 2^31, 1 <= n_points < 2^31 and i0 >= 0 (n_rows=%lld, "
+                    "n_points=%lld, i0=%lld)", (long long)n_rows, (long long)n_points, (long long)i0);
+    if (Vq == nullptr && i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (V == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "V and workspace must be non-null");
+    if (n_rows > 0 && (nbr == nullptr || B == nullptr || F == nullptr || U == nullptr))
+        return fail(NNGP_EINVAL, "nbr, B, F and U must be non-null");
+    if (U != nullptr && (U == V || U == Vq)) return fail(NNGP_EINVAL, "U must not alias V or Vq");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp::whiten_gram_workspace_bytes(n_rows, ncol);
+    if (need == 0 || workspace_bytes < need)
+        return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    const nngp::WhitenArgs a{nbr, order, B, F, n_rows, m, i0, n_points, ncol, V, Vq};
+    hipError_t e = nngp::whiten_gram_launch(a, U, gram, workspace, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, "whiten_gram launch") : NNGP_OK;
 }
 
 size_t nngp_row_order_workspace_bytes(int64_t n_rows) { return nngp::row_order_workspace_bytes(n_rows); }

@@ -646,9 +646,46 @@ at::Tensor factor_cov_apply(const at::Tensor& nbr, const at::Tensor& B, const at
     return out;
 }
 
+// ---------------------------------------------------------------- whitened Gram sweep
+// U = F^-1/2 (I - B) V and, with want_gram, G = U^T U (nngp_whiten_gram); V (n_points, ncol <= 16); Vq: the values
+// at the rows themselves for query rows against a reference set (None: S = T, the rows are points i0 ..)
+std::tuple<at::Tensor, at::Tensor> whiten_gram(const at::Tensor& nbr, const c10::optional<at::Tensor>& order,
+                                               const at::Tensor& B, const at::Tensor& F, int64_t i0,
+                                               const at::Tensor& V, const c10::optional<at::Tensor>& Vq,
+                                               bool want_gram) {
+    TORCH_CHECK(nbr.is_cuda() && B.is_cuda() && F.is_cuda() && V.is_cuda(),
+                "nbr, B, F and V must be ROCm GPU tensors (there is no CPU fallback)");
+    const at::OptionalDeviceGuard guard(nbr.device());
+    check_nbr(nbr, V);
+    const int64_t n = nbr.size(0), m = nbr.size(1);
+    check_f64(B, {n, m}, nbr, "B");
+    check_f64(F, {n}, nbr, "F");
+    TORCH_CHECK(V.scalar_type() == at::kDouble && V.dim() == 2 && V.is_contiguous() && V.size(1) >= 1 &&
+                    V.size(1) <= NNGP_WHITEN_MAX_COLS,
+                "V must be a contiguous float64 (n_points, ncol) tensor, 1 <= ncol <= ", NNGP_WHITEN_MAX_COLS);
+    const int64_t ncol = V.size(1);
+    check_f64(Vq, {n, ncol}, nbr, "Vq");
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == n &&
+                        order->is_contiguous(), "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(nbr, *order, "order");
+    }
+    auto U = at::empty({n, ncol}, V.options());
+    auto gram = at::empty({want_gram ? ncol : 0, want_gram ? ncol : 0}, V.options());
+    auto ws = workspace((int64_t)nngp_whiten_gram_workspace_bytes(n, (int32_t)ncol), V);
+    check_rc(nngp_whiten_gram(nbr.data_ptr<int32_t>(), ptr<int32_t>(order), B.data_ptr<double>(), F.data_ptr<double>(),
+                              n, (int32_t)m, i0, V.size(0), (int32_t)ncol, V.data_ptr<double>(), ptr<double>(Vq),
+                              U.data_ptr<double>(), want_gram ? gram.data_ptr<double>() : nullptr, ws.data_ptr(),
+                              ws.numel(), stream(nbr)),
+             "nngp_whiten_gram");
+    return {U, gram};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(nngp, m) {
+    m.def("whiten_gram(Tensor nbr, Tensor? order, Tensor B, Tensor F, int i0, Tensor V, Tensor? Vq, bool want_gram) "
+          "-> (Tensor, Tensor)");
     m.def("factor_solve(Tensor nbr, Tensor B, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, Tensor rows, "
           "Tensor level_off, Tensor level_off_host, bool trans, int fuse_width, Tensor b) -> Tensor");
     m.def("factor_cov_apply(Tensor nbr, Tensor B, Tensor F, Tensor off, Tensor rev_j, Tensor rev_k, Tensor prep, "
@@ -715,4 +752,5 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("factor_cov_apply", &factor_cov_apply);
     m.impl("latent_cg_batch", &latent_cg_batch);
     m.impl("latent_cg_batch_trace", &latent_cg_batch_trace);
+    m.impl("whiten_gram", &whiten_gram);
 }

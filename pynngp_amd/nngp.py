@@ -538,12 +538,24 @@ class NNGP:
         return self._Nt
 
     # -- prediction at t ------------------------------
-    def predict(self, values=None, cov: Optional[Covariance] = None, query=None, algo: str = "auto"):
+    def predict(self, values=None, cov: Optional[Covariance] = None, query=None, algo: str = "auto", X=None,
+                X_query=None):
         """Kriging of the NNGP at the points ``query`` (default ``t``) from ``values`` on S
         (default ``ws``): returns numpy ``(mean, var)`` with mean_t = B_t v_N(t) and
         var_t = F_t (conditional variance; includes tau2 like C_tt = sigma2 + tau2).
         Neighbours: the m nearest points of S to each query point (for query = t with
-        refType != 'S=T' these are ``Nt``)."""
+        refType != 'S=T' these are ``Nt``).
+
+        ``X`` (n, p) and ``X_query`` (n_query, p): universal kriging of ``values`` (default ``y``) with the
+        regression mean X beta, beta by GLS at ``cov`` (:meth:`gls`): mean x_q' beta + B_q (y - X beta)_N and
+        variance F_q + h_q' cov_beta h_q, h_q = x_q - B_q X_N (``pynngp_amd.regression.universal_kriging``)."""
+        if (X is None) != (X_query is None):
+            raise ValueError("universal kriging needs both X and X_query")
+        if X is not None:
+            from . import regression
+
+            mean, var, _ = regression.universal_kriging(self, cov, X, X_query, values=values, query=query, algo=algo)
+            return mean, var
         cv = self._covariance(cov)
         v = self.ws if values is None else values
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
@@ -689,19 +701,57 @@ class NNGP:
         n = self.nbr.shape[0]
         return -0.5 * (n * LOG_2PI + ph[0] + ph[1])
 
-    def profile_loglik(self, cov: Covariance, values=None, mean: str = "constant", algo: str = "auto"):
+    def gls(self, cov: Optional[Covariance], X, values=None, reml: bool = False, algo: str = "auto"):
+        """GLS of ``values`` (default y) on the design ``X`` (n, p; p + 1 <= 16; the caller adds the intercept
+        column) under the NNGP precision at ``cov``: one sweep that writes B and F, then one ``nngp_whiten_gram`` on
+        [y, X]; the p x p algebra on the host.  Returns a :class:`pynngp_amd.regression.GLSResult` (``beta``,
+        ``cov_beta``, ``loglik``, ``reml``, ``gram``); with ``reml=True`` its ``objective`` is the restricted
+        likelihood, else the profile likelihood.  A rank-deficient ``X`` raises :class:`NNGPNumericalError`."""
+        from . import regression
+
+        return regression.gls(self, cov, X, values=values, reml=reml, algo=algo)
+
+    def conjugate(self, kind: str, phi: float, alpha: float, X, prior: Optional[dict] = None,
+                  nu: Optional[float] = None, values=None, algo: str = "auto"):
+        """The conjugate NNGP (Finley et al.; spNNGP's ``spConjNNGP``) of ``values`` (default y) on ``X`` at fixed
+        (phi, alpha = tau2 / sigma2), computed at ``Covariance(kind, 1, phi, alpha)``: beta and sigma2 integrate out
+        in closed form.  ``prior``: dict ``a``, ``b`` (sigma2 ~ IG(a, b), default 2, 1) and optionally ``mu``, ``V``
+        (beta | sigma2 ~ N(mu, sigma2 V); default flat).  Returns a :class:`pynngp_amd.regression.ConjugateNNGP`: the
+        Normal-inverse-gamma posterior ``mu``, ``V``, ``a``, ``b``, ``log_evidence`` = log p(y | phi, alpha), and
+        ``predict(query, X_query)``, the Student-t predictive (location, scale, 2 a degrees of freedom)."""
+        from . import regression
+
+        return regression.conjugate(self, kind, phi, alpha, X, prior=prior, nu=nu, values=values, algo=algo)
+
+    def conjugate_grid(self, phis, alphas, kind: str, X, prior: Optional[dict] = None, nu: Optional[float] = None,
+                       values=None, algo: str = "auto"):
+        """:meth:`conjugate` over a grid: dict with ``log_evidence`` (len(phis), len(alphas)), its argmax ``phi`` /
+        ``alpha`` and ``best``, the fit there."""
+        from . import regression
+
+        return regression.conjugate_grid(self, phis, alphas, kind, X, prior=prior, nu=nu, values=values, algo=algo)
+
+    def profile_loglik(self, cov: Covariance, values=None, mean: str = "constant", algo: str = "auto", X=None):
         """NNGP log-likelihood of ``values`` (default y) at ``cov`` with a constant mean
         profiled out by GLS under the NNGP precision (I - B)^T F^-1 (I - B):
         mu = sum(r1 ry / F) / sum(r1^2 / F), r1 = (I - B) 1, ry = (I - B) y (two fused
         sweeps with residual output).  ``mean="zero"`` is :meth:`loglik`.  Returns
-        ``(loglik, mu)``."""
+        ``(loglik, mu)``.  ``mean="linear"`` with ``X`` (n, p): the regression mean X beta profiled out
+        (:meth:`gls`: one sweep and one whitened Gram); returns ``(loglik, beta)``."""
+        if mean == "linear":
+            if X is None:
+                raise ValueError("mean='linear' needs the design matrix X")
+            res = self.gls(cov, X, values=values, algo=algo)
+            return res.loglik, res.beta
+        if X is not None:
+            raise ValueError("X is the design of mean='linear'")
         v = self.y if values is None else values
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
                             dtype=torch.float64).to(self.device)
         if mean == "zero":
             return self.loglik(v, cov, algo), 0.0
         if mean != "constant":
-            raise ValueError("mean must be 'constant' or 'zero'")
+            raise ValueError("mean must be 'constant', 'zero' or 'linear'")
         n = v.shape[0]
         ry = torch.empty(n, dtype=torch.float64, device=self.device)
         r1 = torch.empty_like(ry)
@@ -750,12 +800,21 @@ class NNGP:
         n = self.nbr.shape[0]
         return -0.5 * (n * LOG_2PI + h[0] + h[1]), h[4:7].copy()
 
-    def profile_loglik_grad(self, cov: Covariance, values=None, mean: str = "constant"):
+    def profile_loglik_grad(self, cov: Covariance, values=None, mean: str = "constant", X=None):
         """:meth:`profile_loglik` and its gradient in (sigma2, phi, tau2): ``(loglik, mu, grad)``.  By the
         envelope theorem the gradient of the profiled likelihood is the plain gradient at ``values - mu``:
-        the two sweeps for mu plus one gradient sweep."""
+        the two sweeps for mu plus one gradient sweep.  ``mean="linear"`` with ``X``: ``(loglik, beta, grad)``, the
+        gradient sweep at ``values - X beta``."""
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
+        if mean == "linear":
+            from . import regression
+
+            ll, beta = self.profile_loglik(cv, v, mean="linear", X=X)
+            Xd = regression.design(self, X, v.shape[0])
+            return ll, beta, self.loglik_grad(v - Xd @ torch.from_numpy(beta).to(self.device), cv)[1]
+        if X is not None:
+            raise ValueError("X is the design of mean='linear'")
         if mean == "zero":  # one gradient sweep gives both
             ll, g = self.loglik_grad(v, cv)
             return ll, 0.0, g
@@ -764,7 +823,7 @@ class NNGP:
 
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
-            gradient: bool = False):
+            gradient: bool = False, X=None, reml: bool = False):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -775,8 +834,29 @@ class NNGP:
         ``gradient=True``: the objective also returns the analytic gradient
         (:meth:`profile_loglik_grad`, d/d log theta = theta d/d theta) and scipy runs with ``jac=True``,
         L-BFGS-B by default; fused kinds other than ``matern`` and 1 <= m <= 32 only.  The result gains
-        ``n_grad_evals``."""
+        ``n_grad_evals``.
+
+        ``mean="linear"`` with ``X`` (n, p): the regression mean X beta is profiled out (:meth:`gls`); the result
+        gains ``beta`` and ``cov_beta`` at the estimate and ``mu`` is None.  ``reml=True`` (``mean="linear"``, or
+        ``"constant"`` as the design of ones) maximises the restricted likelihood instead, derivative-free."""
         from scipy.optimize import minimize
+
+        if mean == "linear" and X is None:
+            raise ValueError("mean='linear' needs the design matrix X")
+        if mean != "linear" and X is not None:
+            raise ValueError("X is the design of mean='linear'")
+        if reml:
+            if gradient:
+                raise NotImplementedError("the restricted likelihood has no analytic gradient: use gradient=False")
+            if mean == "zero":
+                raise ValueError("reml needs a mean to restrict by: mean='constant' or 'linear'")
+            if mean == "constant":
+                X = np.ones((self.nbr.shape[0], 1))
+        linear = mean == "linear" or reml
+        if linear:  # uploaded once: every evaluation below reuses the device tensor
+            from . import regression
+
+            X = regression.design(self, X, self.nbr.shape[0])
 
         if method is None:
             method = "L-BFGS-B" if gradient else "Nelder-Mead"
@@ -797,7 +877,11 @@ class NNGP:
         def obj(z):
             th = theta_of(z)
             try:
-                ll, mu = self.profile_loglik(Covariance(kind, *th, nu=nu), mean=mean, algo=algo)
+                if linear:
+                    g = self.gls(Covariance(kind, *th, nu=nu), X, reml=reml, algo=algo)
+                    ll, mu = g.objective, None
+                else:
+                    ll, mu = self.profile_loglik(Covariance(kind, *th, nu=nu), mean=mean, algo=algo)
             except NNGPNumericalError:
                 return 1e300
             if ll > best["ll"]:
@@ -809,7 +893,8 @@ class NNGP:
         def obj_grad(z):
             th = theta_of(z)
             try:
-                ll, mu, g = self.profile_loglik_grad(Covariance(kind, *th, nu=nu), mean=mean)
+                ll, mu, g = self.profile_loglik_grad(Covariance(kind, *th, nu=nu), mean=mean, X=X)
+                mu = None if linear else mu
             except NNGPNumericalError:
                 # no gradient exists here: the zero one can end a line search early, so the failure is kept
                 # and shows in ``converged`` when the optimiser stops on such a point
@@ -827,14 +912,22 @@ class NNGP:
             self.cov = Covariance(kind, *best["theta"], nu=nu)
             self._B = self._F = None
             return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
-                    "n_grad_evals": n_grad[0], "converged": bool(res.success) and not last_failed[0]}
+                    "n_grad_evals": n_grad[0], "converged": bool(res.success) and not last_failed[0],
+                    **self._fit_beta(X if linear else None, algo)}
         res = minimize(obj, np.array(z0), method=method, options={"maxiter": maxiter, "xatol": 1e-6,
                                                                   "fatol": 1e-9} if method == "Nelder-Mead"
                        else {"maxiter": maxiter})
         self.cov = Covariance(kind, *best["theta"], nu=nu)
         self._B = self._F = None
         return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
-                "converged": bool(res.success)}
+                "converged": bool(res.success), **self._fit_beta(X if linear else None, algo)}
+
+    def _fit_beta(self, X, algo):
+        """``beta`` and ``cov_beta`` of a regression fit at the estimate ``self.cov`` (nothing without a design)."""
+        if X is None:
+            return {}
+        g = self.gls(self.cov, X, algo=algo)
+        return {"beta": g.beta, "cov_beta": g.cov_beta}
 
     # -- latent field at fixed theta --------------------------------------------
     def _latent_posterior(self, cov, mean: str):

@@ -35,6 +35,8 @@ for tracing.
     torch.ops.nngp.latent_cg_batch_trace(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8,
                                          max_iter=1000, check_every=8) -> (x, info, trace)   # and the CG scalars:
         # trace (nrhs, max_iter, 2), NaN but for trace[c, k] = (alpha_k, beta_k) of the iterations column c completed
+    torch.ops.nngp.whiten_gram(nbr, order, B, F, i0, V, Vq, want_gram) -> (U, G)   # U = F^-1/2 (I - B) V for V
+        # (n_points, ncol <= 16) and G = U^T U ((0, 0) without want_gram); Vq: the rows' own values (query rows), or None
     torch.ops.nngp.polya_gamma(trials, c, seed, sweep) -> (omega, status)   # omega_i ~ PG(trials_i, c_i); status (1,)
         # int32: 0, or the smallest index + 1 whose draw is NaN (non-finite c, trials outside [0, 1024])
     torch.ops.nngp.binomial_newton_step(trials, successes, offset, w) -> (d, rhs, g, partials)   # the binomial
@@ -162,6 +164,11 @@ def _register_fakes() -> None:
     def _(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000, check_every=8):
         raise RuntimeError("latent_cg_batch_trace is a solver call (it synchronises once per chunk of iterations): "
                            "run it eagerly")
+
+    @fake("whiten_gram")
+    def _(nbr, order, B, F, i0, V, Vq, want_gram):
+        ncol = V.shape[1]
+        return V.new_empty((nbr.shape[0], ncol)), V.new_empty((ncol, ncol) if want_gram else (0, 0))
 
     @fake("polya_gamma")
     def _(trials, c, seed, sweep):
