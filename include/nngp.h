@@ -221,6 +221,32 @@ int nngp_bf_dphi(const double *coords, int64_t n_points, int32_t dim, const int3
                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fisher information of the NNGP log-likelihood in (sigma2, phi, tau2), with the log-likelihood's partials and
+ * its gradient, one fused sweep over locations i0 .. i0 + n_rows - 1 (added within revision 4; coords, nbr, order,
+ * i0 and values as nngp_bf_grad).  Row i's term is its expected information under the exact Gaussian law of its
+ * joint block (location and neighbours), 1/2 tr(A^-1 dA_j A^-1 dA_k) - 1/2 tr(N^-1 dN_j N^-1 dN_k) with A the
+ * joint block and N its neighbour block (Guinness 2021), positive semi-definite row by row.
+ *   partials[4]: as nngp_bf_grad
+ *   grad[3]    = sum_i d l_i / d (sigma2, phi, tau2)
+ *   info[6]    = sum_i I_i, the upper triangle in the order (ss, sp, st, pp, pt, tt) for s = sigma2, p = phi,
+ *                t = tau2; all three are fixed-order folds, bit-reproducible run to run
+ *   I_rows     : NULL or (n_rows, 6), the term of location i0 + r in row r (r = order[t] for nbr row t, else t)
+ *   G          : NULL or (n_rows, 3), the gradient's terms, rows as I_rows
+ * values == NULL gives the information alone (it does not depend on the data): grad, G and partials[1] are
+ * written as exactly 0, and info and I_rows hold the bits of the call with values.
+ * Rows flagged in partials[2] get NaN in I_rows and G, and either flag makes the sums meaningless
+ * (nngp_check_partials).  Slots without a point (-1 padding) and out-of-range indices contribute exactly 0 to
+ * every sum.  kind: NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL (the general-nu Matern kind: NNGP_EUNSUP);
+ * 1 <= m <= 32 (else NNGP_EUNSUP); 1 <= dim <= 3.  workspace: nngp_bf_fisher_workspace_bytes(n_rows, m) bytes
+ * (0 for an unsupported m or n_rows < 0), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_fisher_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_fisher(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                   int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                   const double *values, double *I_rows, double *G, double *partials, double *grad, double *info,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Wave pair plans: the same sweep with every covariance a wavefront's locations share evaluated once.
  * The pair kernel (NNGP_ALGO_PAIRB) sweeps 32 consecutive rows per wavefront; in a spatial visiting
  * order neighbouring locations share most of their neighbours, so only ~46 % of a wave's joint-block

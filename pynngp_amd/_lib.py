@@ -72,6 +72,8 @@ SYMBOLS = (
     "nngp_bf_grad",
     "nngp_bf_dphi_workspace_bytes",
     "nngp_bf_dphi",
+    "nngp_bf_fisher_workspace_bytes",
+    "nngp_bf_fisher",
     "nngp_precision_workspace_bytes",
     "nngp_precision_apply",
     "nngp_precision_sqrt_t_apply",
@@ -169,6 +171,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_dphi_workspace_bytes.restype = SZ
     lib.nngp_bf_dphi.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
     lib.nngp_bf_dphi.restype = ctypes.c_int
+    lib.nngp_bf_fisher_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_fisher_workspace_bytes.restype = SZ
+    lib.nngp_bf_fisher.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_fisher.restype = ctypes.c_int
     lib.nngp_bf_cross.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, D, D, D, P, P, P, P, P, P, P, SZ,
                                   I32, P]
     lib.nngp_bf_cross.restype = ctypes.c_int
@@ -749,6 +755,56 @@ def bf_dphi(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2:
                             _ptr(dF), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_dphi")
     return B, F, dB, dF, partials
+
+
+def bf_fisher(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,
+              values: Optional[torch.Tensor] = None, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None):
+    """Fisher information sweep (``nngp_bf_fisher``, include/nngp.h) over rows ``i0 .. i0 + len(nbr)``.
+
+    Returns ``(partials, grad, info, I_rows, G)``: the four partials of :func:`bf_grad`, ``grad`` (3,) = the summed
+    d loglik / d (sigma2, phi, tau2), ``info`` (6,) = the summed expected information, upper triangle in the order
+    (ss, sp, st, pp, pt, tt), and with ``want_rows`` the per-location terms ``I_rows`` (rows, 6) and ``G`` (rows, 3)
+    at their natural rows (NaN in rows flagged in partials[2]), else None.  ``values=None`` gives the information
+    alone: ``grad``, ``G`` and ``partials[1]`` are exactly 0.  Stream-ordered on torch's current stream; no host
+    synchronisation.  Kinds exponential .. spherical, 1 <= m <= 32; ``order`` as in :func:`bf_sweep`.
+    """
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (coords.shape[0],):
+            raise ValueError("values must be float64 (N,) or None")
+        values = values.contiguous()
+    rows, m = nbr.shape
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "matern":
+        raise NotImplementedError("the information sweep serves the kinds exponential .. spherical, not the "
+                                  "general-nu matern kind")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the information sweep serves 1 <= m <= {GRAD_MAX_M} (m={m})")
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_fisher_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    if workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the sweep's device")
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(3, dtype=torch.float64, device=dev)
+    info = torch.empty(6, dtype=torch.float64, device=dev)
+    I_rows = torch.empty((rows, 6), dtype=torch.float64, device=dev) if want_rows else None
+    G = torch.empty((rows, 3), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_fisher(_ptr(coords), coords.shape[0], coords.shape[1], _ptr(nbr), _ptr(order), rows, m, i0,
+                              KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(values), _ptr(I_rows),
+                              _ptr(G), _ptr(partials), _ptr(grad), _ptr(info), _ptr(workspace), workspace.numel(),
+                              _stream(dev)),
+           "nngp_bf_fisher")
+    return partials, grad, info, I_rows, G
 
 
 def nbr_cert(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, order: Optional[torch.Tensor] = None):

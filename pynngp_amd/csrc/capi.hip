@@ -12,6 +12,7 @@
 #include "nbr_cert.h"
 #include "bf_grad.h"
 #include "bf_dphi.h"
+#include "bf_fisher.h"
 #include "latent.h"
 #include "latent_binomial.h"
 #include "factor.h"
@@ -255,6 +256,44 @@ int nngp_bf_dphi(const double* coords, int64_t n_points, int32_t dim, const int3
                      (double*)workspace};
     hipError_t e = nngp::bf_dphi_launch(a, partials, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_dphi launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_fisher_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    // at least one record, so the size is never 0 for a supported call
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * nngp::kFisherRec * sizeof(double));
+}
+
+int nngp_bf_fisher(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                   int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                   const double* values, double* I_rows, double* G, double* partials, double* grad, double* info,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (partials == nullptr || grad == nullptr || info == nullptr)
+        return fail(NNGP_EINVAL, "partials, grad and info must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the information sweep serves 1 <= m <= 32 (m=%d)", m);
+    if (kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the information sweep serves kinds exponential .. spherical, not the general-nu "
+                                 "matern");
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EINVAL, "unknown kind %d", kind);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (!(sigma2 > 0.0) || !(phi > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(phi) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, phi > 0, tau2 >= 0 (finite)");
+    if (I_rows != nullptr && (const void*)I_rows == (const void*)G)
+        return fail(NNGP_EINVAL, "I_rows and G must not alias");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_fisher_workspace_bytes(n_rows, m);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    nngp::FisherArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, phi, tau2, values, I_rows, G,
+                       (double*)workspace};
+    hipError_t e = nngp::bf_fisher_launch(a, partials, grad, info, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_fisher launch");
     return NNGP_OK;
 }
 

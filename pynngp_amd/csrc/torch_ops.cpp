@@ -250,6 +250,35 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_dphi(
     return {B, F, dB, dF, p};
 }
 
+// Fisher information sweep (nngp_bf_fisher): (partials (4,), grad (3,), info (6,), I_rows (rows, 6) or (0, 6),
+// G (rows, 3) or (0, 3)); values None: the information alone
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_fisher(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    double sigma2, double phi, double tau2, const c10::optional<at::Tensor>& values, bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    if (values.has_value()) check_f64(*values, {n}, coords, "values");
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == rows &&
+                        order->is_contiguous(), "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(coords, *order, "order");
+    }
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({3}, f64), info = at::empty({6}, f64);
+    at::Tensor I = at::empty({want_rows ? rows : 0, 6}, f64), G = at::empty({want_rows ? rows : 0, 3}, f64);
+    const int64_t need = (int64_t)nngp_bf_fisher_workspace_bytes(rows, (int32_t)m);
+    auto ws = at::empty({need > 256 ? need : 256}, f64.dtype(at::kByte));
+    check_rc(nngp_bf_fisher(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                            ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2,
+                            ptr<double>(values), want_rows ? I.data_ptr<double>() : nullptr,
+                            want_rows ? G.data_ptr<double>() : nullptr, p.data_ptr<double>(), g.data_ptr<double>(),
+                            info.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(), stream(coords)),
+             "nngp_bf_fisher");
+    return {p, g, info, I, G};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross(const at::Tensor& ref, const at::Tensor& query,
                                                         const at::Tensor& nbr, int64_t kind, double sigma2, double phi,
                                                         double tau2, const c10::optional<at::Tensor>& ref_values,
@@ -721,6 +750,8 @@ TORCH_LIBRARY(nngp, m) {
           "Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_dphi(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2) "
           "-> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_fisher(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2, "
+          "Tensor? values, bool want_rows) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("nbr_cert(Tensor coords, Tensor nbr, Tensor? order, int i0) -> (Tensor, Tensor)");
     m.def("pair_plan(Tensor nbr, Tensor? order, int i0, int n_points, int dim) -> (Tensor, Tensor)");
     m.def("bf_cross(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
@@ -741,6 +772,7 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_cross", &bf_cross);
     m.impl("bf_grad", &bf_grad);
     m.impl("bf_dphi", &bf_dphi);
+    m.impl("bf_fisher", &bf_fisher);
     m.impl("row_order", &row_order);
     m.impl("pair_plan", &pair_plan);
     m.impl("nbr_cert", &nbr_cert);

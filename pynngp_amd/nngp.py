@@ -821,9 +821,146 @@ class NNGP:
         ll, mu = self.profile_loglik(cv, v, mean=mean)
         return ll, mu, self.loglik_grad(v - mu, cv)[1]
 
+    def _fisher_sweep(self, cv: Covariance, v, want_rows: bool = False):
+        """One ``nngp_bf_fisher`` sweep at ``cv`` over ``v`` (a device tensor, or None for the information alone):
+        ``(loglik or None, grad (3,), info (3, 3), I_rows, G)``, host arrays but for the two row tensors."""
+        from . import fisher
+
+        p, g, info, I_rows, G = _lib.bf_fisher(self._s_dev, self._nbr_sorted, 0, cv.kind, cv.sigma2, cv.phi, cv.tau2,
+                                               v, want_rows=want_rows, order=self._order)
+        h = torch.cat([p, g, info]).cpu().numpy()
+        _raise_on_bad(h[:4])
+        n = self.nbr.shape[0]
+        ll = None if v is None else -0.5 * (n * LOG_2PI + h[0] + h[1])
+        return ll, h[4:7].copy(), fisher.info_matrix(h[7:13]), I_rows, G
+
+    def fisher_information(self, cov: Optional[Covariance] = None, values=None, mean: str = "zero", X=None,
+                           log: bool = False, rows: bool = False) -> dict:
+        """The Fisher information of the NNGP (Vecchia) likelihood in theta = (sigma2, phi, tau2) at ``cov``, from
+        one fused sweep (``nngp_bf_fisher``): the sum over locations of each one's expected information under the
+        exact Gaussian law of its joint block (Guinness 2021), positive semi-definite by construction.
+
+        Returns a dict with ``info`` (3, 3), ``grad`` (3,) and ``loglik``; with a profiled mean also ``mu``
+        (``mean="constant"``) or ``beta`` (``mean="linear"`` with ``X``), the gradient and likelihood then taken at
+        ``values - mean`` as in :meth:`profile_loglik_grad` (theta and the mean's coefficients are orthogonal in the
+        information; the coefficients' own block is ``gls``'s ``gram``).  ``rows=True`` adds ``I_rows`` (n, 6), the
+        locations' terms in the order (ss, sp, st, pp, pt, tt), and ``G`` (n, 3).  ``log=True`` gives the forms in log
+        theta: diag(theta) I diag(theta) and theta * grad.
+
+        ``values=None`` is the design-stage call: the information does not depend on the data, ``grad`` is exactly
+        0 and ``loglik`` is None (``mean`` must then be ``"zero"``).  Fused kinds other than ``matern`` and
+        1 <= m <= 32 only."""
+        from . import fisher
+
+        cv = self._grad_cov(cov)
+        if mean not in ("zero", "constant", "linear"):
+            raise ValueError("mean must be 'constant', 'zero' or 'linear'")
+        if mean == "linear" and X is None:
+            raise ValueError("mean='linear' needs the design matrix X")
+        if mean != "linear" and X is not None:
+            raise ValueError("X is the design of mean='linear'")
+        out = {}
+        if values is None:
+            if mean != "zero":
+                raise ValueError("profiling a mean needs values: the design-stage call (values=None) takes mean='zero'")
+            v = None
+        else:
+            v = self._values_dev(values)
+            if mean == "linear":
+                from . import regression
+
+                _, beta = self.profile_loglik(cv, v, mean="linear", X=X)
+                v = v - regression.design(self, X, v.shape[0]) @ torch.from_numpy(beta).to(self.device)
+                out["beta"] = beta
+            elif mean == "constant":
+                _, mu = self.profile_loglik(cv, v, mean="constant")
+                v = v - mu
+                out["mu"] = mu
+        ll, g, info, I_rows, G = self._fisher_sweep(cv, v, want_rows=rows)
+        th = np.array(cv.theta[:3], dtype=np.float64)
+        if log:
+            info, g = fisher.to_log(info, g, th)
+        out.update(info=info, grad=g, loglik=ll)
+        if rows:
+            I_rows, G = I_rows.cpu().numpy(), G.cpu().numpy()
+            out.update(I_rows=fisher.info_rows_scale(I_rows, th) if log else I_rows, G=G * th if log else G)
+        return out
+
+    def _fit_stderr(self, kind, theta, nu, mean, X, free_tau: bool) -> dict:
+        """``info``, ``cov_theta`` and ``se`` of a fit at ``theta``: one information sweep (the information does
+        not read the data) and the inverse of the free parameters' block."""
+        from . import fisher
+
+        _, _, info, _, _ = self._fisher_sweep(self._grad_cov(Covariance(kind, *theta, nu=nu)), None)
+        k = 3 if free_tau else 2
+        cov_theta, se = fisher.theta_cov(info[:k, :k])
+        return {"info": info[:k, :k].copy(), "cov_theta": cov_theta, "se": se}
+
+    def _fit_fisher(self, kind, th0, nu, mean, X, linear, free_tau, fix_tau2, maxiter, tol, algo) -> dict:
+        """Fisher scoring on the free log-parameters (:mod:`pynngp_amd.fisher` has the iteration and its ridge
+        rule): each iteration profiles the mean, runs one information sweep at the residual and halves the step
+        while the profiled likelihood falls."""
+        from . import fisher
+
+        k = 3 if free_tau else 2
+        y = self._values_dev(None)
+        state = {}
+
+        def theta_of(z):
+            return (math.exp(z[0]), math.exp(z[1]), math.exp(z[2]) if free_tau else float(fix_tau2))
+
+        def profile(z):
+            th = theta_of(z)
+            cv = Covariance(kind, *th, nu=nu)
+            try:
+                if linear:
+                    res = self.gls(cv, X, algo=algo)
+                    return res.loglik, res.beta, cv
+                ll, mu = self.profile_loglik(cv, mean=mean, algo=algo)
+                return ll, mu, cv
+            except NNGPNumericalError:
+                return None
+
+        def loglik_only(z):
+            p = profile(z)
+            return None if p is None else p[0]
+
+        def evaluate(z):
+            p = profile(z)
+            if p is None:
+                return None
+            ll, mu, cv = p
+            try:
+                if linear:
+                    v = y - X @ torch.from_numpy(mu).to(self.device)
+                else:
+                    v = y - mu if mean == "constant" else y
+                _, g, info, _, _ = self._fisher_sweep(cv, v)
+            except NNGPNumericalError:
+                return None
+            th = np.array(cv.theta[:3])
+            I_log, g_log = fisher.to_log(info, g, th)
+            state[tuple(z)] = (None if linear else mu, cv.theta[:3], info)
+            return ll, g_log[:k], I_log[:k, :k]
+
+        z0 = [math.log(th0[0]), math.log(th0[1])] + ([math.log(max(th0[2], 1e-6))] if free_tau else [])
+        try:
+            res = fisher.fisher_scoring(evaluate, z0, loglik_only=loglik_only, maxiter=maxiter,
+                                        tol=fisher.DEFAULT_TOL if tol is None else tol)
+        except FloatingPointError as e:
+            raise NNGPNumericalError(f"Fisher scoring: {e}") from None
+        mu, theta, info = state[tuple(res["z"])]
+        theta = tuple(float(t) for t in theta)
+        self.cov = Covariance(kind, *theta, nu=nu)
+        self._B = self._F = None
+        cov_theta, se = fisher.theta_cov(info[:k, :k])
+        return {"theta": theta, "mu": mu, "loglik": res["loglik"], "n_evals": res["n_evals"] + res["n_loglik_evals"],
+                "converged": res["converged"], **self._fit_beta(X if linear else None, algo), "n_iter": res["n_iter"],
+                "info": info[:k, :k].copy(), "cov_theta": cov_theta, "se": se}
+
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
-            gradient: bool = False, X=None, reml: bool = False):
+            gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -838,13 +975,32 @@ class NNGP:
 
         ``mean="linear"`` with ``X`` (n, p): the regression mean X beta is profiled out (:meth:`gls`); the result
         gains ``beta`` and ``cov_beta`` at the estimate and ``mu`` is None.  ``reml=True`` (``mean="linear"``, or
-        ``"constant"`` as the design of ones) maximises the restricted likelihood instead, derivative-free."""
-        from scipy.optimize import minimize
+        ``"constant"`` as the design of ones) maximises the restricted likelihood instead, derivative-free.
 
+        ``method="fisher"``: Fisher scoring on the free log-parameters (Guinness 2021; :mod:`pynngp_amd.fisher`):
+        each iteration profiles the mean, takes the gradient and the expected information from one
+        ``nngp_bf_fisher`` sweep at the residual, and halves the step I^-1 g while the profiled likelihood falls; it
+        stops when |g . step| < ``tol`` (default 1e-10) or after ``maxiter`` steps.  ``fix_tau2`` drops the nugget's
+        row and column.  The result gains ``n_iter``, ``info`` (the free parameters' block of the information in
+        theta), ``cov_theta`` (its inverse) and ``se`` (the root of that diagonal).  The kinds and m of
+        ``gradient=True``; no ``reml``.
+
+        ``stderr=True`` adds ``info``, ``cov_theta`` and ``se`` to any other method's result: one information
+        sweep at the estimate (the same kinds and m)."""
         if mean == "linear" and X is None:
             raise ValueError("mean='linear' needs the design matrix X")
         if mean != "linear" and X is not None:
             raise ValueError("X is the design of mean='linear'")
+        if method == "fisher" or stderr:  # refused before any sweep, as gradient=True's kinds and m are
+            if method == "fisher" and reml:
+                raise NotImplementedError("the restricted likelihood has no analytic gradient or information: "
+                                          "method='fisher' maximises the profile likelihood (reml=False)")
+            if kind is None:
+                self._grad_cov(None)
+            elif kind == "matern":
+                raise NotImplementedError("the analytic gradient does not serve the general-nu matern kind")
+            elif not 1 <= self.m <= _lib.GRAD_MAX_M:
+                raise NotImplementedError(f"the analytic gradient serves 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
         if reml:
             if gradient:
                 raise NotImplementedError("the restricted likelihood has no analytic gradient: use gradient=False")
@@ -867,6 +1023,15 @@ class NNGP:
             nu = base.nu
         th0 = tuple(x0) if x0 is not None else (base.theta if base is not None else (1.0, 10.0, 0.1))
         free_tau = fix_tau2 is None
+        if method == "fisher":
+            return self._fit_fisher(kind, th0, nu, mean, X, linear, free_tau, fix_tau2, maxiter, tol, algo)
+        from scipy.optimize import minimize
+
+        def with_stderr(result):
+            if stderr:
+                result.update(self._fit_stderr(kind, result["theta"], nu, mean, X, free_tau))
+            return result
+
         z0 = [math.log(th0[0]), math.log(th0[1])] + ([math.log(max(th0[2], 1e-6))] if free_tau else [])
 
         def theta_of(z):
@@ -911,16 +1076,17 @@ class NNGP:
             res = minimize(obj_grad, np.array(z0), jac=True, method=method, options={"maxiter": maxiter})
             self.cov = Covariance(kind, *best["theta"], nu=nu)
             self._B = self._F = None
-            return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
-                    "n_grad_evals": n_grad[0], "converged": bool(res.success) and not last_failed[0],
-                    **self._fit_beta(X if linear else None, algo)}
+            return with_stderr({"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"],
+                                "n_evals": int(res.nfev), "n_grad_evals": n_grad[0],
+                                "converged": bool(res.success) and not last_failed[0],
+                                **self._fit_beta(X if linear else None, algo)})
         res = minimize(obj, np.array(z0), method=method, options={"maxiter": maxiter, "xatol": 1e-6,
                                                                   "fatol": 1e-9} if method == "Nelder-Mead"
                        else {"maxiter": maxiter})
         self.cov = Covariance(kind, *best["theta"], nu=nu)
         self._B = self._F = None
-        return {"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
-                "converged": bool(res.success), **self._fit_beta(X if linear else None, algo)}
+        return with_stderr({"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
+                            "converged": bool(res.success), **self._fit_beta(X if linear else None, algo)})
 
     def _fit_beta(self, X, algo):
         """``beta`` and ``cov_beta`` of a regression fit at the estimate ``self.cov`` (nothing without a design)."""

@@ -16,6 +16,8 @@ for tracing.
     torch.ops.nngp.bf_sweep_out(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, B, F, R, partials,
                                 workspace, algo, nu=-1.0, plan=None, plan_info=None, cert=None, cert_info=None)
         -> ()                                                         # the hot path: caller-owned buffers
+    torch.ops.nngp.bf_fisher(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
+        -> (partials, grad, info, I_rows, G)   # Fisher information in (sigma2, phi, tau2); values None: info alone
     torch.ops.nngp.nbr_cert(coords, nbr, order, i0) -> (cert, cert_info)   # neighbour-set certificate (setup)
     torch.ops.nngp.pair_plan(nbr, order, i0, n_points, dim) -> (plan, plan_info)   # wave pair plan (setup)
     torch.ops.nngp.bf_cross(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0) -> (B, F, mean)
@@ -106,6 +108,12 @@ def _register_fakes() -> None:
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
         return (coords.new_empty((4,)), coords.new_empty((3,)),
                 coords.new_empty((nbr.shape[0] if want_rows else 0, 3)))
+
+    @fake("bf_fisher")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
+        rows = nbr.shape[0] if want_rows else 0
+        return (coords.new_empty((4,)), coords.new_empty((3,)), coords.new_empty((6,)), coords.new_empty((rows, 6)),
+                coords.new_empty((rows, 3)))
 
     @fake("bf_sweep_out")
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, B, F, R, partials, workspace, algo, nu=-1.0,
@@ -212,6 +220,17 @@ def bf_sweep_out(coords, nbr, order, i0, kind: str, theta, values, B, F, R, part
     torch.ops.nngp.bf_sweep_out(coords, nbr, order, int(i0), kind_code(kind), float(theta[0]), float(theta[1]),
                                 float(theta[2]), values, B, F, R, partials, workspace, algo_code(algo), nu, pbuf,
                                 pinfo, cbuf, cinfo)
+
+
+def bf_fisher(coords, nbr, order, i0: int, kind: str, theta, values=None, want_rows: bool = False):
+    """The Fisher information sweep through ``torch.ops.nngp.bf_fisher`` (stream-ordered, no host
+    synchronisation): ``(partials (4,), grad (3,), info (6,), I_rows, G)`` at ``theta`` = (sigma2, phi, tau2), the
+    information's upper triangle in the order (ss, sp, st, pp, pt, tt); ``I_rows`` (rows, 6) and ``G`` (rows, 3) with
+    ``want_rows``, else empty.  ``values=None``: the information alone (``grad`` exactly 0).  Kinds exponential ..
+    spherical, 1 <= m <= 32; CPU tensors raise."""
+    load()
+    return torch.ops.nngp.bf_fisher(coords, nbr, order, int(i0), kind_code(kind), float(theta[0]), float(theta[1]),
+                                    float(theta[2]), values, bool(want_rows))
 
 
 def nbr_cert(coords, nbr, order, i0: int):
