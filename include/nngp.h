@@ -87,7 +87,8 @@ const char *nngp_version(void);
  * Revision 4 (library 0.4.0): the pair plans are per wave (a new plan format, m <= 17) and their info
  * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan).
  * Added within revision 4 (nothing earlier moved): the gradient sweep nngp_bf_grad_workspace_bytes /
- * nngp_bf_grad; the latent-field posterior nngp_precision_workspace_bytes / nngp_precision_apply /
+ * nngp_bf_grad and its per-axis form nngp_bf_grad_aniso_workspace_bytes / nngp_bf_grad_aniso; the
+ * latent-field posterior nngp_precision_workspace_bytes / nngp_precision_apply /
  * nngp_precision_sqrt_t_apply / nngp_latent_cg_workspace_bytes / nngp_latent_cg; their forms for several
  * right-hand sides nngp_precision_batch_workspace_bytes / nngp_precision_apply_batch /
  * nngp_precision_sqrt_t_apply_batch / nngp_latent_cg_batch_workspace_bytes / nngp_latent_cg_batch, and
@@ -245,6 +246,33 @@ int nngp_bf_fisher(const double *coords, int64_t n_points, int32_t dim, const in
                    int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
                    const double *values, double *I_rows, double *G, double *partials, double *grad, double *info,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Analytic gradient of the log-likelihood for a covariance with one decay per axis,
+ * u = sqrt(sum_k (phi_k (a_k - b_k))^2), in (sigma2, phi_1 .. phi_dim, tau2): one fused sweep over locations
+ * i0 .. i0 + n_rows - 1 (added within revision 4; coords -- the raw, unscaled coordinates --, nbr, order, i0 and
+ * values as nngp_bf_grad).  B, F and the log-likelihood of this model are nngp_bf_sweep's at phi = 1 on the
+ * coordinates scaled column by column; with delta_k the scaled coordinate difference,
+ * dC_ab / dphi_k = sigma2 rho'(u) delta_k^2 / (u phi_k), exactly 0 for coincident points.
+ *   phi          : HOST array of dim entries, read before the call returns
+ *   partials[4]  : as nngp_bf_grad
+ *   grad[dim + 2] = sum_i d l_i / d (sigma2, phi_1, .., phi_dim, tau2), a fixed-order fold: bit-reproducible run
+ *                  to run
+ *   G            : NULL or (n_rows, dim + 2), the term of location i0 + r in row r (r = order[t] for nbr row t,
+ *                  else t)
+ * Rows flagged in partials[2] get NaN in G, and either flag makes grad meaningless (nngp_check_partials).
+ * Slots without a point (-1 padding) and out-of-range indices contribute exactly 0 to every sum.
+ * kind: NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL (the general-nu Matern kind: NNGP_EUNSUP); 1 <= m <= 32
+ * (else NNGP_EUNSUP); 1 <= dim <= 3 (else NNGP_EUNSUP).  phi == NULL and any phi_k that is not positive and
+ * finite: NNGP_EINVAL, as sigma2 <= 0 and tau2 < 0.  workspace: nngp_bf_grad_aniso_workspace_bytes(n_rows, m,
+ * dim) bytes (0 for an unsupported m or dim, or n_rows < 0), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_grad_aniso_workspace_bytes(int64_t n_rows, int32_t m, int32_t dim);
+int nngp_bf_grad_aniso(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2,
+                       const double *phi /* host, dim entries */, double tau2, const double *values, double *G,
+                       double *partials, double *grad /* dim + 2 */, void *workspace, size_t workspace_bytes,
+                       void *stream);
 
 /* ---------------------------------------------------------------------------
  * Wave pair plans: the same sweep with every covariance a wavefront's locations share evaluated once.

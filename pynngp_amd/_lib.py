@@ -70,6 +70,8 @@ SYMBOLS = (
     "nngp_bf_sweep_cert",
     "nngp_bf_grad_workspace_bytes",
     "nngp_bf_grad",
+    "nngp_bf_grad_aniso_workspace_bytes",
+    "nngp_bf_grad_aniso",
     "nngp_bf_dphi_workspace_bytes",
     "nngp_bf_dphi",
     "nngp_bf_fisher_workspace_bytes",
@@ -167,6 +169,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_grad_workspace_bytes.restype = SZ
     lib.nngp_bf_grad.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad.restype = ctypes.c_int
+    lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_grad_aniso_workspace_bytes.restype = SZ
+    lib.nngp_bf_grad_aniso.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_aniso.restype = ctypes.c_int
     lib.nngp_bf_dphi_workspace_bytes.argtypes = [I64, I32]
     lib.nngp_bf_dphi_workspace_bytes.restype = SZ
     lib.nngp_bf_dphi.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
@@ -707,6 +713,69 @@ def bf_grad(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2:
                             KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(values), _ptr(G),
                             _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_grad")
+    return partials, grad, G
+
+
+def _phi_vec(phi_vec, dim: int) -> Tuple[float, ...]:
+    """The per-axis decays as ``dim`` positive finite floats."""
+    try:
+        phi = tuple(float(p) for p in phi_vec)
+    except TypeError:
+        raise ValueError("phi_vec must be a sequence of dim positive floats") from None
+    if len(phi) != dim:
+        raise ValueError(f"phi_vec has {len(phi)} entries for {dim}-dimensional coordinates")
+    if not all(p > 0.0 and np.isfinite(p) for p in phi):
+        raise ValueError(f"every phi_k must be positive and finite, got {phi}")
+    return phi
+
+
+def bf_grad_aniso(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi_vec, tau2: float,
+                  values: torch.Tensor, order: Optional[torch.Tensor] = None, want_rows: bool = False,
+                  workspace: Optional[torch.Tensor] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Per-axis gradient sweep (``nngp_bf_grad_aniso``, include/nngp.h) over rows ``i0 .. i0 + len(nbr)``, for the
+    covariance with one decay per axis, u = sqrt(sum_k (phi_k (a_k - b_k))^2).  ``coords`` are the raw coordinates;
+    ``phi_vec`` has one entry per column.
+
+    Returns ``(partials, grad, G)``: the four partials of :func:`bf_sweep` (at phi = 1 on the scaled coordinates),
+    ``grad`` = the summed d loglik / d (sigma2, phi_1 .. phi_dim, tau2) (float64 (dim + 2,), fixed fold order) and,
+    with ``want_rows``, ``G`` (rows, dim + 2) (NaN in rows flagged in partials[2]).  Stream-ordered on torch's
+    current stream; no host synchronisation.  Kinds exponential .. spherical, 1 <= m <= 32.
+    """
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if values is None or values.dtype != torch.float64 or values.shape != (coords.shape[0],):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    rows, m = nbr.shape
+    dim = coords.shape[1]
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "matern":
+        raise NotImplementedError("the per-axis gradient sweep serves the kinds exponential .. spherical, not the "
+                                  "general-nu matern kind")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the per-axis gradient sweep serves 1 <= m <= {GRAD_MAX_M} (m={m})")
+    phi = _phi_vec(phi_vec, dim)
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_grad_aniso_workspace_bytes(rows, m, dim)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    if workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the sweep's device")
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(dim + 2, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, dim + 2), dtype=torch.float64, device=dev) if want_rows else None
+    phi_host = (ctypes.c_double * dim)(*phi)
+    _check(lib.nngp_bf_grad_aniso(_ptr(coords), coords.shape[0], dim, _ptr(nbr), _ptr(order), rows, m, i0,
+                                  KIND_CODES[kind], float(sigma2), phi_host, float(tau2), _ptr(values), _ptr(G),
+                                  _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_grad_aniso")
     return partials, grad, G
 
 

@@ -43,9 +43,51 @@ class _LogLik(torch.autograd.Function):
         return None, None, gtheta, gvalues, None, None
 
 
+class _LogLikAniso(torch.autograd.Function):
+    """theta = (sigma2, phi_1 .. phi_dim, tau2): the per-axis sweep (``torch.ops.nngp.bf_grad_aniso``)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, kind, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_aniso(coords, nbr, order, 0, _lib.KIND_CODES[kind], th[0], th[1:-1], th[-1],
+                                               values.detach(), False)
+        ctx.save_for_backward(coords, nbr, values, g)
+        ctx.meta = (kind, order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g = ctx.saved_tensors
+        kind, order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLik: one ordinary sweep, at phi = 1 on the coordinates scaled column by column
+            rows, m = nbr.shape
+            scaled = coords * torch.tensor(th[1:-1], dtype=torch.float64, device=coords.device)
+            R = torch.empty(rows, dtype=torch.float64, device=coords.device)
+            B, F, _ = _lib.bf_sweep(scaled, nbr, 0, kind, th[0], 1.0, th[-1], values=values.detach(), order=order, R=R)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None, None
+
+
 def loglik(coords, nbr, theta, values, kind, order=None):
     """NNGP log-likelihood of ``values`` on S = T at ``theta`` = (sigma2, phi, tau2), a float64 (3,) tensor,
     differentiable in ``theta`` and, when ``values.requires_grad``, in ``values``.
+
+    ``theta`` of shape (dim + 2,) = (sigma2, phi_1 .. phi_dim, tau2) selects the covariance with one decay per axis,
+    u = sqrt(sum_k (phi_k (a_k - b_k))^2), on the raw ``coords`` (``torch.ops.nngp.bf_grad_aniso``); for
+    1-D coordinates (3,) is the isotropic form, which is the same model.
 
     Forward runs one gradient sweep (``torch.ops.nngp.bf_grad``) and synchronises with the host twice: it
     reads theta before the launch and the sweep's two flags after it.  Backward returns ``grad_out * grad`` for theta with no further launch; the gradient in
@@ -57,13 +99,16 @@ def loglik(coords, nbr, theta, values, kind, order=None):
     if kind not in _KINDS:
         raise NotImplementedError("loglik's gradient serves the kinds exponential .. spherical, not the general-nu "
                                   "matern kind")
-    if theta.dtype != torch.float64 or theta.shape != (3,):
-        raise ValueError("theta must be a float64 (3,) tensor (sigma2, phi, tau2)")
+    aniso = theta.dtype == torch.float64 and theta.shape != (3,) and coords.dim() == 2 \
+        and theta.shape == (coords.shape[1] + 2,)
+    if not aniso and (theta.dtype != torch.float64 or theta.shape != (3,)):
+        raise ValueError("theta must be a float64 (3,) tensor (sigma2, phi, tau2) or (dim + 2,) "
+                         "(sigma2, phi_1 .. phi_dim, tau2)")
     if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
         raise NotImplementedError(f"loglik's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
     if nbr.shape[0] != coords.shape[0]:
         raise ValueError("loglik is an S = T sweep: one nbr row per location")
-    ll, p = _LogLik.apply(coords, nbr, theta, values, kind, order)
+    ll, p = (_LogLikAniso if aniso else _LogLik).apply(coords, nbr, theta, values, kind, order)
     from .nngp import _raise_on_bad
 
     _raise_on_bad(p.detach().cpu().numpy())

@@ -11,6 +11,7 @@
 #include "bf_pairb.h"
 #include "nbr_cert.h"
 #include "bf_grad.h"
+#include "bf_grad_aniso.h"
 #include "bf_dphi.h"
 #include "bf_fisher.h"
 #include "latent.h"
@@ -217,6 +218,47 @@ int nngp_bf_grad(const double* coords, int64_t n_points, int32_t dim, const int3
                      (double*)workspace};
     hipError_t e = nngp::bf_grad_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_grad_aniso_workspace_bytes(int64_t n_rows, int32_t m, int32_t dim) {
+    if (n_rows < 0 || m < 1 || m > 32 || dim < 1 || dim > NNGP_MAX_DIM) return 0;
+    // at least one record, so the size is never 0 for a supported call
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * nngp::kGradAnisoRec * sizeof(double));
+}
+
+int nngp_bf_grad_aniso(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double* phi,
+                       double tau2, const double* values, double* G, double* partials, double* grad, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (values == nullptr || partials == nullptr || grad == nullptr)
+        return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    if (phi == nullptr) return fail(NNGP_EINVAL, "phi must be non-null (a host array of dim entries)");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the per-axis gradient sweep serves 1 <= m <= 32 (m=%d)", m);
+    if (kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the per-axis gradient sweep serves kinds exponential .. spherical, not the "
+                                 "general-nu matern");
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EINVAL, "unknown kind %d", kind);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (!(sigma2 > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, tau2 >= 0 (finite)");
+    for (int k = 0; k < dim; ++k)
+        if (!(phi[k] > 0.0) || !isfinite(phi[k]))
+            return fail(NNGP_EINVAL, "phi[%d] = %g must be positive and finite", k, phi[k]);
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_grad_aniso_workspace_bytes(n_rows, m, dim);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    nngp::GradAnisoArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, {1.0, 1.0, 1.0}, tau2,
+                          values, G, (double*)workspace};
+    for (int k = 0; k < dim; ++k) a.phi[k] = phi[k];
+    hipError_t e = nngp::bf_grad_aniso_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_aniso launch");
     return NNGP_OK;
 }
 

@@ -224,6 +224,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad(const at::Tensor& coords,
     return {p, g, G};
 }
 
+// per-axis gradient sweep (nngp_bf_grad_aniso): (partials (4,), grad (dim + 2,), G (rows, dim + 2) or (0, dim + 2))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_aniso(const at::Tensor& coords, const at::Tensor& nbr,
+                                                             const c10::optional<at::Tensor>& order, int64_t i0,
+                                                             int64_t kind, double sigma2, at::ArrayRef<double> phi,
+                                                             double tau2, const at::Tensor& values, bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    check_f64(values, {n}, coords, "values");
+    TORCH_CHECK((int64_t)phi.size() == d, "phi has ", phi.size(), " entries for ", d, "-dimensional coordinates");
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == rows &&
+                        order->is_contiguous(), "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(coords, *order, "order");
+    }
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({d + 2}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, d + 2}, f64);
+    const int64_t need = (int64_t)nngp_bf_grad_aniso_workspace_bytes(rows, (int32_t)m, (int32_t)d);
+    auto ws = at::empty({need > 256 ? need : 256}, f64.dtype(at::kByte));
+    check_rc(nngp_bf_grad_aniso(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order),
+                                rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi.data(), tau2,
+                                values.data_ptr<double>(), want_rows ? G.data_ptr<double>() : nullptr,
+                                p.data_ptr<double>(), g.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(),
+                                stream(coords)),
+             "nngp_bf_grad_aniso");
+    return {p, g, G};
+}
+
 // the factors and their phi-derivatives (nngp_bf_dphi): (B (rows, m), F (rows,), dB (rows, m), dF (rows,), partials (4,))
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_dphi(
     const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
@@ -748,6 +778,8 @@ TORCH_LIBRARY(nngp, m) {
           "Tensor? cert=None, Tensor? cert_info=None) -> ()");
     m.def("bf_grad(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2, "
           "Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_grad_aniso(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float[] phi, "
+          "float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_dphi(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2) "
           "-> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("bf_fisher(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2, "
@@ -771,6 +803,7 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_out", &bf_sweep_out);
     m.impl("bf_cross", &bf_cross);
     m.impl("bf_grad", &bf_grad);
+    m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_dphi", &bf_dphi);
     m.impl("bf_fisher", &bf_fisher);
     m.impl("row_order", &row_order);

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .nngp import Covariance, _default_device, _raise_on_bad
+from .nngp import AnisotropicCovariance, Covariance, _default_device, _raise_on_bad
 
 # Rows per level up to which consecutive levels share one single-workgroup launch (chosen from the
 # fuse_width sweep of tools/bench_factor.py at N = 1e6, m = 15)
@@ -28,6 +28,9 @@ DEFAULT_FUSE_WIDTH = 64
 
 def _check_cov(cov) -> Covariance:
     if not isinstance(cov, Covariance):
+        if isinstance(cov, AnisotropicCovariance):
+            raise TypeError("NNGPFactor does not serve an AnisotropicCovariance (per-axis ranges); it takes a "
+                            "pynngp_amd.Covariance")
         if callable(cov):
             raise NotImplementedError("NNGPFactor takes a fused covariance kind (pynngp_amd.Covariance); a callable "
                                       "covariance is not served")

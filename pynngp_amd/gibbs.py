@@ -138,8 +138,9 @@ class SeqNNGP:
         # re-run the caller's code on every joint block); B / F come from one covariance-blocks sweep
         self._custom = None
         if cov is not None:
-            from .nngp import CallableCovariance
+            from .nngp import CallableCovariance, _refuse_aniso
 
+            _refuse_aniso(cov, "the Gibbs sampler")  # (it is callable, but its ranges would never be sampled)
             fn = cov.fn if isinstance(cov, CallableCovariance) else cov
             if not callable(fn):
                 raise TypeError("cov must be a callable cov(a, b) or a CallableCovariance")

@@ -45,7 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .nngp import Covariance, NNGPNumericalError, _default_device, _raise_on_bad
+from .nngp import AnisotropicCovariance, Covariance, NNGPNumericalError, _default_device, _raise_on_bad
 
 CHECK_EVERY = 8  # CG iterations between host synchronisations
 DEFAULT_BATCH = _lib.LATENT_MAX_RHS  # right-hand sides per batched call where the caller does not say
@@ -102,6 +102,9 @@ def lanczos_quadrature(alpha, beta, f=np.log) -> float:
 
 def _check_cov(cov) -> Covariance:
     if not isinstance(cov, Covariance):
+        if isinstance(cov, AnisotropicCovariance):
+            raise TypeError("LatentPosterior does not serve an AnisotropicCovariance (per-axis ranges); it takes a "
+                            "pynngp_amd.Covariance")
         if callable(cov):
             raise NotImplementedError("LatentPosterior takes a fused covariance kind (pynngp_amd.Covariance); a "
                                       "callable covariance is not served")

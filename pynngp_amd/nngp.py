@@ -107,6 +107,72 @@ class Covariance:
         return e
 
 
+_ANISO_KINDS = ("exponential", "matern32", "matern52", "gaussian", "spherical")
+
+
+@dataclasses.dataclass(frozen=True)
+class AnisotropicCovariance:
+    """A fused kind of :class:`Covariance` with one decay per axis: u = sqrt(sum_k (phi_k (a_k - b_k))^2)
+    (geometric anisotropy along the axes; space x time, covariates as extra coordinates).  ``phi`` has one positive
+    entry per coordinate column; kinds ``exponential`` .. ``spherical``.  The model equals the isotropic one at
+    phi = 1 on the coordinates scaled column by column (:meth:`scaled`), which is how the forward sweeps run it;
+    the gradient in (sigma2, phi_1 .. phi_dim, tau2) comes from ``nngp_bf_grad_aniso``.  Called as ``cov(a, b)`` on
+    coordinate rows it returns the cross-covariance matrix without the nugget."""
+
+    kind: str
+    sigma2: float
+    phi: tuple
+    tau2: float = 0.0
+
+    def __post_init__(self):
+        if self.kind not in _ANISO_KINDS:
+            raise ValueError(f"AnisotropicCovariance serves the kinds {_ANISO_KINDS}, got {self.kind!r}")
+        try:
+            phi = tuple(float(p) for p in self.phi)
+        except TypeError:
+            raise ValueError("phi must be a sequence with one decay per coordinate axis") from None
+        if not 1 <= len(phi) <= _lib.MAX_DIM:
+            raise ValueError(f"phi must have 1 .. {_lib.MAX_DIM} entries (one per coordinate axis), got {len(phi)}")
+        if not all(p > 0 and math.isfinite(p) for p in phi):
+            raise ValueError(f"every phi_k must be positive and finite, got {phi}")
+        if not (self.sigma2 > 0 and math.isfinite(self.sigma2) and self.tau2 >= 0 and math.isfinite(self.tau2)):
+            raise ValueError("need sigma2 > 0, tau2 >= 0 (finite)")
+        object.__setattr__(self, "phi", phi)
+
+    nu = None
+    nu_arg = None
+
+    @property
+    def dim(self) -> int:
+        return len(self.phi)
+
+    @property
+    def theta(self):
+        return (float(self.sigma2), *self.phi, float(self.tau2))
+
+    def replace(self, **kw) -> "AnisotropicCovariance":
+        return dataclasses.replace(self, **kw)
+
+    def scaled(self):
+        """``(Covariance(kind, sigma2, 1.0, tau2), phi_vec)``: the isotropic covariance on ``coords * phi_vec``."""
+        return Covariance(self.kind, self.sigma2, 1.0, self.tau2), np.array(self.phi, dtype=np.float64)
+
+    def __call__(self, a, b):
+        lib = torch if isinstance(a, torch.Tensor) else np
+        d = self.dim
+        if (a.ndim > 1 and a.shape[-1] != d) or (b.ndim > 1 and b.shape[-1] != d):
+            raise ValueError(f"coordinate rows must have {d} columns (len(phi))")
+        s = torch.tensor(self.phi, dtype=a.dtype, device=a.device) if lib is torch else np.array(self.phi)
+        return self.scaled()[0](a.reshape(-1, d) * s, b.reshape(-1, d) * s)
+
+
+def _refuse_aniso(cov, what: str) -> None:
+    if isinstance(cov, AnisotropicCovariance):
+        raise TypeError(f"{what} does not serve an AnisotropicCovariance (per-axis ranges): it would need the "
+                        "range of every axis; use loglik / profile_loglik / loglik_grad / fit(anisotropic=True), or "
+                        "a Covariance on coordinates you scaled yourself")
+
+
 @dataclasses.dataclass(frozen=True)
 class IsotropicCovariance:
     """A covariance of the caller's own -- the reference's `cov` plug-in (nngp.py:6,12) as any
@@ -386,7 +452,7 @@ def joint_points(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, qcoords: 
     return torch.cat([xn, xi[:, None, :]], dim=1)
 
 
-CovLike = Union[Covariance, IsotropicCovariance, CallableCovariance, Callable, None]
+CovLike = Union[Covariance, AnisotropicCovariance, IsotropicCovariance, CallableCovariance, Callable, None]
 
 
 def _sweep_any(cv, coords, nbr, i0=0, values=None, want_bf=True, algo="auto", order=None, R=None, qcoords=None,
@@ -442,6 +508,8 @@ class NNGP:
             raise ValueError(f"m={m} outside [0, {_lib.MAX_M}]")
 
         self._init_s()
+        # the metric of the neighbour search: the per-axis decays of an AnisotropicCovariance, else the plain one
+        self._nbr_phi = self._aniso_phi(cov) if isinstance(cov, AnisotropicCovariance) else None
         self._init_wt()
         self._init_ws()
         self._make_s_neighbor_sets()
@@ -486,8 +554,61 @@ class NNGP:
         y = torch.as_tensor(np.asarray(self.y, dtype=np.float64)).to(self.device)
         self.ws = y[idx].mean(dim=1).cpu().numpy()
 
+    # -- per-axis ranges: the model is the isotropic one at phi = 1 on coordinates scaled column by column -------
+    def _aniso_phi(self, cov: AnisotropicCovariance) -> tuple:
+        if cov.dim != self._s_dev.shape[1]:
+            raise ValueError(f"AnisotropicCovariance has {cov.dim} decays for {self._s_dev.shape[1]}-dimensional "
+                             "coordinates (len(phi) must equal the coordinate dimension)")
+        return cov.phi
+
+    def _phi_dev(self, phi) -> torch.Tensor:
+        return torch.tensor(phi, dtype=torch.float64, device=self.device)
+
+    def _scaled_s(self, phi) -> torch.Tensor:
+        """``s * phi`` on the device: one buffer kept for the instance's life, rewritten in place when phi changes.
+        The neighbour search and the sweeps share it, so the returned tensor is valid only until the next call with
+        another phi: callers use it at once (launches are stream-ordered) and do not keep it."""
+        buf = getattr(self, "_s_scaled", None)
+        if buf is None:
+            buf = self._s_scaled = torch.empty_like(self._s_dev)
+            self._s_scaled_phi = None
+        if self._s_scaled_phi != phi:
+            torch.mul(self._s_dev, self._phi_dev(phi), out=buf)
+            self._s_scaled_phi = phi
+        return buf
+
+    def _sweep_cov(self, cov=None):
+        """``(covariance, reference coordinates)`` of a forward sweep: an :class:`AnisotropicCovariance` runs as
+        its isotropic form at phi = 1 on the scaled copy of ``s``; every other form on ``s`` itself."""
+        c = self.cov if cov is None else cov
+        if isinstance(c, AnisotropicCovariance):
+            return c.scaled()[0], self._scaled_s(self._aniso_phi(c))
+        return self._covariance(c), self._s_dev
+
+    def _query_scale(self, cov, q: torch.Tensor) -> torch.Tensor:
+        c = self.cov if cov is None else cov
+        return q * self._phi_dev(self._aniso_phi(c)) if isinstance(c, AnisotropicCovariance) else q
+
+    def rebuild_neighbors(self, cov=None):
+        """Rebuild the neighbour sets in the metric of ``cov`` (default ``self.cov``): the existing search on the
+        coordinates scaled by an :class:`AnisotropicCovariance`'s decays, on the coordinates themselves for any other
+        covariance.  Clears the kept factors and covariance blocks."""
+        c = self.cov if cov is None else cov
+        self._nbr_phi = self._aniso_phi(c) if isinstance(c, AnisotropicCovariance) else None
+        self._make_s_neighbor_sets()
+        self._make_t_neighbor_sets()
+        self._B = self._F = None
+        self._blk_cache = None
+        self._latent = self._latent_ref = self._factor = None
+
+    def _nbr_coords(self, x: torch.Tensor, own: bool = False) -> torch.Tensor:
+        """``x`` in the neighbour search's metric (``own``: x is ``s`` itself, whose scaled copy is kept)."""
+        if self._nbr_phi is None:
+            return x
+        return self._scaled_s(self._nbr_phi) if own else x * self._phi_dev(self._nbr_phi)
+
     def _make_s_neighbor_sets(self):
-        self.nbr = _lib.knn_prior(self._s_dev, self.m)  # int32 (N, m) on the device, -1 padded
+        self.nbr = _lib.knn_prior(self._nbr_coords(self._s_dev, True), self.m)  # int32 (N, m), -1 padded
         # Z-order visiting order + neighbour rows in that order, for the sweeps (speed only)
         self._order, self._nbr_sorted = _lib.row_order(self._s_dev, nbr=self.nbr)
         self._Ns = None
@@ -510,7 +631,8 @@ class NNGP:
             self.nbr_t = None
             return
         k = min(self.m, self._s_dev.shape[0])
-        self.nbr_t = _lib.knn_query(self._s_dev, self._t_dev, k) if k > 0 else torch.empty(
+        self.nbr_t = _lib.knn_query(self._nbr_coords(self._s_dev, True), self._nbr_coords(self._t_dev), k) \
+            if k > 0 else torch.empty(
             (self._t_dev.shape[0], 0), dtype=torch.int32, device=self.device)
 
     def _same_sets(self) -> bool:
@@ -556,7 +678,7 @@ class NNGP:
 
             mean, var, _ = regression.universal_kriging(self, cov, X, X_query, values=values, query=query, algo=algo)
             return mean, var
-        cv = self._covariance(cov)
+        cv, sc = self._sweep_cov(cov)
         v = self.ws if values is None else values
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
                             dtype=torch.float64).to(self.device)
@@ -568,14 +690,17 @@ class NNGP:
             q = self._t_dev if query is None else torch.as_tensor(
                 np.ascontiguousarray(query, dtype=np.float64)).to(self.device)
             k = min(self.m, self._s_dev.shape[0])
-            nbr = _lib.knn_query(self._s_dev, q, k)
+            nbr = None
+        q = self._query_scale(cov, q)  # an AnisotropicCovariance: the query points in the scaled coordinates too
+        if nbr is None:
+            nbr = _lib.knn_query(sc, q, k)
         n = q.shape[0]
         if nbr.shape[1] == 0:  # m = 0: the marginal
             if isinstance(cv, Covariance):
                 return np.zeros(n), np.full(n, cv.sigma2 + cv.tau2)
             return np.zeros(n), cv.marginal(q).cpu().numpy()
         R = torch.empty(n, dtype=torch.float64, device=self.device)
-        _, F, p = _sweep_any(cv, self._s_dev, nbr, 0, values=v, algo=algo, R=R, qcoords=q)
+        _, F, p = _sweep_any(cv, sc, nbr, 0, values=v, algo=algo, R=R, qcoords=q)
         _raise_on_bad(p.cpu().numpy())
         return (-R).cpu().numpy(), F.cpu().numpy()
 
@@ -585,6 +710,7 @@ class NNGP:
         ``cov(a, b)`` becomes a :class:`CallableCovariance` (one per callable, so its evaluation mode
         is probed once)."""
         c = self.cov if cov is None else cov
+        _refuse_aniso(c, "this method")
         if isinstance(c, (Covariance, IsotropicCovariance, CallableCovariance)):
             return c
         if c is None or not callable(c):
@@ -627,7 +753,7 @@ class NNGP:
     def _call_cov(self, a, b):
         if self.cov is None:
             raise TypeError("cov is None")
-        if isinstance(self.cov, (Covariance, IsotropicCovariance)):
+        if isinstance(self.cov, (Covariance, AnisotropicCovariance, IsotropicCovariance)):
             return self.cov(a, b)
         return self.cov(a.cpu().numpy(), b.cpu().numpy())  # the reference's rows are numpy (nngp.py:7,31)
 
@@ -636,7 +762,7 @@ class NNGP:
         """C_{N(s_i)} (nngp.py:78-82), with the nugget on the diagonal for a Covariance."""
         x = self._s_dev[self._nbr_idx(i)]
         c = self._call_cov(x, x)
-        if isinstance(self.cov, (Covariance, IsotropicCovariance)) and self.cov.tau2 > 0:
+        if isinstance(self.cov, (Covariance, AnisotropicCovariance, IsotropicCovariance)) and self.cov.tau2 > 0:
             c = c + self.cov.tau2 * torch.eye(x.shape[0], dtype=c.dtype, device=c.device)
         return c.cpu().numpy() if isinstance(c, torch.Tensor) else c
 
@@ -649,13 +775,13 @@ class NNGP:
         """C_{s_i, s_i} (nngp.py:92-96), with the nugget for a Covariance."""
         x = self._s_dev[i][None, :]
         c = self._call_cov(x, x)
-        if isinstance(self.cov, (Covariance, IsotropicCovariance)):
+        if isinstance(self.cov, (Covariance, AnisotropicCovariance, IsotropicCovariance)):
             c = c + self.cov.tau2
         return c.cpu().numpy() if isinstance(c, torch.Tensor) else c
 
     def _row_bf(self, i):
-        cv = self._covariance()
-        B, F, p = _sweep_any(cv, self._s_dev, self.nbr[i: i + 1], int(i))
+        cv, sc = self._sweep_cov()
+        B, F, p = _sweep_any(cv, sc, self.nbr[i: i + 1], int(i))
         _raise_on_bad(p.cpu().numpy())
         k = min(int(i), self.m)
         return B[0, :k].cpu().numpy(), float(F[0].item())
@@ -671,8 +797,8 @@ class NNGP:
     # -- whole-field sweep -----------------------------------------------------
     def compute_BF(self, algo: str = "auto"):
         """All B (N, m) and F (N,) as device tensors (one fused sweep)."""
-        cv = self._covariance()
-        B, F, p = _sweep_any(cv, self._s_dev, self._nbr_sorted, 0, algo=algo, order=self._order,
+        cv, sc = self._sweep_cov()
+        B, F, p = _sweep_any(cv, sc, self._nbr_sorted, 0, algo=algo, order=self._order,
                              blocks=self._field_blocks(cv))
         _raise_on_bad(p.cpu().numpy())
         self._B, self._F = B, F
@@ -688,13 +814,13 @@ class NNGP:
 
     def loglik(self, values=None, cov: Optional[Covariance] = None, algo: str = "auto") -> float:
         """NNGP log density of ``values`` (default ``y``): -1/2 sum [log 2pi + log F + r^2/F]."""
-        cv = self._covariance(cov)
+        cv, sc = self._sweep_cov(cov)
         v = self.y if values is None else values
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
                             dtype=torch.float64).to(self.device)
         if v.dim() != 1 or v.shape[0] != self.nbr.shape[0]:
             raise ValueError(f"loglik needs one value per location ({self.nbr.shape[0]}, 1-D)")
-        _, _, p = _sweep_any(cv, self._s_dev, self._nbr_sorted, 0, values=v, qvalues=v, want_bf=False, algo=algo,
+        _, _, p = _sweep_any(cv, sc, self._nbr_sorted, 0, values=v, qvalues=v, want_bf=False, algo=algo,
                              order=self._order, blocks=self._field_blocks(cv))
         ph = p.cpu().numpy()
         _raise_on_bad(ph)
@@ -721,6 +847,7 @@ class NNGP:
         ``predict(query, X_query)``, the Student-t predictive (location, scale, 2 a degrees of freedom)."""
         from . import regression
 
+        _refuse_aniso(self.cov, "conjugate")
         return regression.conjugate(self, kind, phi, alpha, X, prior=prior, nu=nu, values=values, algo=algo)
 
     def conjugate_grid(self, phis, alphas, kind: str, X, prior: Optional[dict] = None, nu: Optional[float] = None,
@@ -729,6 +856,7 @@ class NNGP:
         ``alpha`` and ``best``, the fit there."""
         from . import regression
 
+        _refuse_aniso(self.cov, "conjugate_grid")
         return regression.conjugate_grid(self, phis, alphas, kind, X, prior=prior, nu=nu, values=values, algo=algo)
 
     def profile_loglik(self, cov: Covariance, values=None, mean: str = "constant", algo: str = "auto", X=None):
@@ -755,11 +883,11 @@ class NNGP:
         n = v.shape[0]
         ry = torch.empty(n, dtype=torch.float64, device=self.device)
         r1 = torch.empty_like(ry)
-        cov = self._covariance(cov)
+        cov, sc = self._sweep_cov(cov)
         kw = dict(algo=algo, order=self._order, blocks=self._field_blocks(cov))
-        _, F, py = _sweep_any(cov, self._s_dev, self._nbr_sorted, 0, values=v, qvalues=v, R=ry, **kw)
+        _, F, py = _sweep_any(cov, sc, self._nbr_sorted, 0, values=v, qvalues=v, R=ry, **kw)
         ones = torch.ones_like(v)
-        _, _, p1 = _sweep_any(cov, self._s_dev, self._nbr_sorted, 0, values=ones, qvalues=ones, R=r1, **kw)
+        _, _, p1 = _sweep_any(cov, sc, self._nbr_sorted, 0, values=ones, qvalues=ones, R=r1, **kw)
         s_y1 = torch.sum(ry * r1 / F)
         sums = torch.stack([py[0], py[1], p1[1], s_y1, py[2], py[3]]).cpu().numpy()
         _raise_on_bad(np.array([0.0, 0.0, sums[4], sums[5]]))
@@ -768,12 +896,18 @@ class NNGP:
         quad = qyy - 2.0 * mu * qy1 + mu * mu * q11
         return -0.5 * (n * LOG_2PI + logF + quad), float(mu)
 
-    def _grad_cov(self, cov) -> Covariance:
+    def _grad_cov(self, cov, aniso: bool = True):
         """The covariance of a gradient sweep: a fused kind other than the general-nu Matern, m >= 1."""
-        cv = self._covariance(cov)
-        if not isinstance(cv, Covariance):
+        cv = self.cov if cov is None else cov
+        if isinstance(cv, AnisotropicCovariance):
+            self._aniso_phi(cv)
+        else:
+            cv = self._covariance(cov)
+        if not isinstance(cv, (Covariance, AnisotropicCovariance)):
             raise TypeError("the analytic gradient needs a Covariance of a fused kind (exponential, matern32, "
                             f"matern52, gaussian, spherical), not {type(cv).__name__}")
+        if not aniso:
+            _refuse_aniso(cv, "the Fisher information (fisher_information, fit(method='fisher'), stderr=True)")
         if cv.kind == "matern":
             raise NotImplementedError("the analytic gradient does not serve the general-nu matern kind")
         if not 1 <= self.m <= _lib.GRAD_MAX_M:
@@ -790,9 +924,17 @@ class NNGP:
 
     def loglik_grad(self, values=None, cov: Optional[Covariance] = None):
         """:meth:`loglik` and its analytic gradient in (sigma2, phi, tau2) from one fused gradient sweep
-        (``nngp_bf_grad``): ``(loglik, grad)`` with ``grad`` a float64 ndarray (3,)."""
+        (``nngp_bf_grad``): ``(loglik, grad)`` with ``grad`` a float64 ndarray (3,).  An
+        :class:`AnisotropicCovariance` gives the gradient in (sigma2, phi_1 .. phi_dim, tau2), (dim + 2,), from one
+        ``nngp_bf_grad_aniso`` sweep on the raw coordinates."""
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
+        if isinstance(cv, AnisotropicCovariance):
+            p, g, _ = _lib.bf_grad_aniso(self._s_dev, self._nbr_sorted, 0, cv.kind, cv.sigma2, cv.phi, cv.tau2, v,
+                                         order=self._order)
+            h = torch.cat([p, g]).cpu().numpy()
+            _raise_on_bad(h[:4])
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:].copy()
         p, g, _ = _lib.bf_grad(self._s_dev, self._nbr_sorted, 0, cv.kind, cv.sigma2, cv.phi, cv.tau2, v,
                                order=self._order)
         h = torch.cat([p, g]).cpu().numpy()
@@ -852,7 +994,7 @@ class NNGP:
         1 <= m <= 32 only."""
         from . import fisher
 
-        cv = self._grad_cov(cov)
+        cv = self._grad_cov(cov, aniso=False)
         if mean not in ("zero", "constant", "linear"):
             raise ValueError("mean must be 'constant', 'zero' or 'linear'")
         if mean == "linear" and X is None:
@@ -960,7 +1102,8 @@ class NNGP:
 
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
-            gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None):
+            gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None,
+            anisotropic: bool = False, reneighbor: int = 0):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -986,17 +1129,46 @@ class NNGP:
         ``gradient=True``; no ``reml``.
 
         ``stderr=True`` adds ``info``, ``cov_theta`` and ``se`` to any other method's result: one information
-        sweep at the estimate (the same kinds and m)."""
+        sweep at the estimate (the same kinds and m).
+
+        ``anisotropic=True``: one decay per coordinate axis (:class:`AnisotropicCovariance`), L-BFGS-B on the log of
+        (sigma2, phi_1 .. phi_dim, tau2) with :meth:`profile_loglik_grad` (``nngp_bf_grad_aniso``).  ``x0`` =
+        (sigma2, phi, tau2) with ``phi`` one number (used for every axis) or a tuple; ``fix_tau2`` and ``mean`` as
+        above.  The analytic gradient is always used, whatever ``gradient`` says; ``method`` is any scipy method that
+        takes ``jac``; ``tol`` is the gradient tolerance (L-BFGS-B's ``gtol``: it stops once no free log-parameter's
+        derivative exceeds it; default scipy's 1e-5, beside scipy's relative-decrease rule ``ftol``); ``algo`` serves
+        the sweeps that take one (the final ``beta`` and a reneighboured likelihood); ``nu`` is refused (no kind
+        served here has one).  The result carries ``phi`` as a tuple, ``theta`` = (sigma2, *phi, tau2), ``grad``, the
+        gradient in the free log-parameters at the optimiser's last iterate (all zeros, with ``converged`` False,
+        when that iterate was not positive definite) and ``message``, the optimiser's stopping reason.
+        ``reneighbor=r`` runs r further rounds: each calls :meth:`rebuild_neighbors` at the current estimate and
+        restarts the optimiser from it (the likelihood of a round is the one on that round's sets).  No ``stderr``,
+        ``method="fisher"`` or ``reml`` with it."""
         if mean == "linear" and X is None:
             raise ValueError("mean='linear' needs the design matrix X")
         if mean != "linear" and X is not None:
             raise ValueError("X is the design of mean='linear'")
+        if anisotropic:
+            if stderr or method == "fisher":
+                raise NotImplementedError("the Fisher information sweep has no per-axis form: fit(anisotropic=True) "
+                                          "takes neither stderr=True nor method='fisher'")
+            if reml:
+                raise NotImplementedError("the restricted likelihood has no analytic gradient: anisotropic=True "
+                                          "maximises the profile likelihood (reml=False)")
+            if nu is not None:
+                raise ValueError("nu is the smoothness of the general-nu matern kind, which anisotropic=True does not "
+                                 "serve")
+            return self._fit_aniso(kind, x0, mean, fix_tau2, method or "L-BFGS-B", maxiter, X, int(reneighbor), algo,
+                                   tol)
+        if reneighbor:
+            raise ValueError("reneighbor is an option of anisotropic=True")
+        _refuse_aniso(self.cov, "fit without anisotropic=True")
         if method == "fisher" or stderr:  # refused before any sweep, as gradient=True's kinds and m are
             if method == "fisher" and reml:
                 raise NotImplementedError("the restricted likelihood has no analytic gradient or information: "
                                           "method='fisher' maximises the profile likelihood (reml=False)")
             if kind is None:
-                self._grad_cov(None)
+                self._grad_cov(None, aniso=False)
             elif kind == "matern":
                 raise NotImplementedError("the analytic gradient does not serve the general-nu matern kind")
             elif not 1 <= self.m <= _lib.GRAD_MAX_M:
@@ -1088,6 +1260,88 @@ class NNGP:
         return with_stderr({"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"], "n_evals": int(res.nfev),
                             "converged": bool(res.success), **self._fit_beta(X if linear else None, algo)})
 
+    def _fit_aniso(self, kind, x0, mean, fix_tau2, method, maxiter, X, reneighbor: int, algo: str, tol) -> dict:
+        """``fit(anisotropic=True)``: gradient=True's scaffolding over (sigma2, phi_1 .. phi_dim, tau2)."""
+        from scipy.optimize import minimize
+
+        if reneighbor < 0:
+            raise ValueError("reneighbor must be >= 0")
+        dim = self._s_dev.shape[1]
+        base = self.cov if isinstance(self.cov, (Covariance, AnisotropicCovariance)) else None
+        kind = kind or (base.kind if base is not None else "exponential")
+        if x0 is not None:
+            if len(x0) != 3:
+                raise ValueError("x0 must be (sigma2, phi, tau2) with phi one number or one per axis")
+            s0, p0, t0 = x0
+        elif base is not None:
+            s0, p0, t0 = base.sigma2, base.phi, base.tau2
+        else:
+            s0, p0, t0 = 1.0, 10.0, 0.1
+        p0 = tuple(float(p) for p in p0) if np.ndim(p0) else (float(p0),) * dim
+        free_tau = fix_tau2 is None
+        linear = mean == "linear"
+        if linear:
+            from . import regression
+
+            X = regression.design(self, X, self.nbr.shape[0])
+
+        def cov_of(z):
+            return AnisotropicCovariance(kind, math.exp(z[0]), tuple(math.exp(v) for v in z[1:1 + dim]),
+                                         math.exp(z[1 + dim]) if free_tau else float(fix_tau2))
+
+        start = AnisotropicCovariance(kind, float(s0), p0, max(float(t0), 1e-6) if free_tau else float(fix_tau2))
+        self._grad_cov(start)  # refuse a wrong len(phi) or an unsupported m before optimising
+        n_evals = n_grad = 0
+        options, kw = {"maxiter": maxiter}, {}
+        if tol is not None and method == "L-BFGS-B":
+            options["gtol"] = float(tol)  # the gradient rule alone; scipy's tol= would set ftol to it as well
+        elif tol is not None:
+            kw["tol"] = float(tol)
+        for rnd in range(reneighbor + 1):
+            if rnd > 0:
+                self.rebuild_neighbors(start)
+            best, seen, last_failed = {"ll": -math.inf}, {}, [False]
+
+            def obj_grad(z):
+                cv = cov_of(z)
+                try:
+                    ll, mu, g = self.profile_loglik_grad(cv, mean=mean, X=X)
+                except NNGPNumericalError:
+                    last_failed[0] = True
+                    return 1e300, np.zeros(len(z))
+                last_failed[0] = False
+                th = cv.theta
+                gz = np.array([th[k] * g[k] for k in range(len(z))])
+                seen[tuple(z)] = gz
+                if ll > best["ll"]:
+                    best.update(ll=ll, mu=None if linear else mu, cov=cv)
+                return -ll, -gz
+
+            th = start.theta
+            z0 = np.log(np.array(th[:1 + dim + (1 if free_tau else 0)]))
+            res = minimize(obj_grad, z0, jac=True, method=method, options=options, **kw)
+            n_evals += int(res.nfev)
+            n_grad += len(seen)
+            if "cov" not in best:
+                raise NNGPNumericalError("fit(anisotropic=True): no parameter value the optimiser tried was positive "
+                                         "definite")
+            start = best["cov"]
+        self.cov = start
+        self._B = self._F = None
+        if reneighbor > 0:
+            # leave the sets in the estimate's own metric and report the likelihood on them (grad stays the last
+            # round's: the gradient on the sets that round optimised over)
+            self.rebuild_neighbors(start)
+            if linear:
+                best["ll"] = self.gls(start, X, algo=algo).loglik
+            else:
+                best["ll"], best["mu"] = self.profile_loglik(start, mean=mean, algo=algo)
+        return {"theta": start.theta, "sigma2": start.sigma2, "phi": start.phi, "tau2": start.tau2, "mu": best["mu"],
+                "loglik": best["ll"], "grad": -np.asarray(res.jac, dtype=np.float64), "n_evals": n_evals,
+                "n_grad_evals": n_grad, "converged": bool(res.success) and not last_failed[0],
+                "message": str(res.message), "rounds": reneighbor + 1,
+                **self._fit_beta(X if linear else None, algo)}
+
     def _fit_beta(self, X, algo):
         """``beta`` and ``cov_beta`` of a regression fit at the estimate ``self.cov`` (nothing without a design)."""
         if X is None:
@@ -1099,6 +1353,7 @@ class NNGP:
     def _latent_posterior(self, cov, mean: str):
         """The :class:`pynngp_amd.LatentPosterior` of this instance's ``y`` / ``eps`` / neighbour sets at ``cov``
         (kept between calls; a new theta of the same mean is one ``update``)."""
+        _refuse_aniso(self.cov if cov is None else cov, "the latent posterior")
         if not self._same_sets():
             raise NotImplementedError("the latent posterior serves refType == 'S=T' (the field on the data "
                                       f"locations), not {self.refType!r}")
@@ -1132,6 +1387,7 @@ class NNGP:
         ``"zero"`` takes y as centred; NaN in ``y`` = unobserved; ``eps`` as :meth:`latent_mean`.  Its ``mean`` /
         ``sample`` / ``marginal_variance`` take ``where="data"`` or ``"ref"``, and ``predict(query)`` gives the
         mean, variance and draws at new locations."""
+        _refuse_aniso(self.cov if cov is None else cov, "the latent posterior")
         if self._same_sets():
             return self._latent_posterior(cov, mean)
         if mean not in ("constant", "zero"):
@@ -1215,6 +1471,7 @@ class NNGP:
         one ``update``."""
         from .factor import NNGPFactor, _check_cov
 
+        _refuse_aniso(self.cov if cov is None else cov, "the prior factor (prior_factor, simulate)")
         cv = _check_cov(self.cov if cov is None else cov)
         held = getattr(self, "_factor", None)
         key = self.nbr if self._same_sets() else self.s
@@ -1287,6 +1544,7 @@ class NNGP:
         y = np.asarray(self.y, dtype=np.float64)
         if y.ndim != 1:
             raise ValueError("oneSample needs one response per location (1-D y)")
+        _refuse_aniso(self.cov, "the Gibbs sampler (oneSample)")
         if getattr(self, "_sampler", None) is None:
             from .gibbs import SeqNNGP
 

@@ -109,6 +109,12 @@ def _register_fakes() -> None:
         return (coords.new_empty((4,)), coords.new_empty((3,)),
                 coords.new_empty((nbr.shape[0] if want_rows else 0, 3)))
 
+    @fake("bf_grad_aniso")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
+        k = coords.shape[1] + 2
+        return (coords.new_empty((4,)), coords.new_empty((k,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, k)))
+
     @fake("bf_fisher")
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
         rows = nbr.shape[0] if want_rows else 0

@@ -178,10 +178,10 @@ def whitened_gram(nngp, cov, X: torch.Tensor, v: torch.Tensor, algo: str = "auto
     """One B/F-writing sweep at ``cov`` and one ``nngp_whiten_gram`` on ``[v, X]``: ``(sum log F, G (host), B, F)``."""
     from .nngp import _raise_on_bad, _sweep_any
 
-    cv = nngp._covariance(cov)
+    cv, sc = nngp._sweep_cov(cov)  # an AnisotropicCovariance: its isotropic form on the scaled coordinates
     if nngp.m < 1:
         raise ValueError("the regression needs m >= 1")
-    B, F, p = _sweep_any(cv, nngp._s_dev, nngp._nbr_sorted, 0, algo=algo, order=nngp._order,
+    B, F, p = _sweep_any(cv, sc, nngp._nbr_sorted, 0, algo=algo, order=nngp._order,
                          blocks=nngp._field_blocks(cv))
     V = torch.cat([v[:, None], X], dim=1).contiguous()
     _, G = _lib.whiten_gram(nngp._nbr_sorted, B, F, V, 0, order=nngp._order)
@@ -213,10 +213,12 @@ def cross_terms(nngp, cv, q: torch.Tensor, resid: torch.Tensor, X: torch.Tensor,
     cross mode with F = 1 (device tensors); the neighbours are the m nearest reference points."""
     from .nngp import _raise_on_bad, _sweep_any
 
-    k = min(nngp.m, nngp._s_dev.shape[0])
-    nbr = _lib.knn_query(nngp._s_dev, q, k)
+    q = nngp._query_scale(cv, q)
+    cv, sc = nngp._sweep_cov(cv)
+    k = min(nngp.m, sc.shape[0])
+    nbr = _lib.knn_query(sc, q, k)
     R = torch.empty(q.shape[0], dtype=torch.float64, device=nngp.device)
-    Bq, Fq, p = _sweep_any(cv, nngp._s_dev, nbr, 0, values=resid, algo=algo, R=R, qcoords=q)
+    Bq, Fq, p = _sweep_any(cv, sc, nbr, 0, values=resid, algo=algo, R=R, qcoords=q)
     _raise_on_bad(p.cpu().numpy())
     h, _ = _lib.whiten_gram(nbr, Bq, torch.ones_like(Fq), X, Vq=Xq, want_gram=False)
     return -R, Fq, h
@@ -225,7 +227,11 @@ def cross_terms(nngp, cv, q: torch.Tensor, resid: torch.Tensor, X: torch.Tensor,
 def universal_kriging(nngp, cov, X, X_query, values=None, query=None, algo: str = "auto"):
     """Universal kriging at ``query``: mean x_q' beta + B_q (y - X beta)_N and variance F_q + h_q' cov_beta h_q, the
     second term the uncertainty of the GLS beta.  Returns numpy ``(mean, var, GLSResult)``."""
-    cv = nngp._covariance(cov)
+    from .nngp import AnisotropicCovariance
+
+    cv = nngp.cov if cov is None else cov
+    if not isinstance(cv, AnisotropicCovariance):
+        cv = nngp._covariance(cov)
     v = nngp._values_dev(values)
     Xd = design(nngp, X, v.shape[0])
     q = _query(nngp, query)
