@@ -87,7 +87,8 @@ const char *nngp_version(void);
  * Revision 4 (library 0.4.0): the pair plans are per wave (a new plan format, m <= 17) and their info
  * array holds 10 words (NNGP_PLAN_INFO_LEN: + the nbr / order pointers, checked by nngp_bf_sweep_plan).
  * Added within revision 4 (nothing earlier moved): the gradient sweep nngp_bf_grad_workspace_bytes /
- * nngp_bf_grad and its per-axis form nngp_bf_grad_aniso_workspace_bytes / nngp_bf_grad_aniso; the
+ * nngp_bf_grad, its per-axis form nngp_bf_grad_aniso_workspace_bytes / nngp_bf_grad_aniso and its
+ * general-nu Matern form nngp_bf_grad_matern_workspace_bytes / nngp_bf_grad_matern with nngp_matern_eval_d; the
  * latent-field posterior nngp_precision_workspace_bytes / nngp_precision_apply /
  * nngp_precision_sqrt_t_apply / nngp_latent_cg_workspace_bytes / nngp_latent_cg; their forms for several
  * right-hand sides nngp_precision_batch_workspace_bytes / nngp_precision_apply_batch /
@@ -273,6 +274,37 @@ int nngp_bf_grad_aniso(const double *coords, int64_t n_points, int32_t dim, cons
                        const double *phi /* host, dim entries */, double tau2, const double *values, double *G,
                        double *partials, double *grad /* dim + 2 */, void *workspace, size_t workspace_bytes,
                        void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Gradient sweep for the general-smoothness Matern kind (NNGP_COV_MATERN), with the smoothness as a fourth
+ * parameter: the analytic gradient of the NNGP log-likelihood in (sigma2, phi, tau2, nu), one fused sweep over
+ * locations i0 .. i0 + n_rows - 1 (added within revision 4; coords, nbr, order, i0 and values as nngp_bf_grad).
+ * With rho_nu(u) = 2^(1-nu) / Gamma(nu) u^nu K_nu(u) and u = phi d,
+ *   dC_ab / dphi = sigma2 h(u) / phi,  h(u) = u rho'(u) = -2^(1-nu) / Gamma(nu) u^(nu+1) K_{nu-1}(u),
+ *   dC_ab / dnu  = sigma2 n(u),        n(u) = d rho_nu(u) / d nu,
+ * both exactly 0 for coincident points.  The sweep reads rho, h and n from per-launch tables in t = u^2 that it
+ * builds in the workspace, stream-ordered before the sweep.
+ *   partials[4]  : as nngp_bf_grad
+ *   grad[4]      = sum_i d l_i / d (sigma2, phi, tau2, nu), a fixed-order fold: bit-reproducible run to run
+ *   G            : NULL or (n_rows, 4), the term of location i0 + r in row r (r = order[t] for nbr row t, else t)
+ * Rows flagged in partials[2] get NaN in G, and either flag makes grad meaningless (nngp_check_partials).
+ * Slots without a point (-1 padding) and out-of-range indices contribute exactly 0 to every sum.
+ * 1 <= m <= 32 and 1 <= dim <= 3 (else NNGP_EUNSUP).  nu outside (0, 50], sigma2 <= 0, phi <= 0, tau2 < 0,
+ * values == NULL or a short workspace: NNGP_EINVAL.  workspace: nngp_bf_grad_matern_workspace_bytes(n_rows, m)
+ * bytes (the block records and room for the three tables; 0 for an unsupported m or n_rows < 0), 256-B aligned,
+ * no initialisation needed; it may be reused across calls with different nu.
+ *
+ * nngp_matern_eval_d: h[k] = u rho'(u) and dnu[k] = d rho / d nu at n arguments u >= 0, elementwise, read through
+ * the same derivative table and lookup as the sweep (0 < nu <= 50, else NNGP_EINVAL): a building block, and the
+ * handle by which the tables are tested.  The table lives in stream-ordered memory (hipMallocAsync /
+ * hipFreeAsync on `stream`) for the duration of the call's kernels; no host synchronisation.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_grad_matern_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_grad_matern(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                        int64_t n_rows, int32_t m, int64_t i0, double sigma2, double phi, double tau2, double nu,
+                        const double *values, double *G /* NULL or (n_rows, 4) */, double *partials /* 4 */,
+                        double *grad /* 4 */, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_matern_eval_d(const double *u, int64_t n, double nu, double *h /* u rho'(u) */, double *dnu, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Wave pair plans: the same sweep with every covariance a wavefront's locations share evaluated once.

@@ -8,7 +8,8 @@ it -- the first call that needs it does, and fails loudly if it is missing.
 from ._lib import NNGPExtensionError, LIB_PATH, version  # noqa: F401
 from .nngp import NNGP, CallableCovariance, Covariance, IsotropicCovariance, NNGPNumericalError  # noqa: F401
 from .nngp import AnisotropicCovariance  # noqa: F401
-from .autograd import loglik  # noqa: F401
+from .autograd import loglik, loglik_matern  # noqa: F401
+from .nngp import MaternCovariance  # noqa: F401
 from .sweep import ShardedLogLik, shard_range, combine_partials  # noqa: F401
 from .gibbs import SeqNNGP, SeqNNGPChains, Priors  # noqa: F401
 from .gibbs_sharded import ShardedSeqNNGP  # noqa: F401

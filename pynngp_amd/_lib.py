@@ -72,6 +72,9 @@ SYMBOLS = (
     "nngp_bf_grad",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
+    "nngp_bf_grad_matern_workspace_bytes",
+    "nngp_bf_grad_matern",
+    "nngp_matern_eval_d",
     "nngp_bf_dphi_workspace_bytes",
     "nngp_bf_dphi",
     "nngp_bf_fisher_workspace_bytes",
@@ -173,6 +176,12 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_grad_aniso_workspace_bytes.restype = SZ
     lib.nngp_bf_grad_aniso.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_aniso.restype = ctypes.c_int
+    lib.nngp_bf_grad_matern_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_grad_matern_workspace_bytes.restype = SZ
+    lib.nngp_bf_grad_matern.argtypes = [P, I64, I32, P, P, I64, I32, I64, D, D, D, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_matern.restype = ctypes.c_int
+    lib.nngp_matern_eval_d.argtypes = [P, I64, D, P, P, P]
+    lib.nngp_matern_eval_d.restype = ctypes.c_int
     lib.nngp_bf_dphi_workspace_bytes.argtypes = [I64, I32]
     lib.nngp_bf_dphi_workspace_bytes.restype = SZ
     lib.nngp_bf_dphi.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
@@ -777,6 +786,64 @@ def bf_grad_aniso(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, s
                                   _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_grad_aniso")
     return partials, grad, G
+
+
+def bf_grad_matern(coords: torch.Tensor, nbr: torch.Tensor, i0: int, sigma2: float, phi: float, tau2: float,
+                   nu: float, values: torch.Tensor, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Gradient sweep of the general-smoothness Matern kind (``nngp_bf_grad_matern``, include/nngp.h) over rows
+    ``i0 .. i0 + len(nbr)``, with the smoothness as a fourth parameter.
+
+    Returns ``(partials, grad, G)``: the four partials of :func:`bf_sweep`, ``grad`` = the summed
+    d loglik / d (sigma2, phi, tau2, nu) (float64 (4,), fixed fold order) and, with ``want_rows``, ``G`` (rows, 4)
+    (NaN in rows flagged in partials[2]).  Stream-ordered on torch's current stream; no host synchronisation.
+    0 < nu <= 50, 1 <= m <= 32; ``order`` as in :func:`bf_sweep`.  ``workspace`` (records and the three tables) may
+    be reused across calls and across nu.
+    """
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if values is None or values.dtype != torch.float64 or values.shape != (coords.shape[0],):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    rows, m = nbr.shape
+    _check_kind("matern", nu)
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the matern gradient sweep serves 1 <= m <= {GRAD_MAX_M} (m={m})")
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_grad_matern_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    if workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous tensor on the sweep's device")
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(4, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, 4), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_matern(_ptr(coords), coords.shape[0], coords.shape[1], _ptr(nbr), _ptr(order), rows, m, i0,
+                                   float(sigma2), float(phi), float(tau2), float(nu), _ptr(values), _ptr(G),
+                                   _ptr(partials), _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_grad_matern")
+    return partials, grad, G
+
+
+def matern_eval_d(u: torch.Tensor, nu: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(h, dnu)``: u rho'(u) and d rho / d nu of the Matern correlation, elementwise on the GPU through the
+    gradient sweep's derivative table (``nngp_matern_eval_d``; u >= 0)."""
+    if u.dtype != torch.float64:
+        raise ValueError("u must be float64")
+    dev = _require_gpu(u)
+    _check_kind("matern", nu)
+    u = u.contiguous()
+    h = torch.empty_like(u)
+    dnu = torch.empty_like(u)
+    _check(load().nngp_matern_eval_d(_ptr(u), u.numel(), float(nu), _ptr(h), _ptr(dnu), _stream(dev)),
+           "nngp_matern_eval_d")
+    return h, dnu
 
 
 def bf_dphi(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,

@@ -81,6 +81,67 @@ class _LogLikAniso(torch.autograd.Function):
         return None, None, gtheta, gvalues, None, None
 
 
+class _LogLikMatern(torch.autograd.Function):
+    """theta = (sigma2, phi, tau2, nu): the general-nu Matern sweep (``torch.ops.nngp.bf_grad_matern``)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_matern(coords, nbr, order, 0, th[0], th[1], th[2], th[3], values.detach(),
+                                                False)
+        ctx.save_for_backward(coords, nbr, values, g)
+        ctx.meta = (order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g = ctx.saved_tensors
+        order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLik: one ordinary sweep (B, F, R) of the matern kind at nu
+            rows, m = nbr.shape
+            R = torch.empty(rows, dtype=torch.float64, device=coords.device)
+            B, F, _ = _lib.bf_sweep(coords, nbr, 0, "matern", th[0], th[1], th[2], values=values.detach(), order=order,
+                                    R=R, nu=th[3])
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None
+
+
+def loglik_matern(coords, nbr, theta, values, order=None):
+    """NNGP log-likelihood of ``values`` on S = T under the general-smoothness Matern covariance at ``theta`` =
+    (sigma2, phi, tau2, nu), a float64 (4,) tensor, differentiable in all four entries of ``theta`` and, when
+    ``values.requires_grad``, in ``values``.
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_matern``) and synchronises with the host as
+    :func:`loglik` does; backward returns ``grad_out * grad`` for theta with no further launch.  ``nbr`` (N, m) int32
+    with 1 <= m <= 32, 0 < nu <= 50; the not-PD and bad-index flags raise.
+    """
+    if theta.dtype != torch.float64 or theta.shape != (4,):
+        raise ValueError("theta must be a float64 (4,) tensor (sigma2, phi, tau2, nu)")
+    if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
+        raise NotImplementedError(f"loglik_matern's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
+    if nbr.shape[0] != coords.shape[0]:
+        raise ValueError("loglik_matern is an S = T sweep: one nbr row per location")
+    _lib._check_kind("matern", float(theta.detach()[3]))
+    ll, p = _LogLikMatern.apply(coords, nbr, theta, values, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 def loglik(coords, nbr, theta, values, kind, order=None):
     """NNGP log-likelihood of ``values`` on S = T at ``theta`` = (sigma2, phi, tau2), a float64 (3,) tensor,
     differentiable in ``theta`` and, when ``values.requires_grad``, in ``values``.

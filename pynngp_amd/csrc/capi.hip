@@ -1,5 +1,6 @@
 // C ABI of libnngp_hip.so (declared in include/nngp.h): argument checking,
-// workspace carving and launch.  No host synchronisation, allocation or free.
+// workspace carving and launch.  No host synchronisation, allocation or free (nngp_matern_eval_d alone, which
+// has no workspace argument, takes its table from the stream-ordered allocator).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -12,6 +13,7 @@
 #include "nbr_cert.h"
 #include "bf_grad.h"
 #include "bf_grad_aniso.h"
+#include "bf_grad_matern.h"
 #include "bf_dphi.h"
 #include "bf_fisher.h"
 #include "latent.h"
@@ -259,6 +261,45 @@ int nngp_bf_grad_aniso(const double* coords, int64_t n_points, int32_t dim, cons
     for (int k = 0; k < dim; ++k) a.phi[k] = phi[k];
     hipError_t e = nngp::bf_grad_aniso_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_aniso launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_grad_matern_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    // block records (at least one), then the rho table and the derivative table at their largest extent
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * nngp::kGradRec * sizeof(double)) + align256(3 * NNGP_MT_BYTES(NNGP_MT_MAX_OCT));
+}
+
+int nngp_bf_grad_matern(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                        int64_t n_rows, int32_t m, int64_t i0, double sigma2, double phi, double tau2, double nu,
+                        const double* values, double* G, double* partials, double* grad, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (values == nullptr || partials == nullptr || grad == nullptr)
+        return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the matern gradient sweep serves 1 <= m <= 32 (m=%d)", m);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_points)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_points);
+    if (!(sigma2 > 0.0) || !(phi > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(phi) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, phi > 0, tau2 >= 0 (finite)");
+    if (!(nu > 0.0 && nu <= NNGP_MATERN_NU_MAX))
+        return fail(NNGP_EINVAL, "the matern kind needs 0 < nu <= %g (nu=%g)", NNGP_MATERN_NU_MAX, nu);
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_grad_matern_workspace_bytes(n_rows, m);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    int e0, noct;
+    if (!nngp::matern_table_extent(nu, &e0, &noct))
+        return fail(NNGP_EUNSUP, "matern nu=%g needs %d table octaves (> %d)", nu, noct, NNGP_MT_MAX_OCT);
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    nngp::GradMaternArgs a{coords, n_points, nbr, order, n_rows, i0, m, dim, sigma2, phi, tau2, nu, values, G,
+                           (double*)workspace,
+                           (double*)((char*)workspace + align256((size_t)nb * nngp::kGradRec * sizeof(double))), {}};
+    hipError_t e = nngp::bf_grad_matern_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_matern launch");
     return NNGP_OK;
 }
 
@@ -536,6 +577,26 @@ int nngp_matern_eval(const double* u, int64_t n, double nu, double* out, void* s
         return fail(NNGP_EINVAL, "the matern correlation needs 0 < nu <= %g (nu=%g)", NNGP_MATERN_NU_MAX, nu);
     hipError_t e = nngp::matern_eval_launch(u, n, nu, out, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "matern_eval launch");
+    return NNGP_OK;
+}
+
+int nngp_matern_eval_d(const double* u, int64_t n, double nu, double* h, double* dnu, void* stream) {
+    if (n < 0 || (n > 0 && (u == nullptr || h == nullptr || dnu == nullptr)))
+        return fail(NNGP_EINVAL, "bad n or null pointer");
+    if (!(nu > 0.0 && nu <= NNGP_MATERN_NU_MAX))
+        return fail(NNGP_EINVAL, "the matern correlation needs 0 < nu <= %g (nu=%g)", NNGP_MATERN_NU_MAX, nu);
+    if (n == 0) return NNGP_OK;
+    int e0, noct;
+    if (!nngp::matern_table_extent(nu, &e0, &noct))
+        return fail(NNGP_EUNSUP, "matern nu=%g needs %d table octaves (> %d)", nu, noct, NNGP_MT_MAX_OCT);
+    // the derivative table in stream-ordered memory: live from here to the lookup kernel, no host synchronisation
+    void* tabd = nullptr;
+    hipError_t e = hipMallocAsync(&tabd, 2 * NNGP_MT_BYTES(noct), (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "matern_eval_d table");
+    e = nngp::matern_eval_d_launch(u, n, nu, (double*)tabd, h, dnu, (hipStream_t)stream);
+    const hipError_t ef = hipFreeAsync(tabd, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "matern_eval_d launch");
+    if (ef != hipSuccess) return hip_fail(ef, "matern_eval_d table release");
     return NNGP_OK;
 }
 

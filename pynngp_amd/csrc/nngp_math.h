@@ -98,6 +98,9 @@ struct CovParams {
     // rho = 1 - mt_A t^nu (mt_series = 1), else rho = 1 there
     double mt_A;
     int mt_series;
+    // the derivative functions of the correlation (nngp_matern_drho): log Gamma(nu) and psi(nu) from
+    // nngp_matern_setup, and psi(1 - nu) + ln 4 + psi(1 + nu) for the series below the table
+    double mlgam, mpsi, mt_dA;
 };
 
 NNGP_HD CovParams nngp_cov_params(int kind, double sigma2, double phi, double tau2) {
@@ -136,7 +139,28 @@ NNGP_HD CovParams nngp_cov_params(int kind, double sigma2, double phi, double ta
     p.mt_e0 = p.mt_noct = 0;
     p.mt_A = 0.0;
     p.mt_series = 0;
+    p.mlgam = p.mpsi = p.mt_dA = 0.0;
     return p;
+}
+
+// psi(x) = d ln Gamma(x) / dx for x > 0: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 10, then the
+// asymptotic series through B_14 (the next term is below 5e-17 there)
+NNGP_HD double nngp_digamma(double x) {
+    int steps = 0;
+    while (x + steps < 10.0) ++steps;
+    double r = 0.0;  // sum of 1 / (x + j), the small terms first
+    for (int j = steps - 1; j >= 0; --j) r += 1.0 / (x + j);
+    r = -r;
+    x += steps;
+    const double i2 = 1.0 / (x * x);
+    double t = 1.0 / 12.0;
+    t = fma(-t, i2, 691.0 / 32760.0);
+    t = fma(-t, i2, 1.0 / 132.0);
+    t = fma(-t, i2, 1.0 / 240.0);
+    t = fma(-t, i2, 1.0 / 252.0);
+    t = fma(-t, i2, 1.0 / 120.0);
+    t = fma(-t, i2, 1.0 / 12.0);
+    return r + (log(x) - 0.5 / x - t * i2);
 }
 
 // ---------------------------------------------------------------- Matern, general smoothness nu
@@ -177,6 +201,8 @@ NNGP_HD void nngp_matern_setup(CovParams& p, double nu) {
     p.mscale = ldexp(1.0, 1 - p.mnl) / gnu;
     const double umax = 1500.0 + 30.0 * nu;
     p.d2max = (umax / p.phi) * (umax / p.phi);
+    p.mlgam = lgamma(nu);
+    p.mpsi = nngp_digamma(nu);
 }
 
 NNGP_HD CovParams nngp_cov_params_nu(int kind, double sigma2, double phi, double tau2, double nu) {
@@ -275,6 +301,57 @@ NNGP_HD double nngp_matern_rho(const CovParams& P, double u) {
     return P.mscale * j1;
 }
 
+// The two derivative functions of rho_nu(u) = c u^nu K_nu(u), c = 2^(1 - nu) / Gamma(nu) (bf_grad_matern.h):
+//   h(u) = u rho'(u) = -c u^(nu + 1) K_{nu - 1}(u)        (d C / d phi   = sigma2 h / phi)
+//   n(u) = d rho_nu(u) / d nu                             (d C / d nu    = sigma2 n)
+// both from K_nu(u) = int_0^inf e^(-u cosh s) cosh(nu s) ds by the trapezoid rule with step 0.05 on
+// [0, ln(2 (800 + 60 nu) / u) + 2] (the integrand is analytic and decays doubly exponentially: the rule
+// converges geometrically).  h's integrand, cosh((nu - 1) s), is positive: no cancellation.  n's is
+//   c u^nu e^(-u cosh s) [ (k + s) e^(nu s) + (k - s) e^(-nu s) ] / 2,   k = ln(u / 2) - psi(nu),
+// where the large ln u and s cancel inside the bracket, node by node (the integrand peaks where k + s ~ 0).
+// Every term is one exponential of log c + nu ln u - u cosh s +- nu s, so nu = 50 at a small u neither
+// overflows nor underflows early.  h(0) = n(0) = 0; both are 0 where e^-u has underflowed.
+#define NNGP_MATERN_DRHO_STEP 0.05
+NNGP_HD void nngp_matern_drho(const CovParams& P, double u, double* h, double* n) {
+    *h = 0.0;
+    *n = 0.0;
+    if (!(u > 0.0)) return;
+    const double nu = P.nu;
+    const double smax = log(2.0 * (800.0 + 60.0 * nu) / u) + 2.0;
+    if (!(smax > 0.0)) return;
+    const double ln2 = 0.6931471805599453;
+    // ln u = lu + lul: n(u) at a small u is the mean of ln u + s under rho's integrand less a constant, so ln u's
+    // own rounding (half an ulp of 345 at u = 1e-150) would pass into n unreduced
+    const double lu = log(u);
+    const double lul = log1p(fma(u, exp(-lu), -1.0));
+    const double kk = ln2 + P.mpsi;                       // k + s = (ln u + s) - kk
+    const double cst = (1.0 - nu) * ln2 - P.mlgam;        // ln c, rounded at its size (178 at nu = 50) ...
+    const double corr = P.mscale * exp2(-P.mu) * exp(-cst);  // ... and c / e^cst = 1 + O(1e-14) from c itself
+    const int N = (int)ceil(smax / NNGP_MATERN_DRHO_STEP);
+    const bool tiny = lu < -60.0;
+    const double hs = tiny ? 2.0 * lu : 0.0;
+    double sh = 0.0, shc = 0.0, sn = 0.0;
+    for (int j = 0; j <= N; ++j) {
+        const double s = j * NNGP_MATERN_DRHO_STEP;
+        const double w = j == 0 ? 0.25 : 0.5;  // trapezoid weight times the 1/2 of cosh
+        const double uc = u * cosh(s);
+        // ln u + s and ln u - s first: at a small u both ln u and s are large and their sum is small (and exact),
+        // so the exponents nu (ln u +- s) + ln c - u cosh s round at their own size, not at nu |ln u|
+        const double ap = (lu + s) + lul, am = (lu - s) + lul;
+        const double xp = fma(nu, ap, cst) - uc, xm = fma(nu, am, cst) - uc;
+        sn = fma(w, fma(ap - kk, exp(xp), (am - kk) * exp(xm)), sn);
+        // h: c u^(nu + 1) e^(-u cosh s) e^(+-(nu - 1) s) = u^2 c e^((nu - 1) (ln u +- s) - u cosh s), again with
+        // exponents that round at their own size; u^2 is applied at the end (inside the exponent for a tiny u,
+        // where e^((1 - nu) (s - ln u)) alone would overflow and h itself is far below any rounding)
+        const double ht = w * (exp(fma(nu - 1.0, ap, cst) - uc + hs) + exp(fma(nu - 1.0, am, cst) - uc + hs));
+        const double hy = ht - shc, hn = sh + hy;  // compensated: the sum of a few hundred terms stays within an ulp
+        shc = (hn - sh) - hy;
+        sh = hn;
+    }
+    *h = -NNGP_MATERN_DRHO_STEP * corr * (tiny ? 1.0 : u * u) * sh;
+    *n = NNGP_MATERN_DRHO_STEP * corr * sn;
+}
+
 // ---------------------------------------------------------------- Matern-nu by table (bf_pairb)
 // The fused pair kernel evaluates rho from a per-launch table in t = u^2 = phi^2 d^2 (no square root,
 // no Bessel loop).  Octave o of t -- t in [2^(e0+o-1), 2^(e0+o)), o = (frexp exponent of t) - e0 -- is
@@ -331,6 +408,27 @@ __device__ __attribute__((noinline)) static double nngp_matern_below(double A, d
 }
 #endif
 
+// ... and its two derivative functions there, h = u rho' = -2 nu A t^nu and
+// n = d rho / d nu = -A t^nu (ln t - psi(1 - nu) - ln 4 - psi(1 + nu)) (dA = the three constants, mt_dA);
+// exactly 0 for coincident points
+struct NngpHN {
+    double h, n;
+};
+#ifdef NNGP_MATH_HOST
+static inline NngpHN nngp_matern_below_d(double A, double dA, double t, double nu, double mphi2) {
+#else
+// (returned by value: out-pointers into the caller's frame would cost every caller scratch memory)
+__device__ __attribute__((noinline)) static NngpHN nngp_matern_below_d(double A, double dA, double t, double nu,
+                                                                       double mphi2) {
+#endif
+    NngpHN r = {0.0, 0.0};
+    if (t <= NNGP_D2_FLOOR * mphi2) return r;
+    const double at = A * pow(t, nu);
+    r.h = -2.0 * nu * at;
+    r.n = -at * (log(t) - dA);
+    return r;
+}
+
 // table extent for P (nngp_matern_setup done): returns false when it would exceed NNGP_MT_MAX_OCT
 NNGP_HD bool nngp_matern_table_setup(CovParams& p) {
     p.mphi2 = p.phi * p.phi;
@@ -346,6 +444,7 @@ NNGP_HD bool nngp_matern_table_setup(CovParams& p) {
         e0 = NNGP_MT_SERIES_E;  // the series serves t < 2^e0
         p.mt_series = 1;
         p.mt_A = tgamma(1.0 - p.nu) / (pow(4.0, p.nu) * tgamma(1.0 + p.nu));
+        p.mt_dA = nngp_digamma(1.0 - p.nu) + 1.3862943611198906 + nngp_digamma(1.0 + p.nu);
     }
     p.mt_e0 = e0;
     p.mt_noct = ez - e0 + 2;
@@ -369,12 +468,13 @@ NNGP_HD void nngp_matern_costab(double* costab) {
 
 // monomial coefficients in f of bin b's interpolant from rho at the bin's nodes (rho_nodes[k] at
 // nngp_matern_node(k)); octave 0 = 1, the last octave = 0
-NNGP_HD void nngp_matern_bin_fit(const CovParams& p, int b, const double* rho_nodes, const double* costab,
-                                 double* coef) {
+// (v0: the constant of octave 0 -- 1 for rho, 0 for its derivative functions, whose tables share the geometry)
+NNGP_HD void nngp_matern_bin_fit_v0(const CovParams& p, int b, const double* rho_nodes, const double* costab,
+                                    double* coef, double v0) {
     const int o = b / NNGP_MT_K;
     for (int k = 0; k < NNGP_MT_NC; ++k) coef[k] = 0.0;
     if (o == 0) {
-        coef[0] = 1.0;
+        coef[0] = v0;
         return;
     }
     if (o >= p.mt_noct - 1) return;
@@ -404,6 +504,10 @@ NNGP_HD void nngp_matern_bin_fit(const CovParams& p, int b, const double* rho_no
         }
     }
     coef[0] += vref;
+}
+NNGP_HD void nngp_matern_bin_fit(const CovParams& p, int b, const double* rho_nodes, const double* costab,
+                                 double* coef) {
+    nngp_matern_bin_fit_v0(p, b, rho_nodes, costab, coef, 1.0);
 }
 
 // rho(phi d) from the table (tab: the launch's table, 16-B aligned), d2 = d^2 from the distance.
@@ -445,6 +549,53 @@ NNGP_HD double nngp_matern_tab(const CovParams& P, const double* tab, double d2)
     }
 #endif
     return r;
+}
+
+// h and n at t = phi^2 d^2 from the derivative table (matern_table.hip: nngp_matern_tab's geometry, each bin
+// holding h's NNGP_MT_NC coefficients and then n's, so one lookup touches 160 contiguous bytes); the same
+// index arithmetic and Horner order as nngp_matern_tab.  The end octaves hold 0.
+NNGP_HD void nngp_matern_tab_d(const CovParams& P, const double* tabd, double d2, double* h, double* n) {
+    const double t = fmin(d2 * P.mphi2, 0x1p1000);
+#ifdef NNGP_MATH_HOST
+    int ex;
+    const double mant = frexp(t, &ex);
+    const double s = mant * (2.0 * NNGP_MT_K);  // [K, 2K)
+    const double f = s - floor(s);
+#else
+    const int ex = __builtin_amdgcn_frexp_exp(t);
+    const double s = __builtin_amdgcn_frexp_mant(t) * (2.0 * NNGP_MT_K);
+    const double f = __builtin_amdgcn_fract(s);
+#endif
+    const int j = (int)s - NNGP_MT_K;
+    if (P.mt_series && ex <= P.mt_e0) {  // below the table (rare)
+        const NngpHN r = nngp_matern_below_d(P.mt_A, P.mt_dA, t, P.nu, P.mphi2);
+        *h = r.h;
+        *n = r.n;
+        return;
+    }
+    int o = ex - P.mt_e0;
+    o = o < 0 ? 0 : (o > P.mt_noct - 1 ? P.mt_noct - 1 : o);
+    const double* c = tabd + (o * NNGP_MT_K + j) * (2 * NNGP_MT_NC);
+#ifdef NNGP_MATH_HOST
+    double rh = c[NNGP_MT_NC - 1], rn = c[2 * NNGP_MT_NC - 1];
+    for (int k = NNGP_MT_NC - 2; k >= 0; --k) {
+        rh = fma(rh, f, c[k]);
+        rn = fma(rn, f, c[NNGP_MT_NC + k]);
+    }
+#else
+    const double2* c2 = (const double2*)c;
+    double2 v = c2[NNGP_MT_NC / 2 - 1], w = c2[NNGP_MT_NC - 1];
+    double rh = fma(v.y, f, v.x), rn = fma(w.y, f, w.x);
+#pragma unroll
+    for (int q = NNGP_MT_NC / 2 - 2; q >= 0; --q) {
+        v = c2[q];
+        w = c2[NNGP_MT_NC / 2 + q];
+        rh = fma(fma(rh, f, v.y), f, v.x);
+        rn = fma(fma(rn, f, w.y), f, w.x);
+    }
+#endif
+    *h = rh;
+    *n = rn;
 }
 
 #ifndef NNGP_MATH_HOST

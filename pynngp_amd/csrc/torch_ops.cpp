@@ -254,6 +254,46 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_aniso(const at::Tensor& c
     return {p, g, G};
 }
 
+// general-nu Matern gradient sweep (nngp_bf_grad_matern): (partials (4,), grad (4,), G (rows, 4) or (0, 4))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_matern(const at::Tensor& coords, const at::Tensor& nbr,
+                                                              const c10::optional<at::Tensor>& order, int64_t i0,
+                                                              double sigma2, double phi, double tau2, double nu,
+                                                              const at::Tensor& values, bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(values, {n}, coords, "values");
+    if (order.has_value()) {
+        TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == rows &&
+                        order->is_contiguous(), "order must be a contiguous int32 (rows,) tensor");
+        check_same_device(coords, *order, "order");
+    }
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({4}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, 4}, f64);
+    const int64_t need = (int64_t)nngp_bf_grad_matern_workspace_bytes(rows, (int32_t)m);
+    auto ws = at::empty({need > 256 ? need : 256}, f64.dtype(at::kByte));
+    check_rc(nngp_bf_grad_matern(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                                 ptr<int32_t>(order), rows, (int32_t)m, i0, sigma2, phi, tau2, nu,
+                                 values.data_ptr<double>(), want_rows ? G.data_ptr<double>() : nullptr,
+                                 p.data_ptr<double>(), g.data_ptr<double>(), ws.data_ptr(), (size_t)ws.numel(),
+                                 stream(coords)),
+             "nngp_bf_grad_matern");
+    return {p, g, G};
+}
+
+// u rho'(u) and d rho / d nu of the Matern correlation through the sweep's derivative table (nngp_matern_eval_d)
+std::tuple<at::Tensor, at::Tensor> matern_eval_d(const at::Tensor& u, double nu) {
+    TORCH_CHECK(u.scalar_type() == at::kDouble && u.is_contiguous(), "u must be a contiguous float64 tensor");
+    const at::OptionalDeviceGuard guard(u.device());
+    at::Tensor h = at::empty_like(u), dnu = at::empty_like(u);
+    check_rc(nngp_matern_eval_d(u.data_ptr<double>(), u.numel(), nu, h.data_ptr<double>(), dnu.data_ptr<double>(),
+                                stream(u)),
+             "nngp_matern_eval_d");
+    return {h, dnu};
+}
+
 // the factors and their phi-derivatives (nngp_bf_dphi): (B (rows, m), F (rows,), dB (rows, m), dF (rows,), partials (4,))
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_dphi(
     const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
@@ -780,6 +820,9 @@ TORCH_LIBRARY(nngp, m) {
           "Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_grad_aniso(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float[] phi, "
           "float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_grad_matern(Tensor coords, Tensor nbr, Tensor? order, int i0, float sigma2, float phi, float tau2, "
+          "float nu, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("matern_eval_d(Tensor u, float nu) -> (Tensor, Tensor)");
     m.def("bf_dphi(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2) "
           "-> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("bf_fisher(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, float tau2, "
@@ -804,6 +847,8 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_cross", &bf_cross);
     m.impl("bf_grad", &bf_grad);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
+    m.impl("bf_grad_matern", &bf_grad_matern);
+    m.impl("matern_eval_d", &matern_eval_d);
     m.impl("bf_dphi", &bf_dphi);
     m.impl("bf_fisher", &bf_fisher);
     m.impl("row_order", &row_order);

@@ -107,6 +107,33 @@ class Covariance:
         return e
 
 
+@dataclasses.dataclass(frozen=True, init=False)
+class MaternCovariance(Covariance):
+    """The general-smoothness Matern covariance with the smoothness as a fourth parameter:
+    ``MaternCovariance(sigma2, phi, tau2, nu)``, ``theta`` = (sigma2, phi, tau2, nu).
+
+    Forward it is ``Covariance("matern", sigma2, phi, tau2, nu=nu)`` -- the same sweeps, the same bits.  It is the
+    type by which :meth:`NNGP.loglik_grad`, :meth:`NNGP.profile_loglik_grad` and ``fit(estimate_nu=...)`` select the
+    four-component gradient sweep (``nngp_bf_grad_matern``), which ``Covariance("matern", ...)`` keeps refusing.
+    The Fisher, latent-gradient and per-axis paths refuse it as they refuse the kind."""
+
+    def __init__(self, sigma2: float, phi: float, tau2: float = 0.0, nu: Optional[float] = None):
+        for k, v in (("kind", "matern"), ("sigma2", sigma2), ("phi", phi), ("tau2", tau2), ("nu", nu)):
+            object.__setattr__(self, k, v)
+        self.__post_init__()
+
+    @property
+    def theta(self):
+        return (float(self.sigma2), float(self.phi), float(self.tau2), float(self.nu))
+
+    def replace(self, **kw) -> "MaternCovariance":
+        if kw.get("kind", "matern") != "matern":
+            raise ValueError("a MaternCovariance is of kind 'matern'")
+        f = {"sigma2": self.sigma2, "phi": self.phi, "tau2": self.tau2, "nu": self.nu}
+        f.update({k: v for k, v in kw.items() if k != "kind"})
+        return MaternCovariance(**f)
+
+
 _ANISO_KINDS = ("exponential", "matern32", "matern52", "gaussian", "spherical")
 
 
@@ -479,9 +506,9 @@ def _sweep_any(cv, coords, nbr, i0=0, values=None, want_bf=True, algo="auto", or
         return _lib.bf_sweep_blocks(blocks, nbr, coords.shape[0], i0, values=values, qvalues=qvalues, want_bf=want_bf,
                                     order=order, R=R, n_locs=nq)
     if qcoords is not None:
-        return _lib.bf_cross(coords, qcoords, nbr, cv.kind, *cv.theta, ref_values=values, query_values=qvalues,
+        return _lib.bf_cross(coords, qcoords, nbr, cv.kind, *cv.theta[:3], ref_values=values, query_values=qvalues,
                              q0=i0, algo=algo, R=R, nu=cv.nu_arg)
-    return _lib.bf_sweep(coords, nbr, i0, cv.kind, *cv.theta, values=values, want_bf=want_bf, algo=algo, order=order,
+    return _lib.bf_sweep(coords, nbr, i0, cv.kind, *cv.theta[:3], values=values, want_bf=want_bf, algo=algo, order=order,
                          R=R, nu=cv.nu_arg)
 
 
@@ -908,11 +935,19 @@ class NNGP:
                             f"matern52, gaussian, spherical), not {type(cv).__name__}")
         if not aniso:
             _refuse_aniso(cv, "the Fisher information (fisher_information, fit(method='fisher'), stderr=True)")
-        if cv.kind == "matern":
+        if cv.kind == "matern" and not (aniso and isinstance(cv, MaternCovariance)):
             raise NotImplementedError("the analytic gradient does not serve the general-nu matern kind")
         if not 1 <= self.m <= _lib.GRAD_MAX_M:
             raise NotImplementedError(f"the analytic gradient serves 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
         return cv
+
+    def _matern_grad_ws(self) -> torch.Tensor:
+        """The Matern gradient sweep's workspace (records and tables), kept across a fit's evaluations."""
+        need = _lib.load().nngp_bf_grad_matern_workspace_bytes(self.nbr.shape[0], self.m)
+        ws = getattr(self, "_mgrad_ws", None)
+        if ws is None or ws.numel() < need or ws.device != self._s_dev.device:
+            ws = self._mgrad_ws = _lib._workspace(need, self._s_dev.device)
+        return ws
 
     def _values_dev(self, values):
         v = self.y if values is None else values
@@ -926,9 +961,16 @@ class NNGP:
         """:meth:`loglik` and its analytic gradient in (sigma2, phi, tau2) from one fused gradient sweep
         (``nngp_bf_grad``): ``(loglik, grad)`` with ``grad`` a float64 ndarray (3,).  An
         :class:`AnisotropicCovariance` gives the gradient in (sigma2, phi_1 .. phi_dim, tau2), (dim + 2,), from one
-        ``nngp_bf_grad_aniso`` sweep on the raw coordinates."""
+        ``nngp_bf_grad_aniso`` sweep on the raw coordinates; a :class:`MaternCovariance` the gradient in
+        (sigma2, phi, tau2, nu), (4,), from one ``nngp_bf_grad_matern`` sweep."""
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
+        if isinstance(cv, MaternCovariance):
+            p, g, _ = _lib.bf_grad_matern(self._s_dev, self._nbr_sorted, 0, cv.sigma2, cv.phi, cv.tau2, cv.nu, v,
+                                          order=self._order, workspace=self._matern_grad_ws())
+            h = torch.cat([p, g]).cpu().numpy()
+            _raise_on_bad(h[:4])
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:].copy()
         if isinstance(cv, AnisotropicCovariance):
             p, g, _ = _lib.bf_grad_aniso(self._s_dev, self._nbr_sorted, 0, cv.kind, cv.sigma2, cv.phi, cv.tau2, v,
                                          order=self._order)
@@ -1103,7 +1145,8 @@ class NNGP:
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
             gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None,
-            anisotropic: bool = False, reneighbor: int = 0):
+            anisotropic: bool = False, reneighbor: int = 0, estimate_nu: Optional[bool] = None,
+            nu_bounds=(0.05, 50.0)):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -1143,11 +1186,30 @@ class NNGP:
         when that iterate was not positive definite) and ``message``, the optimiser's stopping reason.
         ``reneighbor=r`` runs r further rounds: each calls :meth:`rebuild_neighbors` at the current estimate and
         restarts the optimiser from it (the likelihood of a round is the one on that round's sets).  No ``stderr``,
-        ``method="fisher"`` or ``reml`` with it."""
+        ``method="fisher"`` or ``reml`` with it.
+
+        ``estimate_nu`` (``kind="matern"`` only; None, the default, changes nothing): ``True`` runs L-BFGS-B on the
+        log of (sigma2, phi, tau2, nu) from ``nu`` with the four-component gradient of one ``nngp_bf_grad_matern``
+        sweep per evaluation (:class:`MaternCovariance`), nu kept inside ``nu_bounds``; ``False`` does the same at
+        the fixed ``nu`` with the first three components.  ``fix_tau2`` and ``mean`` as for ``anisotropic=True``;
+        ``tol`` is L-BFGS-B's ``gtol`` and, when given, the only stopping rule beside ``maxiter`` (``ftol`` is set
+        to 1e-15).  The result carries ``nu``, ``theta`` = (sigma2, phi, tau2, nu), ``grad`` (the
+        gradient in the free log-parameters at the optimiser's last iterate) and ``message``.  No ``reml``,
+        ``anisotropic``, ``method="fisher"`` or ``stderr`` with it."""
+        if estimate_nu is not None:
+            for on, what in ((reml, "reml=True"), (anisotropic, "anisotropic=True"),
+                             (method == "fisher", "method='fisher'"), (stderr, "stderr=True")):
+                if on:
+                    raise NotImplementedError(f"fit(estimate_nu=...) with {what}: the general-nu matern kind has a "
+                                              "gradient sweep only (no restricted likelihood gradient, per-axis form "
+                                              "or Fisher information sweep)")
         if mean == "linear" and X is None:
             raise ValueError("mean='linear' needs the design matrix X")
         if mean != "linear" and X is not None:
             raise ValueError("X is the design of mean='linear'")
+        if estimate_nu is not None:
+            return self._fit_matern(kind, x0, mean, fix_tau2, method or "L-BFGS-B", maxiter, X, algo, tol, nu,
+                                    bool(estimate_nu), nu_bounds)
         if anisotropic:
             if stderr or method == "fisher":
                 raise NotImplementedError("the Fisher information sweep has no per-axis form: fit(anisotropic=True) "
@@ -1193,7 +1255,7 @@ class NNGP:
         kind = kind or (base.kind if base is not None else "exponential")
         if nu is None and base is not None and base.kind == kind:
             nu = base.nu
-        th0 = tuple(x0) if x0 is not None else (base.theta if base is not None else (1.0, 10.0, 0.1))
+        th0 = tuple(x0) if x0 is not None else (base.theta[:3] if base is not None else (1.0, 10.0, 0.1))
         free_tau = fix_tau2 is None
         if method == "fisher":
             return self._fit_fisher(kind, th0, nu, mean, X, linear, free_tau, fix_tau2, maxiter, tol, algo)
@@ -1340,6 +1402,80 @@ class NNGP:
                 "loglik": best["ll"], "grad": -np.asarray(res.jac, dtype=np.float64), "n_evals": n_evals,
                 "n_grad_evals": n_grad, "converged": bool(res.success) and not last_failed[0],
                 "message": str(res.message), "rounds": reneighbor + 1,
+                **self._fit_beta(X if linear else None, algo)}
+
+    def _fit_matern(self, kind, x0, mean, fix_tau2, method, maxiter, X, algo, tol, nu, free_nu: bool,
+                    nu_bounds) -> dict:
+        """``fit(estimate_nu=...)``: gradient=True's scaffolding over (sigma2, phi, tau2[, nu])."""
+        from scipy.optimize import minimize
+
+        _refuse_aniso(self.cov, "fit(estimate_nu=...)")
+        base = self.cov if isinstance(self.cov, Covariance) else None
+        kind = kind or (base.kind if base is not None else None)
+        if kind != "matern":
+            raise ValueError(f"estimate_nu is an option of kind='matern' (kind={kind!r})")
+        if nu is None and base is not None and base.kind == "matern":
+            nu = base.nu
+        lo, hi = (float(b) for b in nu_bounds)
+        if not 0.0 < lo < hi <= _lib.MATERN_NU_MAX:
+            raise ValueError(f"nu_bounds must satisfy 0 < lo < hi <= {_lib.MATERN_NU_MAX:g}")
+        th0 = tuple(x0)[:3] if x0 is not None else (base.theta[:3] if base is not None else (1.0, 10.0, 0.1))
+        free_tau = fix_tau2 is None
+        linear = mean == "linear"
+        if linear:
+            from . import regression
+
+            X = regression.design(self, X, self.nbr.shape[0])
+        start = MaternCovariance(float(th0[0]), float(th0[1]),
+                                 max(float(th0[2]), 1e-6) if free_tau else float(fix_tau2),
+                                 min(max(float(nu), lo), hi) if free_nu and nu is not None else nu)
+        self._grad_cov(start)  # refuse an unsupported m before optimising
+        idx = [0, 1] + ([2] if free_tau else []) + ([3] if free_nu else [])  # theta's free entries
+
+        def cov_of(z):
+            th = list(start.theta)
+            for k, j in enumerate(idx):
+                th[j] = math.exp(z[k])
+            return MaternCovariance(*th)
+
+        best, last_failed, n_grad = {"ll": -math.inf}, [False], [0]
+
+        def obj_grad(z):
+            cv = cov_of(z)
+            try:
+                ll, mu, g = self.profile_loglik_grad(cv, mean=mean, X=X)
+            except NNGPNumericalError:
+                last_failed[0] = True
+                return 1e300, np.zeros(len(z))
+            last_failed[0] = False
+            n_grad[0] += 1
+            th = cv.theta
+            if ll > best["ll"]:
+                best.update(ll=ll, mu=None if linear else mu, cov=cv)
+            return -ll, -np.array([th[j] * g[j] for j in idx])
+
+        options, kw = {"maxiter": maxiter}, {}
+        if tol is not None and method == "L-BFGS-B":
+            # the gradient rule alone decides: the relative-decrease rule (ftol) is set below any step it could end,
+            # so a converged fit reports a gradient within tol
+            options["gtol"] = float(tol)
+            options["ftol"] = 1e-15
+        elif tol is not None:
+            kw["tol"] = float(tol)
+        if method == "L-BFGS-B":
+            kw["bounds"] = [(math.log(lo), math.log(hi)) if j == 3 else (None, None) for j in idx]
+        z0 = np.log(np.array([start.theta[j] for j in idx]))
+        res = minimize(obj_grad, z0, jac=True, method=method, options=options, **kw)
+        if "cov" not in best:
+            raise NNGPNumericalError("fit(estimate_nu=...): no parameter value the optimiser tried was positive "
+                                     "definite")
+        cv = best["cov"]
+        self.cov = cv
+        self._B = self._F = None
+        return {"theta": cv.theta, "sigma2": cv.sigma2, "phi": cv.phi, "tau2": cv.tau2, "nu": float(cv.nu),
+                "mu": best["mu"], "loglik": best["ll"], "grad": -np.asarray(res.jac, dtype=np.float64),
+                "n_evals": int(res.nfev), "n_grad_evals": n_grad[0],
+                "converged": bool(res.success) and not last_failed[0], "message": str(res.message),
                 **self._fit_beta(X if linear else None, algo)}
 
     def _fit_beta(self, X, algo):

@@ -115,6 +115,15 @@ def _register_fakes() -> None:
         return (coords.new_empty((4,)), coords.new_empty((k,)),
                 coords.new_empty((nbr.shape[0] if want_rows else 0, k)))
 
+    @fake("bf_grad_matern")
+    def _(coords, nbr, order, i0, sigma2, phi, tau2, nu, values, want_rows):
+        return (coords.new_empty((4,)), coords.new_empty((4,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, 4)))
+
+    @fake("matern_eval_d")
+    def _(u, nu):
+        return torch.empty_like(u), torch.empty_like(u)
+
     @fake("bf_fisher")
     def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
         rows = nbr.shape[0] if want_rows else 0

@@ -193,7 +193,7 @@ class ShardedLogLik:
             return p if out is None else out.copy_(p)
         B, F = (self._B, self._F) if want_bf else (None, None)
         p = self._partials if out is None else out
-        s2, phi, tau2 = cov.theta
+        s2, phi, tau2 = cov.theta[:3]
         plan = self._plan_for(cov.kind)
         if self.api == "ctypes":  # the same C-ABI call without the dispatcher (A/B of the op overhead)
             _lib.bf_sweep(self._coords_sweep, self._nbr_sweep, self.lo, cov.kind, s2, phi, tau2, values=values,
