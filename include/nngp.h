@@ -454,6 +454,32 @@ int nngp_row_order(const double *coords, int64_t n_points, int32_t dim, const in
                    void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Model order of the points: the levelled max-min (nested-net) order (no reference counterpart: the reference
+ * takes the caller's row order, nngp.py:51).  Added within ABI revision 4 (nothing earlier moved).
+ * The order is defined in DESIGN.md 4.4a and restated in tests/order_ref.py; a call reproduces it index for
+ * index and bit for bit from run to run.  In short: p1 is the point nearest the centre of the bounding box,
+ * R the distance of the farthest point from p1; level l = 1 .. 19 selects, in rounds, points that keep a
+ * distance >= R 2^-l from everything selected before them until every point has a selected point closer than
+ * that; the points no level selects (coincident points, and points closer than R 2^-19 to an earlier one) are
+ * the tail, level 20.  Inside a level, and in the tail, points are sorted by
+ * key(i) = mix32(i + seed * 0x9e3779b9) << 32 | i (mix32: the murmur3 finaliser).
+ *   coords (n, dim) fp64 row-major, finite, 1 <= dim <= 3, 1 <= n < 2^31.
+ *   perm_out int64 (n,): perm_out[k] = the input row at position k.   level_out int32 (n,): level_out[k] = the
+ *   level (0 for p1, 1 .. 19, 20 for the tail) of the point at position k, non-decreasing in k.
+ * NNGP_EINVAL for a NULL pointer, dim outside [1, 3], n < 1, a short or misaligned workspace, a coordinate that
+ * is not finite or a squared distance that overflows.
+ * workspace: nngp_order_maxmin_workspace_bytes(n, dim) bytes (0 for bad arguments), 256-B aligned, no
+ * initialisation needed.  On return its first 64 int32 hold what the call did: launches enqueued, count reads,
+ * the last level entered, the tail's size, then 20 each of rounds, accept/retire iterations and points selected
+ * per level (index = level).
+ * A SETUP CALL: it synchronises `stream` once per round (the host sizes the next launches by one 256-byte read),
+ * so it cannot be captured into a graph.
+ * ------------------------------------------------------------------------- */
+size_t nngp_order_maxmin_workspace_bytes(int64_t n, int32_t dim);
+int nngp_order_maxmin(const double *coords, int64_t n, int32_t dim, uint32_t seed, int64_t *perm_out,
+                      int32_t *level_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU: fold the all-gathered partials of `world` ranks (device array
  * (world, 4), rank-major, e.g. from an RCCL all-gather) in rank order:
  * partials[0..1] = sums, partials[2..3] = smallest non-negative flag or -1.

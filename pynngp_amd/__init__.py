@@ -17,6 +17,8 @@ from .latent import LatentPosterior, LogDet, SolveInfo, lanczos_quadrature  # no
 from .gibbs_binomial import BinomialSeqNNGP, polya_gamma  # noqa: F401
 from .latent_binomial import BinomialLatentPosterior, ModeInfo  # noqa: F401
 from .factor import NNGPFactor  # noqa: F401
+from . import ordering  # noqa: F401
+from .ordering import order_maxmin, order_random, order_coordinate, order_middleout, maxmin_subset  # noqa: F401
 
 __version__ = "0.3.0"
 

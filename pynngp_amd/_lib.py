@@ -115,6 +115,8 @@ SYMBOLS = (
     "nngp_factor_prior_draw_batch",
     "nngp_whiten_gram_workspace_bytes",
     "nngp_whiten_gram",
+    "nngp_order_maxmin_workspace_bytes",
+    "nngp_order_maxmin",
 )
 
 KIND_CODES = {"exponential": 0, "matern32": 1, "matern52": 2, "gaussian": 3, "spherical": 4, "matern": 5}
@@ -350,6 +352,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_whiten_gram_workspace_bytes.restype = SZ
     lib.nngp_whiten_gram.argtypes = [P, P, P, P, I64, I32, I64, I64, I32, P, P, P, P, P, SZ, P]
     lib.nngp_whiten_gram.restype = ctypes.c_int
+    lib.nngp_order_maxmin_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_order_maxmin_workspace_bytes.restype = SZ
+    lib.nngp_order_maxmin.argtypes = [P, I64, I32, ctypes.c_uint32, P, P, P, SZ, P]
+    lib.nngp_order_maxmin.restype = ctypes.c_int
     lib.nngp_check_partials.argtypes = [P, P, P]
     lib.nngp_check_partials.restype = ctypes.c_int
     lib.nngp_loglik_from_partials.argtypes = [P, I64]
@@ -1155,6 +1161,40 @@ def row_order(coords: torch.Tensor, i0: int = 0, rows: Optional[int] = None,
     _check(lib.nngp_row_order(_ptr(coords), n, coords.shape[1], _ptr(nbr), m, i0, rows, _ptr(out), _ptr(srt), _ptr(ws),
                               ws.numel(), _stream(dev)), "nngp_row_order")
     return out, srt
+
+
+MAXMIN_TAIL = 20  # level of the points no level of the max-min order selected
+MAXMIN_STATS_LEN = 64  # int32 counters nngp_order_maxmin leaves at the head of its workspace
+
+
+def order_maxmin(coords: torch.Tensor, seed: int = 0, want_stats: bool = False):
+    """Levelled max-min order of ``coords`` (``nngp_order_maxmin``, include/nngp.h):
+    ``(perm, level)``, ``perm`` int64 (n,) with ``perm[k]`` the input row at position k and ``level`` int32 (n,) the
+    level of the point at position k (0 for the first point, 1 .. 19, 20 for the tail).  A setup call: it
+    synchronises the current stream once per round.  ``want_stats``: also a dict of what the call did (launches,
+    count reads, rounds / accept-retire iterations / points selected per level)."""
+    coords = _as_coords(coords)
+    dev = _require_gpu(coords)
+    n, d = coords.shape
+    if n < 1:
+        raise ValueError("order_maxmin needs at least one point")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"seed must be a uint32, got {seed}")
+    lib = load()
+    need = lib.nngp_order_maxmin_workspace_bytes(n, d)
+    if need == 0:
+        raise NNGPExtensionError("nngp_order_maxmin_workspace_bytes failed")
+    ws = _workspace(need, dev)
+    perm = torch.empty((n,), dtype=torch.int64, device=dev)
+    level = torch.empty((n,), dtype=torch.int32, device=dev)
+    _check(lib.nngp_order_maxmin(_ptr(coords), n, d, int(seed), _ptr(perm), _ptr(level), _ptr(ws), ws.numel(),
+                                 _stream(dev)), "nngp_order_maxmin")
+    if not want_stats:
+        return perm, level
+    st = ws[:4 * MAXMIN_STATS_LEN].view(torch.int32).cpu().tolist()
+    stats = {"launches": st[0], "host_reads": st[1], "levels": st[2], "n_tail": st[3], "rounds": st[4:24],
+             "accept_iterations": st[24:44], "selected": st[44:64]}
+    return perm, level, stats
 
 
 def combine_partials(gathered: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -21,6 +21,7 @@
 #include "factor.h"
 #include "factor_levels.h"
 #include "whiten_gram.h"
+#include "order_maxmin.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1381,6 +1382,28 @@ int nngp_row_order(const double* coords, int64_t n_points, int32_t dim, const in
                                           workspace_bytes, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "row_order launch");
     return NNGP_OK;
+}
+
+size_t nngp_order_maxmin_workspace_bytes(int64_t n, int32_t dim) { return nngp::order_maxmin_workspace_bytes(n, dim); }
+
+int nngp_order_maxmin(const double* coords, int64_t n, int32_t dim, uint32_t seed, int64_t* perm_out,
+                      int32_t* level_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (coords == nullptr || perm_out == nullptr || level_out == nullptr || workspace == nullptr)
+        return fail(NNGP_EINVAL, "coords, perm_out, level_out and workspace must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EINVAL, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (n < 1 || n > INT32_MAX) return fail(NNGP_EINVAL, "n=%lld outside [1, 2^31)", (long long)n);
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp::order_maxmin_workspace_bytes(n, dim);
+    if (need == 0 || workspace_bytes < need)
+        return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    hipError_t e = hipSuccess;
+    switch (nngp::order_maxmin_launch(coords, n, dim, seed, perm_out, level_out, workspace, (hipStream_t)stream, &e)) {
+        case nngp::kMaxminOk: return NNGP_OK;
+        case nngp::kMaxminNotFinite:
+            return fail(NNGP_EINVAL, "coordinates must be finite, with squared distances that are finite too");
+        case nngp::kMaxminTableOverflow: return fail(NNGP_EUNSUP, "order_maxmin: a cell table overflowed or a round made no progress");
+        default: return hip_fail(e, "order_maxmin");
+    }
 }
 
 size_t nngp_knn_workspace_bytes(int64_t n_points, int32_t dim, int32_t m) {

@@ -445,6 +445,24 @@ std::tuple<at::Tensor, at::Tensor> row_order(const at::Tensor& coords, int64_t i
     return {order, srt};
 }
 
+// levelled max-min order (nngp_order_maxmin): (perm int64 (n,), level int32 (n,)); a setup call (it synchronises
+// the stream once per round)
+std::tuple<at::Tensor, at::Tensor> order_maxmin(const at::Tensor& coords, int64_t seed) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    const int64_t n = coords.size(0);
+    TORCH_CHECK(n >= 1, "order_maxmin needs at least one point");
+    TORCH_CHECK(seed >= 0 && seed <= (int64_t)std::numeric_limits<uint32_t>::max(), "seed must be a uint32");
+    auto perm = at::empty({n}, coords.options().dtype(at::kLong));
+    auto level = at::empty({n}, coords.options().dtype(at::kInt));
+    auto ws = workspace((int64_t)nngp_order_maxmin_workspace_bytes(n, (int32_t)coords.size(1)), coords);
+    check_rc(nngp_order_maxmin(coords.data_ptr<double>(), n, (int32_t)coords.size(1), (uint32_t)seed,
+                               perm.data_ptr<int64_t>(), level.data_ptr<int32_t>(), ws.data_ptr(), ws.nbytes(),
+                               stream(coords)),
+             "nngp_order_maxmin");
+    return {perm, level};
+}
+
 // gathered (world, 4) -> out (4,), or a batch of independent sweeps: gathered (world, n_slots, 4) -> out (n_slots, 4)
 void combine_partials_out(const at::Tensor& gathered, const at::Tensor& out) {
     TORCH_CHECK(gathered.is_cuda() && gathered.scalar_type() == at::kDouble &&
@@ -832,6 +850,7 @@ TORCH_LIBRARY(nngp, m) {
     m.def("bf_cross(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
           "Tensor? ref_values, int algo, float nu=-1.0) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
+    m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
 }
 
@@ -852,6 +871,7 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_dphi", &bf_dphi);
     m.impl("bf_fisher", &bf_fisher);
     m.impl("row_order", &row_order);
+    m.impl("order_maxmin", &order_maxmin);
     m.impl("pair_plan", &pair_plan);
     m.impl("nbr_cert", &nbr_cert);
     m.impl("combine_partials_out", &combine_partials_out);

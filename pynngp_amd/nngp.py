@@ -521,9 +521,27 @@ def _default_device(device):
 
 
 class NNGP:
-    """Nearest-neighbour GP over ordinates ``t`` (mirrors ``pyNNGP.NNGP``)."""
+    """Nearest-neighbour GP over ordinates ``t`` (mirrors ``pyNNGP.NNGP``).
 
-    def __init__(self, t, y, eps, refType, m, cov: CovLike, device=None):
+    The model order.  Every reference point conditions on its ``m`` nearest *earlier* reference points, so the
+    order of the reference set is part of the model.  ``ordering=None`` (the default) takes the caller's row
+    order, as the reference does.  ``ordering="maxmin"`` (the levelled max-min order, :mod:`pynngp_amd.ordering`),
+    ``"random"`` or an explicit permutation orders the reference set before the neighbour sets are built:
+
+    * ``refType='S=T'``: ``t``, ``y`` and a per-point ``eps`` are permuted together, and the instance then lives
+      entirely in model order -- its attributes ``t, y, eps, s, ws, wt``, every ``values=`` / ``X=`` argument,
+      ``nbr``, ``B``, ``F`` and every per-location result are in model order.  ``model.perm`` (device int64,
+      ``perm[k]`` = the input row at model position ``k``; ``None`` without an ordering) and
+      ``model.to_model_order(a)`` / ``model.to_input_order(a)`` (rows of a numpy array or a tensor) convert
+      between the two.
+    * a tuple ``refType``: only the reference set ``s`` is ordered (``perm`` then indexes the drawn ``s``);
+      ``t`` and ``y`` keep the caller's order.
+
+    ``refType=("maxmin", nRef)`` takes as ``s`` the first ``nRef`` points of the max-min order of ``t``, in that
+    order: distinct, space-filling points (``('subset', nRef)`` draws with replacement).
+    """
+
+    def __init__(self, t, y, eps, refType, m, cov: CovLike, device=None, ordering=None):
         self.t = t  # ordinates (held by reference, nngp.py:7)
         self.y = y  # abscissae
         self.eps = eps  # measurement uncertainties in y (stored, unused: SURVEY Appendix A)
@@ -533,6 +551,10 @@ class NNGP:
         self.device = _default_device(device)
         if not 0 <= self.m <= _lib.MAX_M:
             raise ValueError(f"m={m} outside [0, {_lib.MAX_M}]")
+        self.perm = None
+        self._ordering = ordering
+        if ordering is not None and self._same_sets():
+            self._order_inputs(ordering)
 
         self._init_s()
         # the metric of the neighbour search: the per-axis decays of an AnisotropicCovariance, else the plain one
@@ -543,10 +565,74 @@ class NNGP:
         self._make_t_neighbor_sets()
         self._B = self._F = None
 
+    # -- the model order ---------------------------------------------------------
+    def _host_points(self, a, what: str) -> np.ndarray:
+        """``a`` as finite float64 (n, d) host points, d <= 3 (what an ordering is computed from)."""
+        p = np.ascontiguousarray(a, dtype=np.float64)
+        if p.ndim == 1:
+            p = p[:, None]
+        if p.ndim != 2 or not 1 <= p.shape[1] <= _lib.MAX_DIM:
+            raise ValueError(f"{what} must be (N, d) with 1 <= d <= {_lib.MAX_DIM}, got {tuple(p.shape)}")
+        if not np.all(np.isfinite(p)):
+            raise ValueError(f"Input contains NaN or infinity ({what})")
+        return p
+
+    def _order_inputs(self, ordering):
+        """'S=T' with an ordering: permute t, y and a per-point eps together; the instance is in model order."""
+        from . import ordering as _ordering
+
+        t_host = self._host_points(self.t, "ordinates t")
+        n = t_host.shape[0]
+        perm = _ordering.resolve(ordering, torch.as_tensor(t_host).to(self.device))
+        self.perm = torch.as_tensor(perm).to(self.device)
+        self.t = np.asarray(self.t)[perm]
+        y = np.asarray(self.y)
+        if y.shape[:1] != (n,):
+            raise ValueError(f"y must have one row per ordinate ({n}), got {tuple(y.shape)}")
+        self.y = y[perm]
+        if self.eps is not None and np.ndim(self.eps) >= 1 and np.shape(self.eps)[0] == n:
+            self.eps = np.asarray(self.eps)[perm]
+
+    def _order_reference(self, ordering):
+        """A tuple refType with an ordering: the drawn reference set alone is put into model order."""
+        from . import ordering as _ordering
+
+        s_host = self._host_points(self.s, "reference set s")
+        perm = _ordering.resolve(ordering, torch.as_tensor(s_host).to(self.device))
+        self.perm = torch.as_tensor(perm).to(self.device)
+        self.s = np.asarray(self.s)[perm]
+
+    def to_model_order(self, a):
+        """Rows of ``a`` (numpy array or tensor, one row per point of the ordered set, input order) in model
+        order: ``a[perm]``.  Without an ordering: ``a`` itself."""
+        perm = getattr(self, "perm", None)
+        if perm is None:
+            return a
+        if torch.is_tensor(a):
+            return a[perm.to(a.device)]
+        return np.asarray(a)[perm.cpu().numpy()]
+
+    def to_input_order(self, a):
+        """The inverse of :meth:`to_model_order`: rows of a model-order ``a`` back at their input rows."""
+        perm = getattr(self, "perm", None)
+        if perm is None:
+            return a
+        if torch.is_tensor(a):
+            out = torch.empty_like(a)
+            out[perm.to(a.device)] = a
+            return out
+        a = np.asarray(a)
+        out = np.empty_like(a)
+        out[perm.cpu().numpy()] = a
+        return out
+
     # -- construction (nngp.py:21-71) -----------------------------------------
     def _init_s(self):
-        """Reference set S (nngp.py:21-40): 'S=T', ('subset', nRef) or ('random', nRef, bounds)."""
-        self.s = reference_set(self.t, self.refType)
+        """Reference set S (nngp.py:21-40): 'S=T', ('subset', nRef), ('random', nRef, bounds) or
+        ('maxmin', nRef)."""
+        self.s = reference_set(self.t, self.refType, device=self.device)
+        if getattr(self, "_ordering", None) is not None and self.s is not self.t:
+            self._order_reference(self._ordering)
         t_host = np.ascontiguousarray(self.t, dtype=np.float64)
         if not np.all(np.isfinite(t_host)):  # as sklearn's KDTree / KNeighborsRegressor (nngp.py:46,55)
             raise ValueError("Input contains NaN or infinity (ordinates t)")
@@ -1715,11 +1801,13 @@ class NNGP:
         return self._sampler
 
 
-def reference_set(t, refType):
+def reference_set(t, refType, device=None):
     """S for a refType (nngp.py:21-40).  The tuple forms draw from numpy's global RNG with
     the reference's own calls: ('subset', nRef) -> t[np.random.choice(len(t), size=nRef)]
     (with replacement, as nngp.py:36); ('random', nRef, bounds) -> one
-    np.random.uniform(lo, hi, nRef) column per (lo, hi) in bounds (nngp.py:39-40)."""
+    np.random.uniform(lo, hi, nRef) column per (lo, hi) in bounds (nngp.py:39-40).
+    ('maxmin', nRef) -> the first nRef points of the max-min order of t, in that order (no RNG; distinct,
+    space-filling; computed on ``device``, default the current GPU)."""
     if isinstance(refType, str):
         if refType != "S=T":
             raise ValueError(f"unknown refType {refType!r} (only 'S=T' is a string option)")
@@ -1734,7 +1822,13 @@ def reference_set(t, refType):
                 raise ValueError("('random', nRef, bounds) needs bounds")
             nRef, bounds = int(refType[1]), refType[2]
             return np.vstack([np.random.uniform(lo, hi, nRef) for lo, hi in bounds]).T
-        raise ValueError(f"unknown refType kind {typ!r} (expected 'subset' or 'random')")
+        if typ == "maxmin":
+            from .ordering import maxmin_subset
+
+            t_host = np.ascontiguousarray(t, dtype=np.float64)
+            pts = torch.as_tensor(t_host[:, None] if t_host.ndim == 1 else t_host).to(_default_device(device))
+            return np.asarray(t)[maxmin_subset(pts, int(refType[1])).cpu().numpy()]
+        raise ValueError(f"unknown refType kind {typ!r} (expected 'subset', 'random' or 'maxmin')")
     raise TypeError(f"refType must be 'S=T' or a tuple, got {refType!r}")
 
 

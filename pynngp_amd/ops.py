@@ -22,6 +22,8 @@ for tracing.
     torch.ops.nngp.pair_plan(nbr, order, i0, n_points, dim) -> (plan, plan_info)   # wave pair plan (setup)
     torch.ops.nngp.bf_cross(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0) -> (B, F, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
+    torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
+        # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
     torch.ops.nngp.combine_partials_out(gathered, out) -> ()
     torch.ops.nngp.precision_apply(nbr, B, off, rev_j, rev_k, prep, sigma2, d, x) -> A x   # latent-field precision
     torch.ops.nngp.latent_cg(nbr, B, off, rev_j, rev_k, prep, sigma2, d, b, x0=None, rtol=1e-8, max_iter=1000,
@@ -152,6 +154,11 @@ def _register_fakes() -> None:
     def _(coords, i0, rows, nbr):
         srt = torch.empty_like(nbr) if nbr is not None else coords.new_empty((0, 0), dtype=torch.int32)
         return coords.new_empty((rows,), dtype=torch.int32), srt
+
+    @fake("order_maxmin")
+    def _(coords, seed):
+        n = coords.shape[0]
+        return coords.new_empty((n,), dtype=torch.int64), coords.new_empty((n,), dtype=torch.int32)
 
     @fake("combine_partials_out")
     def _(gathered, out):
