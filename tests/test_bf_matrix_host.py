@@ -1,5 +1,6 @@
-"""CPU: the inputs of tests/test_gpu_bf_matrix.py (every pair-sweep instantiation up to m = 24) and the precondition
-of its tolerances.
+"""CPU: the inputs of tests/test_gpu_bf_matrix.py (the pair-sweep instantiations m = 1 .. 24; the kernel is
+instantiated to m = 32, and tests/test_gpu_bf_precision.py covers M_PRECISION = 1 .. 32 on these fields) and the
+precondition of its tolerances.
 
 The GPU file compares the pair kernel with the C oracle (oracle/nngp_oracle.c, fp64) at |dF| <= 1e-10 F and
 |dB| <= 1e-9 (1 + |B|).  Those figures measure the kernel only where the oracle's own fp64 rounding is far below
@@ -22,6 +23,7 @@ from oracle import nngp_oracle as O
 N = 300
 DIMS = (1, 2, 3)
 M_ALL = tuple(range(1, 25))
+M_PRECISION = tuple(range(1, 33))  # the precision files' range (tests/bf_precision_ref.py): every pair instantiation
 SEED = 24
 # one theta per kind; tau2 >= 0.05 keeps the blocks of field B (exact duplicates) positive definite
 THETAS = {
