@@ -202,6 +202,38 @@ int nngp_bf_grad(const double *coords, int64_t n_points, int32_t dim, const int3
                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Per-point noise: y_i = mu + w(s_i) + e_i with e_i ~ N(0, tau2 v_i), v_i >= 0 given per point (added within
+ * revision 4; nothing earlier moved).  noise_var (n_points,) holds the weights v (v = 1 everywhere is the model
+ * of nngp_bf_sweep / nngp_bf_grad).  The diagonal entry of every joint block is sigma2 + tau2 v_j of the point in
+ * that slot -- the location's own entry included --, the weight gathered with the point's coordinates.  The
+ * reference's `eps` ("measurement uncertainties in y", nngp.py:9) squared is v; it has no sweep of its own.
+ *   nngp_bf_sweep_noise: the contract of nngp_bf_sweep (B, F, R, partials[4], order, i0, -1 padding, the two
+ *     flags, NaN rows on a bad pivot, a fixed-order fold), without nu / algo and with partials required.
+ *   nngp_bf_cross_noise: the contract of nngp_bf_cross; noise_ref (n_ref,) weighs the neighbour block,
+ *     noise_query (n_query,) or NULL (1) the query point's own diagonal entry.
+ *   nngp_bf_grad_noise: the contract of nngp_bf_grad (G, partials[4], grad[3] in (sigma2, phi, tau2)) with
+ *     d/dtau2: dF = v_i + sum_j b_j^2 v_j, dr = sum_j a_j b_j v_j; d/dsigma2: dF = (F - tau2 dF_tau2) / sigma2,
+ *     dr = -tau2 dr_tau2 / sigma2; d/dphi unchanged.
+ * Scope: kinds NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL, 1 <= m <= 32, 1 <= dim <= 3, else NNGP_EUNSUP.
+ * workspace: nngp_bf_sweep_noise_workspace_bytes(n_rows, m) for the sweep and the cross form,
+ * nngp_bf_grad_workspace_bytes(n_rows, m) for the gradient; 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_noise_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_sweep_noise(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                        int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                        const double *values, const double *noise_var, double *B, double *F, double *R,
+                        double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_noise(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                        const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                        double sigma2, double phi, double tau2, const double *ref_values, const double *query_values,
+                        const double *noise_ref, const double *noise_query, double *B, double *F, double *R,
+                        double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_grad_noise(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                       const double *values, const double *noise_var, double *G, double *partials, double *grad,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,
  * order and i0 as nngp_bf_sweep).  With D_ab = sigma2 d_ab rho'(phi d_ab) and u = [-B_i; 1]:
  *   B  (n_rows, m), F (n_rows,): the factors of nngp_bf_sweep at this theta, equal to that sweep's to its own

@@ -70,6 +70,10 @@ SYMBOLS = (
     "nngp_bf_sweep_cert",
     "nngp_bf_grad_workspace_bytes",
     "nngp_bf_grad",
+    "nngp_bf_sweep_noise_workspace_bytes",
+    "nngp_bf_sweep_noise",
+    "nngp_bf_cross_noise",
+    "nngp_bf_grad_noise",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
     "nngp_bf_grad_matern_workspace_bytes",
@@ -174,6 +178,15 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_grad_workspace_bytes.restype = SZ
     lib.nngp_bf_grad.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad.restype = ctypes.c_int
+    lib.nngp_bf_sweep_noise_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_sweep_noise_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_noise.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_noise.restype = ctypes.c_int
+    lib.nngp_bf_cross_noise.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, P, P, P,
+                                        SZ, P]
+    lib.nngp_bf_cross_noise.restype = ctypes.c_int
+    lib.nngp_bf_grad_noise.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_noise.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
     lib.nngp_bf_grad_aniso_workspace_bytes.restype = SZ
     lib.nngp_bf_grad_aniso.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
@@ -1033,6 +1046,142 @@ def bf_cross(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: st
                              _ptr(query_values), _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace),
                              workspace.numel(), a, _stream(dev)), "nngp_bf_cross")
     return B, F, partials
+
+
+def _noise_checks(kind: str, m: int) -> None:
+    """The scope of the per-point noise sweeps (nngp_bf_*_noise): kinds exponential .. spherical, 1 <= m <= 32."""
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "matern":
+        raise NotImplementedError("the per-point noise sweeps serve the kinds exponential .. spherical, not the "
+                                  "general-nu matern kind")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the per-point noise sweeps serve 1 <= m <= {GRAD_MAX_M} (m={m})")
+
+
+def _noise_var(v: Optional[torch.Tensor], n: int, name: str) -> torch.Tensor:
+    if v is None or v.dtype != torch.float64 or v.shape != (n,):
+        raise ValueError(f"{name} must be float64 ({n},)")
+    return v.contiguous()
+
+
+def bf_sweep_noise(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,
+                   noise_var: torch.Tensor, values: Optional[torch.Tensor] = None, want_bf: bool = True,
+                   order: Optional[torch.Tensor] = None, want_r: bool = False,
+                   workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep` with per-point noise (``nngp_bf_sweep_noise``, include/nngp.h): the noise variance of point j
+    is ``tau2 * noise_var[j]`` (float64 (N,), >= 0), so every joint block's diagonal is ``sigma2 + tau2 v_j`` of the
+    point in that slot.  Returns ``(B, F, R, partials)`` (B, F None without ``want_bf``; R None without ``want_r``,
+    which needs ``values``).  Kinds exponential .. spherical, 1 <= m <= 32; ``order`` as in :func:`bf_sweep`.
+    """
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n = coords.shape[0]
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (n,):
+            raise ValueError("values must be float64 (N,)")
+        values = values.contiguous()
+    noise_var = _noise_var(noise_var, n, "noise_var")
+    rows, m = nbr.shape
+    _noise_checks(kind, m)
+    dev = _require_gpu(coords, nbr, values, noise_var, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and values is None:
+        raise ValueError("want_r needs values")
+    lib = load()
+    need = lib.nngp_bf_sweep_noise_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev) if want_bf else None
+    F = torch.empty((rows,), dtype=torch.float64, device=dev) if want_bf else None
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_noise(_ptr(coords), n, coords.shape[1], _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                   KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(values),
+                                   _ptr(noise_var), _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace),
+                                   workspace.numel(), _stream(dev)), "nngp_bf_sweep_noise")
+    return B, F, R, partials
+
+
+def bf_grad_noise(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi: float, tau2: float,
+                  values: torch.Tensor, noise_var: torch.Tensor, want_rows: bool = False,
+                  order: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`bf_grad` with per-point noise (``nngp_bf_grad_noise``): ``(partials, grad, G)`` of the model whose
+    noise variance at point j is ``tau2 * noise_var[j]``; grad in (sigma2, phi, tau2)."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n = coords.shape[0]
+    if values is None or values.dtype != torch.float64 or values.shape != (n,):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    noise_var = _noise_var(noise_var, n, "noise_var")
+    rows, m = nbr.shape
+    _noise_checks(kind, m)
+    dev = _require_gpu(coords, nbr, values, noise_var, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_grad_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(3, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, 3), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_noise(_ptr(coords), n, coords.shape[1], _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                  KIND_CODES[kind], float(sigma2), float(phi), float(tau2), _ptr(values),
+                                  _ptr(noise_var), _ptr(G), _ptr(partials), _ptr(grad), _ptr(workspace),
+                                  workspace.numel(), _stream(dev)), "nngp_bf_grad_noise")
+    return partials, grad, G
+
+
+def bf_cross_noise(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: str, sigma2: float, phi: float,
+                   tau2: float, noise_ref: torch.Tensor, noise_query: Optional[torch.Tensor] = None,
+                   ref_values: Optional[torch.Tensor] = None, query_values: Optional[torch.Tensor] = None,
+                   q0: int = 0, order: Optional[torch.Tensor] = None, want_r: bool = False):
+    """:func:`bf_cross` with per-point noise (``nngp_bf_cross_noise``): ``noise_ref`` (n_ref,) weighs the neighbour
+    block, ``noise_query`` (n_query,) or None (1) the query point's own diagonal entry.  Returns
+    ``(B, F, R, partials)`` (R None without ``want_r``, which needs ``ref_values``)."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if ref_values is not None:
+        if ref_values.dtype != torch.float64 or ref_values.shape != (ref.shape[0],):
+            raise ValueError("ref_values must be float64 (n_ref,)")
+        ref_values = ref_values.contiguous()
+    if query_values is not None:
+        if query_values.dtype != torch.float64 or query_values.shape != (query.shape[0],):
+            raise ValueError("query_values must be float64 (n_query,)")
+        query_values = query_values.contiguous()
+    noise_ref = _noise_var(noise_ref, ref.shape[0], "noise_ref")
+    if noise_query is not None:
+        noise_query = _noise_var(noise_query, query.shape[0], "noise_query")
+    rows, m = nbr.shape
+    _noise_checks(kind, m)
+    dev = _require_gpu(ref, query, nbr, ref_values, query_values, noise_ref, noise_query, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and ref_values is None:
+        raise ValueError("want_r needs ref_values")
+    lib = load()
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev)
+    F = torch.empty((rows,), dtype=torch.float64, device=dev)
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_noise_workspace_bytes(rows, m), dev)
+    _check(lib.nngp_bf_cross_noise(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order), rows,
+                                   m, int(q0), KIND_CODES[kind], float(sigma2), float(phi), float(tau2),
+                                   _ptr(ref_values), _ptr(query_values), _ptr(noise_ref), _ptr(noise_query), _ptr(B),
+                                   _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_cross_noise")
+    return B, F, R, partials
 
 
 def joint_dist(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, qcoords: Optional[torch.Tensor] = None,

@@ -119,6 +119,42 @@ class _LogLikMatern(torch.autograd.Function):
         return None, None, gtheta, gvalues, None
 
 
+class _LogLikNoise(torch.autograd.Function):
+    """Per-point noise tau2 * v (``torch.ops.nngp.bf_grad_noise``); no gradient with respect to v."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, kind, order, v):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_noise(coords, nbr, order, 0, _lib.KIND_CODES[kind], th[0], th[1], th[2],
+                                               values.detach(), v, False)
+        ctx.save_for_backward(coords, nbr, values, g, v)
+        ctx.meta = (kind, order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g, v = ctx.saved_tensors
+        kind, order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLik: one ordinary sweep (B, F, R) of the same model
+            B, F, R, _ = _lib.bf_sweep_noise(coords, nbr, 0, kind, th[0], th[1], th[2], v, values=values.detach(),
+                                             order=order, want_r=True)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None, None, None
+
+
 def loglik_matern(coords, nbr, theta, values, order=None):
     """NNGP log-likelihood of ``values`` on S = T under the general-smoothness Matern covariance at ``theta`` =
     (sigma2, phi, tau2, nu), a float64 (4,) tensor, differentiable in all four entries of ``theta`` and, when
@@ -142,7 +178,7 @@ def loglik_matern(coords, nbr, theta, values, order=None):
     return ll
 
 
-def loglik(coords, nbr, theta, values, kind, order=None):
+def loglik(coords, nbr, theta, values, kind, order=None, noise=None):
     """NNGP log-likelihood of ``values`` on S = T at ``theta`` = (sigma2, phi, tau2), a float64 (3,) tensor,
     differentiable in ``theta`` and, when ``values.requires_grad``, in ``values``.
 
@@ -154,6 +190,9 @@ def loglik(coords, nbr, theta, values, kind, order=None):
     reads theta before the launch and the sweep's two flags after it.  Backward returns ``grad_out * grad`` for theta with no further launch; the gradient in
     the values costs one ordinary sweep.  ``nbr`` (N, m) int32 with 1 <= m <= 32, ``order`` as in ``bf_sweep``
     (pass the sorted rows); kinds exponential .. spherical.  The not-PD and bad-index flags raise.
+
+    ``noise``: a float64 (N,) device tensor of per-point noise sigmas e (the reference's ``eps``): the noise variance
+    of point j is ``tau2 * e_j^2`` (``torch.ops.nngp.bf_grad_noise``; the (3,) theta only).  No gradient flows to it.
     """
     if kind not in _lib.KIND_CODES:
         raise ValueError(f"unknown covariance kind {kind!r}")
@@ -169,7 +208,16 @@ def loglik(coords, nbr, theta, values, kind, order=None):
         raise NotImplementedError(f"loglik's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
     if nbr.shape[0] != coords.shape[0]:
         raise ValueError("loglik is an S = T sweep: one nbr row per location")
-    ll, p = (_LogLikAniso if aniso else _LogLik).apply(coords, nbr, theta, values, kind, order)
+    if noise is not None:
+        if aniso:
+            raise NotImplementedError("loglik(noise=...) serves the isotropic (3,) theta: the per-point noise sweeps "
+                                      "have no per-axis form")
+        if not isinstance(noise, torch.Tensor) or noise.dtype != torch.float64 or noise.shape != (coords.shape[0],):
+            raise ValueError("noise must be a float64 (N,) tensor of per-point sigmas")
+        e = noise.detach()
+        ll, p = _LogLikNoise.apply(coords, nbr, theta, values, kind, order, e * e)
+    else:
+        ll, p = (_LogLikAniso if aniso else _LogLik).apply(coords, nbr, theta, values, kind, order)
     from .nngp import _raise_on_bad
 
     _raise_on_bad(p.detach().cpu().numpy())

@@ -370,5 +370,7 @@ bool bf_grad_launch_f(const GradArgs& a, hipStream_t s);
 bool bf_grad_launch_g(const GradArgs& a, hipStream_t s);
 bool bf_grad_launch_h(const GradArgs& a, hipStream_t s);
 hipError_t bf_grad_launch(const GradArgs& a, double* partials, double* grad, hipStream_t s);
+// the fold alone: n_blocks records of kGradRec doubles (block_grad_store) -> partials[4], grad[3]
+hipError_t bf_grad_fold_launch(const double* rec, int64_t n_blocks, double* partials, double* grad, hipStream_t s);
 
 }  // namespace nngp

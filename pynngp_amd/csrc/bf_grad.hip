@@ -71,7 +71,11 @@ hipError_t bf_grad_launch(const GradArgs& a, double* partials, double* grad, hip
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(bf_grad_finalize, dim3(1), dim3(1024), 0, s, a.rec, nb, partials, grad);
+    return bf_grad_fold_launch(a.rec, nb, partials, grad, s);
+}
+
+hipError_t bf_grad_fold_launch(const double* rec, int64_t n_blocks, double* partials, double* grad, hipStream_t s) {
+    hipLaunchKernelGGL(bf_grad_finalize, dim3(1), dim3(1024), 0, s, rec, n_blocks, partials, grad);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include "bf_pairb.h"
 #include "nbr_cert.h"
 #include "bf_grad.h"
+#include "bf_noise.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -221,6 +222,87 @@ int nngp_bf_grad(const double* coords, int64_t n_points, int32_t dim, const int3
                      (double*)workspace};
     hipError_t e = nngp::bf_grad_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_sweep_noise_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * 4 * sizeof(double));
+}
+
+// the checks the three per-point noise entry points share (theta, scope, workspace); need: the workspace size
+static int noise_common(const double* coords, int64_t n_points, int32_t dim, const double* noise, const int32_t* nbr,
+                        int64_t n_rows, int32_t m, int64_t i0, int64_t n_locs, int32_t kind, double sigma2, double phi,
+                        double tau2, double* partials, void* workspace, size_t workspace_bytes, size_t need) {
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (noise == nullptr || partials == nullptr) return fail(NNGP_EINVAL, "the noise weights and partials must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the per-point noise sweeps serve 1 <= m <= 32 (m=%d)", m);
+    if (kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the per-point noise sweeps serve kinds exponential .. spherical, not the general-nu "
+                                 "matern");
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EINVAL, "unknown kind %d", kind);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_locs)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_locs);
+    if (!(sigma2 > 0.0) || !(phi > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(phi) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, phi > 0, tau2 >= 0 (finite)");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return NNGP_OK;
+}
+
+static int noise_forward(const double* coords, int64_t n_points, int32_t dim, const double* qcoords, int64_t n_locs,
+                         const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
+                         double sigma2, double phi, double tau2, const double* values, const double* qvalues,
+                         const double* noise, const double* qnoise, double* B, double* F, double* R, double* partials,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (qcoords == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    const int rc = noise_common(coords, n_points, dim, noise, nbr, n_rows, m, i0, n_locs, kind, sigma2, phi, tau2,
+                                partials, workspace, workspace_bytes, nngp_bf_sweep_noise_workspace_bytes(n_rows, m));
+    if (rc != NNGP_OK) return rc;
+    if (B != nullptr && F == nullptr) return fail(NNGP_EINVAL, "B given without F");
+    if (F != nullptr && B == nullptr && n_rows > 0) return fail(NNGP_EINVAL, "F given without B");
+    if (R != nullptr && values == nullptr) return fail(NNGP_EINVAL, "R (residuals) needs values");
+    nngp::NoiseArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, phi, tau2, values, noise, qcoords,
+                      qvalues, qnoise, B, F, R, nullptr, (double*)workspace};
+    hipError_t e = nngp::bf_noise_launch(a, partials, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_noise launch");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_noise(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                        int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                        const double* values, const double* noise_var, double* B, double* F, double* R,
+                        double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    return noise_forward(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2,
+                         values, values, noise_var, noise_var, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_cross_noise(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,
+                        const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                        double sigma2, double phi, double tau2, const double* ref_values, const double* query_values,
+                        const double* noise_ref, const double* noise_query, double* B, double* F, double* R,
+                        double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    if (query_values != nullptr && ref_values == nullptr) return fail(NNGP_EINVAL, "query_values need ref_values");
+    return noise_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, m, q0, kind, sigma2, phi, tau2, ref_values,
+                         query_values, noise_ref, noise_query, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_grad_noise(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, double phi, double tau2,
+                       const double* values, const double* noise_var, double* G, double* partials, double* grad,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (values == nullptr || grad == nullptr) return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    const int rc = noise_common(coords, n_points, dim, noise_var, nbr, n_rows, m, i0, n_points, kind, sigma2, phi, tau2,
+                                partials, workspace, workspace_bytes, nngp_bf_grad_workspace_bytes(n_rows, m));
+    if (rc != NNGP_OK) return rc;
+    nngp::NoiseArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, phi, tau2, values, noise_var, coords,
+                      values, noise_var, nullptr, nullptr, nullptr, G, (double*)workspace};
+    hipError_t e = nngp::bf_noise_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_noise launch");
     return NNGP_OK;
 }
 

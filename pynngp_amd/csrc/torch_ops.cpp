@@ -377,6 +377,99 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross(const at::Tensor& ref, c
     return {B, F, mean};
 }
 
+// ---------------------------------------------------------------- per-point noise (nngp_bf_*_noise)
+static void check_order(const c10::optional<at::Tensor>& order, int64_t rows, const at::Tensor& like) {
+    if (!order.has_value()) return;
+    TORCH_CHECK(order->scalar_type() == at::kInt && order->dim() == 1 && order->size(0) == rows && order->is_contiguous(),
+                "order must be a contiguous int32 (rows,) tensor");
+    check_same_device(like, *order, "order");
+}
+
+// (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_noise(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    double sigma2, double phi, double tau2, const c10::optional<at::Tensor>& values, const at::Tensor& noise_var,
+    bool want_bf) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(values, {n}, coords, "values");
+    check_f64(noise_var, {n}, coords, "noise_var");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool wr = values.has_value();
+    at::Tensor B = at::empty({want_bf ? rows : 0, m}, f64), F = at::empty({want_bf ? rows : 0}, f64);
+    at::Tensor R = at::empty({wr ? rows : 0}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_noise_workspace_bytes(rows, (int32_t)m), coords);
+    check_rc(nngp_bf_sweep_noise(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                                 ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2,
+                                 ptr<double>(values), noise_var.data_ptr<double>(), want_bf ? B.data_ptr<double>() : nullptr,
+                                 want_bf ? F.data_ptr<double>() : nullptr, wr ? R.data_ptr<double>() : nullptr,
+                                 p.data_ptr<double>(), ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_noise");
+    return {B, F, R, p};
+}
+
+// (partials (4,), grad (3,), G (rows, 3) or (0, 3)), as bf_grad
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_noise(const at::Tensor& coords, const at::Tensor& nbr,
+                                                             const c10::optional<at::Tensor>& order, int64_t i0,
+                                                             int64_t kind, double sigma2, double phi, double tau2,
+                                                             const at::Tensor& values, const at::Tensor& noise_var,
+                                                             bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(values, {n}, coords, "values");
+    check_f64(noise_var, {n}, coords, "noise_var");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({3}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, 3}, f64);
+    const int64_t need = (int64_t)nngp_bf_grad_workspace_bytes(rows, (int32_t)m);
+    auto ws = at::empty({need > 256 ? need : 256}, f64.dtype(at::kByte));
+    check_rc(nngp_bf_grad_noise(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                                ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind, sigma2, phi, tau2,
+                                values.data_ptr<double>(), noise_var.data_ptr<double>(),
+                                want_rows ? G.data_ptr<double>() : nullptr, p.data_ptr<double>(), g.data_ptr<double>(),
+                                ws.data_ptr(), (size_t)ws.numel(), stream(coords)),
+             "nngp_bf_grad_noise");
+    return {p, g, G};
+}
+
+// (B, F, kriging mean), as bf_cross
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_noise(const at::Tensor& ref, const at::Tensor& query,
+                                                              const at::Tensor& nbr, int64_t kind, double sigma2,
+                                                              double phi, double tau2,
+                                                              const c10::optional<at::Tensor>& ref_values,
+                                                              const at::Tensor& noise_ref,
+                                                              const c10::optional<at::Tensor>& noise_query) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    check_f64(ref_values, {ref.size(0)}, ref, "ref_values");
+    check_f64(noise_ref, {ref.size(0)}, ref, "noise_ref");
+    check_f64(noise_query, {query.size(0)}, ref, "noise_query");
+    auto f64 = ref.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64), R = at::empty({rows}, f64);
+    at::Tensor p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_noise_workspace_bytes(rows, (int32_t)m), ref);
+    check_rc(nngp_bf_cross_noise(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(), query.size(0),
+                                 nbr.data_ptr<int32_t>(), nullptr, rows, (int32_t)m, 0, (int32_t)kind, sigma2, phi, tau2,
+                                 ptr<double>(ref_values), nullptr, noise_ref.data_ptr<double>(), ptr<double>(noise_query),
+                                 B.data_ptr<double>(), F.data_ptr<double>(),
+                                 ref_values.has_value() ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(),
+                                 ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_noise");
+    at::Tensor mean = ref_values.has_value() ? R.neg() : at::zeros({rows}, f64);
+    return {B, F, mean};
+}
+
 // the wave pair plan of a sweep over nbr (include/nngp.h nngp_pair_plan_build): (plan bytes on the GPU,
 // CPU int64 info).  A setup call: it synchronises the tensors' stream once.
 std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0,
@@ -849,6 +942,12 @@ TORCH_LIBRARY(nngp, m) {
     m.def("pair_plan(Tensor nbr, Tensor? order, int i0, int n_points, int dim) -> (Tensor, Tensor)");
     m.def("bf_cross(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
           "Tensor? ref_values, int algo, float nu=-1.0) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_noise(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, "
+          "float tau2, Tensor? values, Tensor noise_var, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_grad_noise(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float phi, "
+          "float tau2, Tensor values, Tensor noise_var, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_cross_noise(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
+          "Tensor? ref_values, Tensor noise_ref, Tensor? noise_query) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
     m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
@@ -865,6 +964,9 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_out", &bf_sweep_out);
     m.impl("bf_cross", &bf_cross);
     m.impl("bf_grad", &bf_grad);
+    m.impl("bf_sweep_noise", &bf_sweep_noise);
+    m.impl("bf_grad_noise", &bf_grad_noise);
+    m.impl("bf_cross_noise", &bf_cross_noise);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

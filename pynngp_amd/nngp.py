@@ -512,6 +512,21 @@ def _sweep_any(cv, coords, nbr, i0=0, values=None, want_bf=True, algo="auto", or
                          R=R, nu=cv.nu_arg)
 
 
+_NOISE_SCOPE = ("per-point noise (noise=) serves refType='S=T', a Covariance of kind exponential .. spherical, "
+                "1 <= m <= 32 and mean='constant' or 'zero'")
+
+
+def _refuse_noise(what: str):
+    raise NotImplementedError(f"{what} is not served with noise=: {_NOISE_SCOPE}")
+
+
+class _NoiseVar:
+    """Validated per-point noise weights v = e^2 on the device (what ``noise=`` resolves to; a fit resolves once)."""
+
+    def __init__(self, v: torch.Tensor):
+        self.v = v
+
+
 def _default_device(device):
     if device is not None:
         return torch.device(device)
@@ -544,7 +559,9 @@ class NNGP:
     def __init__(self, t, y, eps, refType, m, cov: CovLike, device=None, ordering=None):
         self.t = t  # ordinates (held by reference, nngp.py:7)
         self.y = y  # abscissae
-        self.eps = eps  # measurement uncertainties in y (stored, unused: SURVEY Appendix A)
+        # measurement uncertainties in y (nngp.py:9): per-point noise sigmas for oneSample, latent_posterior and,
+        # through noise="eps", the response model (loglik, loglik_grad, profile_loglik, fit, predict)
+        self.eps = eps
         self.refType = refType
         self.m = int(m)
         self.cov = cov
@@ -773,8 +790,44 @@ class NNGP:
         return self._Nt
 
     # -- prediction at t ------------------------------
+    # -- per-point noise in the response model ---------------------------------
+    def _noise_sigmas(self, e, n: int, what: str, positive: bool) -> torch.Tensor:
+        """``n`` per-point sigmas as the device weights v = e^2 (finite; positive, or >= 0 for an explicit array)."""
+        e = e.detach().cpu().numpy() if isinstance(e, torch.Tensor) else e
+        e = None if e is None else np.asarray(e, dtype=np.float64)
+        if e is None or e.shape != (n,):
+            raise ValueError(f"{what} must hold one sigma per location ({n},), got "
+                             f"{'None' if e is None else e.shape}")
+        if not np.all(np.isfinite(e)) or np.any(e <= 0 if positive else e < 0):
+            raise ValueError(f"{what} must be finite and {'positive' if positive else 'non-negative'}")
+        return torch.from_numpy(e * e).to(self.device)
+
+    def _noise_setup(self, noise, cov=None):
+        """``noise=`` of the response-model methods: ``(cv, v)`` with ``cv`` the fused-kind :class:`Covariance` and
+        ``v`` the device weights (noise variance tau2 v_i).  ``"eps"``: the instance's per-location sigmas, as
+        :meth:`oneSample` and :meth:`latent_posterior` read them; an array: sigmas in model order."""
+        if not self._same_sets():
+            _refuse_noise(f"refType={self.refType!r}")
+        c = self.cov if cov is None else cov
+        if isinstance(c, AnisotropicCovariance):
+            _refuse_noise("an AnisotropicCovariance")
+        if not isinstance(c, Covariance):
+            _refuse_noise(f"a callable or custom covariance ({type(c).__name__})")
+        if c.kind == "matern":
+            _refuse_noise("the general-nu matern kind")
+        if not 1 <= self.m <= _lib.GRAD_MAX_M:
+            _refuse_noise(f"m={self.m}")
+        if isinstance(noise, _NoiseVar):
+            return c, noise.v
+        n = self.nbr.shape[0]
+        if isinstance(noise, str):
+            if noise != "eps":
+                raise ValueError(f"noise must be None, 'eps' or an array of sigmas, got {noise!r}")
+            return c, self._noise_sigmas(self.eps, n, "noise='eps': the instance's eps", positive=True)
+        return c, self._noise_sigmas(noise, n, "noise", positive=False)
+
     def predict(self, values=None, cov: Optional[Covariance] = None, query=None, algo: str = "auto", X=None,
-                X_query=None):
+                X_query=None, noise=None, noise_query=None):
         """Kriging of the NNGP at the points ``query`` (default ``t``) from ``values`` on S
         (default ``ws``): returns numpy ``(mean, var)`` with mean_t = B_t v_N(t) and
         var_t = F_t (conditional variance; includes tau2 like C_tt = sigma2 + tau2).
@@ -783,9 +836,18 @@ class NNGP:
 
         ``X`` (n, p) and ``X_query`` (n_query, p): universal kriging of ``values`` (default ``y``) with the
         regression mean X beta, beta by GLS at ``cov`` (:meth:`gls`): mean x_q' beta + B_q (y - X beta)_N and
-        variance F_q + h_q' cov_beta h_q, h_q = x_q - B_q X_N (``pynngp_amd.regression.universal_kriging``)."""
+        variance F_q + h_q' cov_beta h_q, h_q = x_q - B_q X_N (``pynngp_amd.regression.universal_kriging``).
+
+        ``noise`` (``"eps"`` or sigmas e in model order): the reference points' noise variances are tau2 e_j^2 in
+        the neighbour blocks (``nngp_bf_cross_noise``); ``noise_query`` (n_query,) sigmas set the predicted points' own
+        noise variance (default 1: var_t includes tau2).  ``algo`` is not used then."""
         if (X is None) != (X_query is None):
             raise ValueError("universal kriging needs both X and X_query")
+        if noise is None and noise_query is not None:
+            raise ValueError("noise_query needs noise")
+        if noise is not None and X is not None:
+            _refuse_noise("universal kriging (X, X_query)")
+        nzv = None if noise is None else self._noise_setup(noise, cov)[1]
         if X is not None:
             from . import regression
 
@@ -812,6 +874,12 @@ class NNGP:
             if isinstance(cv, Covariance):
                 return np.zeros(n), np.full(n, cv.sigma2 + cv.tau2)
             return np.zeros(n), cv.marginal(q).cpu().numpy()
+        if nzv is not None:
+            nq = None if noise_query is None else self._noise_sigmas(noise_query, n, "noise_query", positive=False)
+            _, F, R, p = _lib.bf_cross_noise(sc, q, nbr, cv.kind, *cv.theta[:3], nzv, noise_query=nq, ref_values=v,
+                                             want_r=True)
+            _raise_on_bad(p.cpu().numpy())
+            return (-R).cpu().numpy(), F.cpu().numpy()
         R = torch.empty(n, dtype=torch.float64, device=self.device)
         _, F, p = _sweep_any(cv, sc, nbr, 0, values=v, algo=algo, R=R, qcoords=q)
         _raise_on_bad(p.cpu().numpy())
@@ -925,8 +993,19 @@ class NNGP:
     def F(self):
         return self.compute_BF()[1] if self._F is None else self._F
 
-    def loglik(self, values=None, cov: Optional[Covariance] = None, algo: str = "auto") -> float:
-        """NNGP log density of ``values`` (default ``y``): -1/2 sum [log 2pi + log F + r^2/F]."""
+    def loglik(self, values=None, cov: Optional[Covariance] = None, algo: str = "auto", noise=None) -> float:
+        """NNGP log density of ``values`` (default ``y``): -1/2 sum [log 2pi + log F + r^2/F].
+
+        ``noise``: ``"eps"`` (the instance's per-location sigmas) or an array of sigmas e in model order: the noise
+        variance of point i is tau2 e_i^2 instead of tau2 (``nngp_bf_sweep_noise``; ``algo`` is not used then)."""
+        if noise is not None:
+            cv, nzv = self._noise_setup(noise, cov)
+            v = self._values_dev(values)
+            _, _, _, p = _lib.bf_sweep_noise(self._s_dev, self._nbr_sorted, 0, cv.kind, *cv.theta[:3], nzv, values=v,
+                                             want_bf=False, order=self._order)
+            ph = p.cpu().numpy()
+            _raise_on_bad(ph)
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + ph[0] + ph[1])
         cv, sc = self._sweep_cov(cov)
         v = self.y if values is None else values
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
@@ -940,7 +1019,7 @@ class NNGP:
         n = self.nbr.shape[0]
         return -0.5 * (n * LOG_2PI + ph[0] + ph[1])
 
-    def gls(self, cov: Optional[Covariance], X, values=None, reml: bool = False, algo: str = "auto"):
+    def gls(self, cov: Optional[Covariance], X, values=None, reml: bool = False, algo: str = "auto", noise=None):
         """GLS of ``values`` (default y) on the design ``X`` (n, p; p + 1 <= 16; the caller adds the intercept
         column) under the NNGP precision at ``cov``: one sweep that writes B and F, then one ``nngp_whiten_gram`` on
         [y, X]; the p x p algebra on the host.  Returns a :class:`pynngp_amd.regression.GLSResult` (``beta``,
@@ -948,10 +1027,12 @@ class NNGP:
         likelihood, else the profile likelihood.  A rank-deficient ``X`` raises :class:`NNGPNumericalError`."""
         from . import regression
 
+        if noise is not None:
+            _refuse_noise("gls (a regression mean)")
         return regression.gls(self, cov, X, values=values, reml=reml, algo=algo)
 
     def conjugate(self, kind: str, phi: float, alpha: float, X, prior: Optional[dict] = None,
-                  nu: Optional[float] = None, values=None, algo: str = "auto"):
+                  nu: Optional[float] = None, values=None, algo: str = "auto", noise=None):
         """The conjugate NNGP (Finley et al.; spNNGP's ``spConjNNGP``) of ``values`` (default y) on ``X`` at fixed
         (phi, alpha = tau2 / sigma2), computed at ``Covariance(kind, 1, phi, alpha)``: beta and sigma2 integrate out
         in closed form.  ``prior``: dict ``a``, ``b`` (sigma2 ~ IG(a, b), default 2, 1) and optionally ``mu``, ``V``
@@ -960,6 +1041,8 @@ class NNGP:
         ``predict(query, X_query)``, the Student-t predictive (location, scale, 2 a degrees of freedom)."""
         from . import regression
 
+        if noise is not None:
+            _refuse_noise("conjugate")
         _refuse_aniso(self.cov, "conjugate")
         return regression.conjugate(self, kind, phi, alpha, X, prior=prior, nu=nu, values=values, algo=algo)
 
@@ -972,13 +1055,17 @@ class NNGP:
         _refuse_aniso(self.cov, "conjugate_grid")
         return regression.conjugate_grid(self, phis, alphas, kind, X, prior=prior, nu=nu, values=values, algo=algo)
 
-    def profile_loglik(self, cov: Covariance, values=None, mean: str = "constant", algo: str = "auto", X=None):
+    def profile_loglik(self, cov: Covariance, values=None, mean: str = "constant", algo: str = "auto", X=None,
+                       noise=None):
         """NNGP log-likelihood of ``values`` (default y) at ``cov`` with a constant mean
         profiled out by GLS under the NNGP precision (I - B)^T F^-1 (I - B):
         mu = sum(r1 ry / F) / sum(r1^2 / F), r1 = (I - B) 1, ry = (I - B) y (two fused
         sweeps with residual output).  ``mean="zero"`` is :meth:`loglik`.  Returns
         ``(loglik, mu)``.  ``mean="linear"`` with ``X`` (n, p): the regression mean X beta profiled out
-        (:meth:`gls`: one sweep and one whitened Gram); returns ``(loglik, beta)``."""
+        (:meth:`gls`: one sweep and one whitened Gram); returns ``(loglik, beta)``.  ``noise``: as :meth:`loglik`
+        (constant and zero means)."""
+        if noise is not None and (mean == "linear" or X is not None):
+            _refuse_noise("mean='linear'")
         if mean == "linear":
             if X is None:
                 raise ValueError("mean='linear' needs the design matrix X")
@@ -990,10 +1077,23 @@ class NNGP:
         v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not isinstance(v, torch.Tensor) else v,
                             dtype=torch.float64).to(self.device)
         if mean == "zero":
-            return self.loglik(v, cov, algo), 0.0
+            return self.loglik(v, cov, algo, noise=noise), 0.0
         if mean != "constant":
             raise ValueError("mean must be 'constant', 'zero' or 'linear'")
         n = v.shape[0]
+        if noise is not None:
+            cv, nzv = self._noise_setup(noise, cov)
+            v = self._values_dev(v)
+            kw = dict(want_bf=True, want_r=True, order=self._order)
+            _, F, ry, py = _lib.bf_sweep_noise(self._s_dev, self._nbr_sorted, 0, cv.kind, *cv.theta[:3], nzv, values=v,
+                                               **kw)
+            _, _, r1, p1 = _lib.bf_sweep_noise(self._s_dev, self._nbr_sorted, 0, cv.kind, *cv.theta[:3], nzv,
+                                               values=torch.ones_like(v), **kw)
+            sums = torch.stack([py[0], py[1], p1[1], torch.sum(ry * r1 / F), py[2], py[3]]).cpu().numpy()
+            _raise_on_bad(np.array([0.0, 0.0, sums[4], sums[5]]))
+            logF, qyy, q11, qy1 = sums[:4]
+            mu = qy1 / q11
+            return -0.5 * (n * LOG_2PI + logF + qyy - 2.0 * mu * qy1 + mu * mu * q11), float(mu)
         ry = torch.empty(n, dtype=torch.float64, device=self.device)
         r1 = torch.empty_like(ry)
         cov, sc = self._sweep_cov(cov)
@@ -1043,12 +1143,20 @@ class NNGP:
             raise ValueError(f"one value per location is needed ({self.nbr.shape[0]}, 1-D)")
         return v
 
-    def loglik_grad(self, values=None, cov: Optional[Covariance] = None):
+    def loglik_grad(self, values=None, cov: Optional[Covariance] = None, noise=None):
         """:meth:`loglik` and its analytic gradient in (sigma2, phi, tau2) from one fused gradient sweep
         (``nngp_bf_grad``): ``(loglik, grad)`` with ``grad`` a float64 ndarray (3,).  An
         :class:`AnisotropicCovariance` gives the gradient in (sigma2, phi_1 .. phi_dim, tau2), (dim + 2,), from one
         ``nngp_bf_grad_aniso`` sweep on the raw coordinates; a :class:`MaternCovariance` the gradient in
-        (sigma2, phi, tau2, nu), (4,), from one ``nngp_bf_grad_matern`` sweep."""
+        (sigma2, phi, tau2, nu), (4,), from one ``nngp_bf_grad_matern`` sweep.  ``noise``: as :meth:`loglik`, the
+        gradient in (sigma2, phi, tau2) from one ``nngp_bf_grad_noise`` sweep (tau2 scales the given variances)."""
+        if noise is not None:
+            cv, nzv = self._noise_setup(noise, cov)
+            p, g, _ = _lib.bf_grad_noise(self._s_dev, self._nbr_sorted, 0, cv.kind, *cv.theta[:3],
+                                         self._values_dev(values), nzv, order=self._order)
+            h = torch.cat([p, g]).cpu().numpy()
+            _raise_on_bad(h[:4])
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:7].copy()
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
         if isinstance(cv, MaternCovariance):
@@ -1070,11 +1178,22 @@ class NNGP:
         n = self.nbr.shape[0]
         return -0.5 * (n * LOG_2PI + h[0] + h[1]), h[4:7].copy()
 
-    def profile_loglik_grad(self, cov: Covariance, values=None, mean: str = "constant", X=None):
+    def profile_loglik_grad(self, cov: Covariance, values=None, mean: str = "constant", X=None, noise=None):
         """:meth:`profile_loglik` and its gradient in (sigma2, phi, tau2): ``(loglik, mu, grad)``.  By the
         envelope theorem the gradient of the profiled likelihood is the plain gradient at ``values - mu``:
         the two sweeps for mu plus one gradient sweep.  ``mean="linear"`` with ``X``: ``(loglik, beta, grad)``, the
-        gradient sweep at ``values - X beta``."""
+        gradient sweep at ``values - X beta``.  ``noise``: as :meth:`loglik_grad` (constant and zero means)."""
+        if noise is not None:
+            if mean == "linear" or X is not None:
+                _refuse_noise("mean='linear'")
+            cv, nzv = self._noise_setup(noise, cov)
+            nz = _NoiseVar(nzv)
+            v = self._values_dev(values)
+            if mean == "zero":
+                ll, g = self.loglik_grad(v, cv, noise=nz)
+                return ll, 0.0, g
+            ll, mu = self.profile_loglik(cv, v, mean=mean, noise=nz)
+            return ll, mu, self.loglik_grad(v - mu, cv, noise=nz)[1]
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
         if mean == "linear":
@@ -1105,8 +1224,8 @@ class NNGP:
         return ll, h[4:7].copy(), fisher.info_matrix(h[7:13]), I_rows, G
 
     def fisher_information(self, cov: Optional[Covariance] = None, values=None, mean: str = "zero", X=None,
-                           log: bool = False, rows: bool = False) -> dict:
-        """The Fisher information of the NNGP (Vecchia) likelihood in theta = (sigma2, phi, tau2) at ``cov``, from
+                           log: bool = False, rows: bool = False, noise=None) -> dict:
+        """(``noise``: refused -- the information sweep has no per-point noise form.)  The Fisher information of the NNGP (Vecchia) likelihood in theta = (sigma2, phi, tau2) at ``cov``, from
         one fused sweep (``nngp_bf_fisher``): the sum over locations of each one's expected information under the
         exact Gaussian law of its joint block (Guinness 2021), positive semi-definite by construction.
 
@@ -1120,6 +1239,8 @@ class NNGP:
         ``values=None`` is the design-stage call: the information does not depend on the data, ``grad`` is exactly
         0 and ``loglik`` is None (``mean`` must then be ``"zero"``).  Fused kinds other than ``matern`` and
         1 <= m <= 32 only."""
+        if noise is not None:
+            _refuse_noise("the Fisher information (fisher_information, fit(method='fisher'), stderr=True)")
         from . import fisher
 
         cv = self._grad_cov(cov, aniso=False)
@@ -1232,7 +1353,7 @@ class NNGP:
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
             gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None,
             anisotropic: bool = False, reneighbor: int = 0, estimate_nu: Optional[bool] = None,
-            nu_bounds=(0.05, 50.0)):
+            nu_bounds=(0.05, 50.0), noise=None):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -1281,7 +1402,21 @@ class NNGP:
         ``tol`` is L-BFGS-B's ``gtol`` and, when given, the only stopping rule beside ``maxiter`` (``ftol`` is set
         to 1e-15).  The result carries ``nu``, ``theta`` = (sigma2, phi, tau2, nu), ``grad`` (the
         gradient in the free log-parameters at the optimiser's last iterate) and ``message``.  No ``reml``,
-        ``anisotropic``, ``method="fisher"`` or ``stderr`` with it."""
+        ``anisotropic``, ``method="fisher"`` or ``stderr`` with it.
+
+        ``noise`` (``"eps"`` or sigmas e in model order): per-point noise variances tau2 e_i^2 (:meth:`loglik`).
+        ``fix_tau2=1.0`` takes the error bars as exact; a free tau2 rescales them.  Derivative-free or
+        ``gradient=True`` (``nngp_bf_grad_noise``; ``tol``, when given, is then L-BFGS-B's ``gtol`` and the only
+        stopping rule beside ``maxiter``); the result gains ``grad``, the gradient in the free log-parameters at the
+        estimate.  Constant and zero means; no ``stderr``, ``method="fisher"``, ``anisotropic``, ``reml``,
+        ``estimate_nu`` or the ``matern`` kind with it."""
+        if noise is not None:
+            for on, what in ((stderr, "stderr=True"), (method == "fisher", "method='fisher'"),
+                             (anisotropic, "anisotropic=True"), (estimate_nu is not None, "estimate_nu"),
+                             (kind == "matern", "the general-nu matern kind"), (mean == "linear", "mean='linear'"),
+                             (reml, "reml=True (a regression mean)")):
+                if on:
+                    _refuse_noise(f"fit with {what}")
         if estimate_nu is not None:
             for on, what in ((reml, "reml=True"), (anisotropic, "anisotropic=True"),
                              (method == "fisher", "method='fisher'"), (stderr, "stderr=True")):
@@ -1343,6 +1478,8 @@ class NNGP:
             nu = base.nu
         th0 = tuple(x0) if x0 is not None else (base.theta[:3] if base is not None else (1.0, 10.0, 0.1))
         free_tau = fix_tau2 is None
+        # noise=: resolved (and refused) once, before any sweep; every evaluation reuses the device weights
+        nz = None if noise is None else _NoiseVar(self._noise_setup(noise, Covariance(kind, *th0, nu=nu))[1])
         if method == "fisher":
             return self._fit_fisher(kind, th0, nu, mean, X, linear, free_tau, fix_tau2, maxiter, tol, algo)
         from scipy.optimize import minimize
@@ -1366,7 +1503,7 @@ class NNGP:
                     g = self.gls(Covariance(kind, *th, nu=nu), X, reml=reml, algo=algo)
                     ll, mu = g.objective, None
                 else:
-                    ll, mu = self.profile_loglik(Covariance(kind, *th, nu=nu), mean=mean, algo=algo)
+                    ll, mu = self.profile_loglik(Covariance(kind, *th, nu=nu), mean=mean, algo=algo, noise=nz)
             except NNGPNumericalError:
                 return 1e300
             if ll > best["ll"]:
@@ -1378,7 +1515,7 @@ class NNGP:
         def obj_grad(z):
             th = theta_of(z)
             try:
-                ll, mu, g = self.profile_loglik_grad(Covariance(kind, *th, nu=nu), mean=mean, X=X)
+                ll, mu, g = self.profile_loglik_grad(Covariance(kind, *th, nu=nu), mean=mean, X=X, noise=nz)
                 mu = None if linear else mu
             except NNGPNumericalError:
                 # no gradient exists here: the zero one can end a line search early, so the failure is kept
@@ -1387,18 +1524,23 @@ class NNGP:
                 return 1e300, np.zeros(len(z))
             last_failed[0] = False
             n_grad[0] += 1
+            glog = np.array([th[k] * g[k] for k in range(len(z))])
             if ll > best["ll"]:
-                best.update(ll=ll, mu=mu, theta=th)
-            return -ll, -np.array([th[k] * g[k] for k in range(len(z))])
+                best.update(ll=ll, mu=mu, theta=th, grad=glog)
+            return -ll, -glog
 
         if gradient:
             self._grad_cov(Covariance(kind, *th0, nu=nu))  # refuse unsupported kinds / m before optimising
-            res = minimize(obj_grad, np.array(z0), jac=True, method=method, options={"maxiter": maxiter})
+            opts = {"maxiter": maxiter}
+            if nz is not None and tol is not None:
+                opts.update(gtol=float(tol), ftol=1e-15)
+            res = minimize(obj_grad, np.array(z0), jac=True, method=method, options=opts)
             self.cov = Covariance(kind, *best["theta"], nu=nu)
             self._B = self._F = None
             return with_stderr({"theta": best["theta"], "mu": best["mu"], "loglik": best["ll"],
                                 "n_evals": int(res.nfev), "n_grad_evals": n_grad[0],
                                 "converged": bool(res.success) and not last_failed[0],
+                                **({} if nz is None else {"grad": best["grad"]}),
                                 **self._fit_beta(X if linear else None, algo)})
         res = minimize(obj, np.array(z0), method=method, options={"maxiter": maxiter, "xatol": 1e-6,
                                                                   "fatol": 1e-9} if method == "Nelder-Mead"

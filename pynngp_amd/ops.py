@@ -21,6 +21,12 @@ for tracing.
     torch.ops.nngp.nbr_cert(coords, nbr, order, i0) -> (cert, cert_info)   # neighbour-set certificate (setup)
     torch.ops.nngp.pair_plan(nbr, order, i0, n_points, dim) -> (plan, plan_info)   # wave pair plan (setup)
     torch.ops.nngp.bf_cross(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0) -> (B, F, mean)
+    torch.ops.nngp.bf_sweep_noise(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, noise_var, want_bf)
+        -> (B, F, R, partials)   # per-point noise tau2 * noise_var[j]; B, F empty without want_bf, R without values
+    torch.ops.nngp.bf_grad_noise(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, noise_var, want_rows)
+        -> (partials, grad, G)                                         # bf_grad of that model
+    torch.ops.nngp.bf_cross_noise(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, noise_ref, noise_query)
+        -> (B, F, mean)                                                # bf_cross of that model; noise_query None: 1
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -147,6 +153,22 @@ def _register_fakes() -> None:
 
     @fake("bf_cross")
     def _(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, algo, nu=-1.0):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_noise")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, noise_var, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_grad_noise")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, noise_var, want_rows):
+        return (coords.new_empty((4,)), coords.new_empty((3,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, 3)))
+
+    @fake("bf_cross_noise")
+    def _(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, noise_ref, noise_query):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 
