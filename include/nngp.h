@@ -234,6 +234,37 @@ int nngp_bf_grad_noise(const double *coords, int64_t n_points, int32_t dim, cons
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Separable space-time covariance (added within revision 4; nothing earlier moved):
+ *   C(a, b) = sigma2 rho_s(phi_s |a_s - b_s|) rho_t(phi_t |a_t - b_t|) + tau2 delta_ab.
+ * The points are (n, dim) with dim = 2 or 3: the last column is time, the first dim - 1 columns are space.
+ * kind_s and kind_t are the kinds of the two correlations, NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL each.
+ *   nngp_bf_sweep_sep: the contract of nngp_bf_sweep_noise (B, F, R, partials[4] required, order, i0, -1 padding,
+ *     the two flags, NaN rows on a bad pivot, a fixed-order fold).
+ *   nngp_bf_cross_sep: the contract of nngp_bf_cross_noise (reference points, query points).
+ *   nngp_bf_grad_sep: the contract of nngp_bf_grad with G (n_rows, 4) and grad[4] in (sigma2, phi_s, phi_t, tau2):
+ *     dC_ab/dphi_s = sigma2 (u_s rho_s'(u_s)) rho_t(u_t) / phi_s, dC_ab/dphi_t likewise; each is exactly 0 where
+ *     that factor's distance is 0.
+ * Scope: 1 <= m <= 32, dim 2 or 3, no general-nu factor, else NNGP_EUNSUP.  NNGP_EINVAL for sigma2 <= 0, tau2 < 0
+ * or a non-positive or non-finite phi.
+ * workspace: nngp_bf_sweep_sep_workspace_bytes(n_rows, m) serves all three (0 for unsupported arguments);
+ * 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_sep_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_sweep_sep(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                      int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s, int32_t kind_t, double sigma2,
+                      double phi_s, double phi_t, double tau2, const double *values, double *B, double *F, double *R,
+                      double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_sep(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                      const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind_s,
+                      int32_t kind_t, double sigma2, double phi_s, double phi_t, double tau2, const double *ref_values,
+                      const double *query_values, double *B, double *F, double *R, double *partials, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int nngp_bf_grad_sep(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s, int32_t kind_t, double sigma2,
+                     double phi_s, double phi_t, double tau2, const double *values, double *G, double *partials,
+                     double *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,
  * order and i0 as nngp_bf_sweep).  With D_ab = sigma2 d_ab rho'(phi d_ab) and u = [-B_i; 1]:
  *   B  (n_rows, m), F (n_rows,): the factors of nngp_bf_sweep at this theta, equal to that sweep's to its own

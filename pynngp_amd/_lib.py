@@ -74,6 +74,10 @@ SYMBOLS = (
     "nngp_bf_sweep_noise",
     "nngp_bf_cross_noise",
     "nngp_bf_grad_noise",
+    "nngp_bf_sweep_sep_workspace_bytes",
+    "nngp_bf_sweep_sep",
+    "nngp_bf_cross_sep",
+    "nngp_bf_grad_sep",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
     "nngp_bf_grad_matern_workspace_bytes",
@@ -187,6 +191,15 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_cross_noise.restype = ctypes.c_int
     lib.nngp_bf_grad_noise.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, P, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_noise.restype = ctypes.c_int
+    lib.nngp_bf_sweep_sep_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_sweep_sep_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_sep.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, I32, D, D, D, D, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_sep.restype = ctypes.c_int
+    lib.nngp_bf_cross_sep.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, I32, D, D, D, D, P, P, P, P, P, P, P,
+                                      SZ, P]
+    lib.nngp_bf_cross_sep.restype = ctypes.c_int
+    lib.nngp_bf_grad_sep.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, I32, D, D, D, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_sep.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
     lib.nngp_bf_grad_aniso_workspace_bytes.restype = SZ
     lib.nngp_bf_grad_aniso.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
@@ -1181,6 +1194,135 @@ def bf_cross_noise(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, ki
                                    _ptr(ref_values), _ptr(query_values), _ptr(noise_ref), _ptr(noise_query), _ptr(B),
                                    _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_cross_noise")
+    return B, F, R, partials
+
+
+def _sep_checks(kind_s: str, kind_t: str, m: int, dim: int) -> None:
+    """The scope of the separable space-time sweeps (nngp_bf_*_sep): factors exponential .. spherical, dim 2 or 3,
+    1 <= m <= 32."""
+    for k in (kind_s, kind_t):
+        if k not in KIND_CODES:
+            raise ValueError(f"unknown covariance kind {k!r}")
+        if k == "matern":
+            raise NotImplementedError("the separable sweeps serve factors of kind exponential .. spherical, not the "
+                                      "general-nu matern kind")
+    if dim not in (2, 3):
+        raise NotImplementedError(f"the separable sweeps serve dim 2 or 3 (space, then time in the last column), "
+                                  f"dim={dim}")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the separable sweeps serve 1 <= m <= {GRAD_MAX_M} (m={m})")
+
+
+def bf_sweep_sep(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind_s: str, kind_t: str, sigma2: float,
+                 phi_s: float, phi_t: float, tau2: float, values: Optional[torch.Tensor] = None, want_bf: bool = True,
+                 order: Optional[torch.Tensor] = None, want_r: bool = False,
+                 workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep` under the separable space-time covariance (``nngp_bf_sweep_sep``, include/nngp.h):
+    ``sigma2 rho_s(phi_s |a_s - b_s|) rho_t(phi_t |a_t - b_t|) + tau2 delta_ab`` with the time in the last column of
+    ``coords`` (dim 2 or 3).  Returns ``(B, F, R, partials)`` (B, F None without ``want_bf``; R None without
+    ``want_r``, which needs ``values``).  Factors exponential .. spherical, 1 <= m <= 32; ``order`` as in
+    :func:`bf_sweep`."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n = coords.shape[0]
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (n,):
+            raise ValueError("values must be float64 (N,)")
+        values = values.contiguous()
+    rows, m = nbr.shape
+    _sep_checks(kind_s, kind_t, m, coords.shape[1])
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and values is None:
+        raise ValueError("want_r needs values")
+    lib = load()
+    need = lib.nngp_bf_sweep_sep_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev) if want_bf else None
+    F = torch.empty((rows,), dtype=torch.float64, device=dev) if want_bf else None
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_sep(_ptr(coords), n, coords.shape[1], _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                 KIND_CODES[kind_s], KIND_CODES[kind_t], float(sigma2), float(phi_s), float(phi_t),
+                                 float(tau2), _ptr(values), _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace),
+                                 workspace.numel(), _stream(dev)), "nngp_bf_sweep_sep")
+    return B, F, R, partials
+
+
+def bf_grad_sep(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind_s: str, kind_t: str, sigma2: float,
+                phi_s: float, phi_t: float, tau2: float, values: torch.Tensor, want_rows: bool = False,
+                order: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`bf_grad` under the separable space-time covariance (``nngp_bf_grad_sep``): ``(partials, grad, G)`` with
+    grad (4,) and G (rows, 4) in (sigma2, phi_s, phi_t, tau2)."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n = coords.shape[0]
+    if values is None or values.dtype != torch.float64 or values.shape != (n,):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    rows, m = nbr.shape
+    _sep_checks(kind_s, kind_t, m, coords.shape[1])
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_sweep_sep_workspace_bytes(rows, m)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(4, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, 4), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_sep(_ptr(coords), n, coords.shape[1], _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                KIND_CODES[kind_s], KIND_CODES[kind_t], float(sigma2), float(phi_s), float(phi_t),
+                                float(tau2), _ptr(values), _ptr(G), _ptr(partials), _ptr(grad), _ptr(workspace),
+                                workspace.numel(), _stream(dev)), "nngp_bf_grad_sep")
+    return partials, grad, G
+
+
+def bf_cross_sep(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind_s: str, kind_t: str, sigma2: float,
+                 phi_s: float, phi_t: float, tau2: float, ref_values: Optional[torch.Tensor] = None,
+                 query_values: Optional[torch.Tensor] = None, q0: int = 0, order: Optional[torch.Tensor] = None,
+                 want_r: bool = False):
+    """:func:`bf_cross` under the separable space-time covariance (``nngp_bf_cross_sep``).  Returns
+    ``(B, F, R, partials)`` (R None without ``want_r``, which needs ``ref_values``)."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if ref_values is not None:
+        if ref_values.dtype != torch.float64 or ref_values.shape != (ref.shape[0],):
+            raise ValueError("ref_values must be float64 (n_ref,)")
+        ref_values = ref_values.contiguous()
+    if query_values is not None:
+        if query_values.dtype != torch.float64 or query_values.shape != (query.shape[0],):
+            raise ValueError("query_values must be float64 (n_query,)")
+        query_values = query_values.contiguous()
+    rows, m = nbr.shape
+    _sep_checks(kind_s, kind_t, m, d)
+    dev = _require_gpu(ref, query, nbr, ref_values, query_values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and ref_values is None:
+        raise ValueError("want_r needs ref_values")
+    lib = load()
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev)
+    F = torch.empty((rows,), dtype=torch.float64, device=dev)
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_sep_workspace_bytes(rows, m), dev)
+    _check(lib.nngp_bf_cross_sep(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order), rows, m,
+                                 int(q0), KIND_CODES[kind_s], KIND_CODES[kind_t], float(sigma2), float(phi_s),
+                                 float(phi_t), float(tau2), _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F),
+                                 _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_cross_sep")
     return B, F, R, partials
 
 

@@ -155,6 +155,72 @@ class _LogLikNoise(torch.autograd.Function):
         return None, None, gtheta, gvalues, None, None, None
 
 
+class _LogLikSep(torch.autograd.Function):
+    """theta = (sigma2, phi_s, phi_t, tau2): the separable space-time sweep (``torch.ops.nngp.bf_grad_sep``)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, kind_s, kind_t, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_sep(coords, nbr, order, 0, _lib.KIND_CODES[kind_s], _lib.KIND_CODES[kind_t],
+                                             th[0], th[1], th[2], th[3], values.detach(), False)
+        ctx.save_for_backward(coords, nbr, values, g)
+        ctx.meta = (kind_s, kind_t, order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g = ctx.saved_tensors
+        kind_s, kind_t, order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLik: one ordinary sweep (B, F, R) of the same model
+            B, F, R, _ = _lib.bf_sweep_sep(coords, nbr, 0, kind_s, kind_t, th[0], th[1], th[2], th[3],
+                                           values=values.detach(), order=order, want_r=True)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None, None, None
+
+
+def loglik_sep(coords, nbr, kind_s, kind_t, theta4, values, order=None):
+    """NNGP log-likelihood of ``values`` on S = T under the separable space-time covariance
+    ``sigma2 rho_s(phi_s d_s) rho_t(phi_t d_t) + tau2 delta`` (time in the last column of ``coords``, dim 2 or 3) at
+    ``theta4`` = (sigma2, phi_s, phi_t, tau2), a float64 (4,) tensor, differentiable in ``theta4`` and, when
+    ``values.requires_grad``, in ``values``.
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_sep``) and synchronises with the host as
+    :func:`loglik` does; backward returns ``grad_out * grad`` for theta with no further launch.  ``nbr`` (N, m) int32
+    with 1 <= m <= 32; factors exponential .. spherical; the not-PD and bad-index flags raise.
+    """
+    for k in (kind_s, kind_t):
+        if k not in _lib.KIND_CODES:
+            raise ValueError(f"unknown covariance kind {k!r}")
+        if k not in _KINDS:
+            raise NotImplementedError(f"loglik_sep serves the factor kinds {_KINDS}")
+    if theta4.dtype != torch.float64 or theta4.shape != (4,):
+        raise ValueError("theta4 must be a float64 (4,) tensor (sigma2, phi_s, phi_t, tau2)")
+    if coords.dim() != 2 or coords.shape[1] not in (2, 3):
+        raise NotImplementedError("loglik_sep serves 2 or 3 coordinate columns (space, then time)")
+    if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
+        raise NotImplementedError(f"loglik_sep's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
+    if nbr.shape[0] != coords.shape[0]:
+        raise ValueError("loglik_sep is an S = T sweep: one nbr row per location")
+    ll, p = _LogLikSep.apply(coords, nbr, theta4, values, kind_s, kind_t, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 def loglik_matern(coords, nbr, theta, values, order=None):
     """NNGP log-likelihood of ``values`` on S = T under the general-smoothness Matern covariance at ``theta`` =
     (sigma2, phi, tau2, nu), a float64 (4,) tensor, differentiable in all four entries of ``theta`` and, when

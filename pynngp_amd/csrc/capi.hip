@@ -13,6 +13,7 @@
 #include "nbr_cert.h"
 #include "bf_grad.h"
 #include "bf_noise.h"
+#include "bf_sep.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -303,6 +304,93 @@ int nngp_bf_grad_noise(const double* coords, int64_t n_points, int32_t dim, cons
                       values, noise_var, nullptr, nullptr, nullptr, G, (double*)workspace};
     hipError_t e = nngp::bf_noise_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_noise launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_sweep_sep_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    // at least one record; the gradient's records (kSepRec doubles per block) cover the forward sweep's four
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * nngp::kSepRec * sizeof(double));
+}
+
+// the checks the three separable entry points share (scope, theta, workspace)
+static int sep_common(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, int64_t n_rows, int32_t m,
+                      int64_t i0, int64_t n_locs, int32_t kind_s, int32_t kind_t, double sigma2, double phi_s,
+                      double phi_t, double tau2, double* partials, void* workspace, size_t workspace_bytes) {
+    if (dim < 2 || dim > 3)
+        return fail(NNGP_EUNSUP, "the separable sweeps serve dim 2 or 3 (space, then time in the last column), dim=%d", dim);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the separable sweeps serve 1 <= m <= 32 (m=%d)", m);
+    if (kind_s == NNGP_COV_MATERN || kind_t == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the separable sweeps serve factors of kind exponential .. spherical, not the "
+                                 "general-nu matern");
+    if (kind_s < NNGP_COV_EXPONENTIAL || kind_s > NNGP_COV_MATERN || kind_t < NNGP_COV_EXPONENTIAL ||
+        kind_t > NNGP_COV_MATERN)
+        return fail(NNGP_EINVAL, "unknown kinds %d, %d", kind_s, kind_t);
+    if (!(sigma2 > 0.0) || !(phi_s > 0.0) || !(phi_t > 0.0) || !(tau2 >= 0.0) || !isfinite(sigma2) || !isfinite(phi_s) ||
+        !isfinite(phi_t) || !isfinite(tau2))
+        return fail(NNGP_EINVAL, "theta must satisfy sigma2 > 0, phi_s > 0, phi_t > 0, tau2 >= 0 (finite)");
+    if (coords == nullptr || workspace == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (partials == nullptr) return fail(NNGP_EINVAL, "partials must be non-null");
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_locs)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_locs);
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_sweep_sep_workspace_bytes(n_rows, m);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return NNGP_OK;
+}
+
+static int sep_forward(const double* coords, int64_t n_points, int32_t dim, const double* qcoords, int64_t n_locs,
+                       const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s,
+                       int32_t kind_t, double sigma2, double phi_s, double phi_t, double tau2, const double* values,
+                       const double* qvalues, double* B, double* F, double* R, double* partials, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    const int rc = sep_common(coords, n_points, dim, nbr, n_rows, m, i0, n_locs, kind_s, kind_t, sigma2, phi_s, phi_t,
+                              tau2, partials, workspace, workspace_bytes);
+    if (rc != NNGP_OK) return rc;
+    if (qcoords == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (B != nullptr && F == nullptr) return fail(NNGP_EINVAL, "B given without F");
+    if (F != nullptr && B == nullptr && n_rows > 0) return fail(NNGP_EINVAL, "F given without B");
+    if (R != nullptr && values == nullptr) return fail(NNGP_EINVAL, "R (residuals) needs values");
+    nngp::SepArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind_s, kind_t, dim, sigma2, phi_s, phi_t, tau2, values,
+                    qcoords, qvalues, B, F, R, nullptr, (double*)workspace};
+    hipError_t e = nngp::bf_sep_launch(a, partials, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_sep launch");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_sep(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                      int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s, int32_t kind_t, double sigma2,
+                      double phi_s, double phi_t, double tau2, const double* values, double* B, double* F, double* R,
+                      double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    return sep_forward(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind_s, kind_t, sigma2, phi_s,
+                       phi_t, tau2, values, values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_cross_sep(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,
+                      const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind_s,
+                      int32_t kind_t, double sigma2, double phi_s, double phi_t, double tau2, const double* ref_values,
+                      const double* query_values, double* B, double* F, double* R, double* partials, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (query_values != nullptr && ref_values == nullptr) return fail(NNGP_EINVAL, "query_values need ref_values");
+    return sep_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, m, q0, kind_s, kind_t, sigma2, phi_s, phi_t,
+                       tau2, ref_values, query_values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_grad_sep(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s, int32_t kind_t, double sigma2,
+                     double phi_s, double phi_t, double tau2, const double* values, double* G, double* partials,
+                     double* grad, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = sep_common(coords, n_points, dim, nbr, n_rows, m, i0, n_points, kind_s, kind_t, sigma2, phi_s, phi_t,
+                              tau2, partials, workspace, workspace_bytes);
+    if (rc != NNGP_OK) return rc;
+    if (values == nullptr || grad == nullptr) return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    nngp::SepArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind_s, kind_t, dim, sigma2, phi_s, phi_t, tau2, values,
+                    coords, values, nullptr, nullptr, nullptr, G, (double*)workspace};
+    hipError_t e = nngp::bf_sep_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_sep launch");
     return NNGP_OK;
 }
 

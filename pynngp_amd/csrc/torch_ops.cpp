@@ -470,6 +470,84 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_noise(const at::Tensor& 
     return {B, F, mean};
 }
 
+// ---------------------------------------------------------------- separable space-time (nngp_bf_*_sep)
+// (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_sep(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind_s,
+    int64_t kind_t, double sigma2, double phi_s, double phi_t, double tau2, const c10::optional<at::Tensor>& values,
+    bool want_bf) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool wr = values.has_value();
+    at::Tensor B = at::empty({want_bf ? rows : 0, m}, f64), F = at::empty({want_bf ? rows : 0}, f64);
+    at::Tensor R = at::empty({wr ? rows : 0}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_sep_workspace_bytes(rows, (int32_t)m), coords);
+    check_rc(nngp_bf_sweep_sep(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                               ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind_s, (int32_t)kind_t, sigma2, phi_s,
+                               phi_t, tau2, ptr<double>(values), want_bf ? B.data_ptr<double>() : nullptr,
+                               want_bf ? F.data_ptr<double>() : nullptr, wr ? R.data_ptr<double>() : nullptr,
+                               p.data_ptr<double>(), ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_sep");
+    return {B, F, R, p};
+}
+
+// (partials (4,), grad (4,) in (sigma2, phi_s, phi_t, tau2), G (rows, 4) or (0, 4))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_sep(const at::Tensor& coords, const at::Tensor& nbr,
+                                                           const c10::optional<at::Tensor>& order, int64_t i0,
+                                                           int64_t kind_s, int64_t kind_t, double sigma2, double phi_s,
+                                                           double phi_t, double tau2, const at::Tensor& values,
+                                                           bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({4}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, 4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_sep_workspace_bytes(rows, (int32_t)m), coords);
+    check_rc(nngp_bf_grad_sep(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                              ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind_s, (int32_t)kind_t, sigma2, phi_s,
+                              phi_t, tau2, values.data_ptr<double>(), want_rows ? G.data_ptr<double>() : nullptr,
+                              p.data_ptr<double>(), g.data_ptr<double>(), ws.data_ptr(), (size_t)ws.nbytes(),
+                              stream(coords)),
+             "nngp_bf_grad_sep");
+    return {p, g, G};
+}
+
+// (B, F, kriging mean), as bf_cross
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_sep(const at::Tensor& ref, const at::Tensor& query,
+                                                            const at::Tensor& nbr, int64_t kind_s, int64_t kind_t,
+                                                            double sigma2, double phi_s, double phi_t, double tau2,
+                                                            const c10::optional<at::Tensor>& ref_values) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    check_f64(ref_values, {ref.size(0)}, ref, "ref_values");
+    auto f64 = ref.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64), R = at::empty({rows}, f64);
+    at::Tensor p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_sep_workspace_bytes(rows, (int32_t)m), ref);
+    check_rc(nngp_bf_cross_sep(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(), query.size(0),
+                               nbr.data_ptr<int32_t>(), nullptr, rows, (int32_t)m, 0, (int32_t)kind_s, (int32_t)kind_t,
+                               sigma2, phi_s, phi_t, tau2, ptr<double>(ref_values), nullptr, B.data_ptr<double>(),
+                               F.data_ptr<double>(), ref_values.has_value() ? R.data_ptr<double>() : nullptr,
+                               p.data_ptr<double>(), ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_sep");
+    at::Tensor mean = ref_values.has_value() ? R.neg() : at::zeros({rows}, f64);
+    return {B, F, mean};
+}
+
 // the wave pair plan of a sweep over nbr (include/nngp.h nngp_pair_plan_build): (plan bytes on the GPU,
 // CPU int64 info).  A setup call: it synchronises the tensors' stream once.
 std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0,
@@ -948,6 +1026,12 @@ TORCH_LIBRARY(nngp, m) {
           "float tau2, Tensor values, Tensor noise_var, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_cross_noise(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float phi, float tau2, "
           "Tensor? ref_values, Tensor noise_ref, Tensor? noise_query) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_sep(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind_s, int kind_t, float sigma2, "
+          "float phi_s, float phi_t, float tau2, Tensor? values, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_grad_sep(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind_s, int kind_t, float sigma2, "
+          "float phi_s, float phi_t, float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_cross_sep(Tensor ref, Tensor query, Tensor nbr, int kind_s, int kind_t, float sigma2, float phi_s, "
+          "float phi_t, float tau2, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
     m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
@@ -967,6 +1051,9 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_noise", &bf_sweep_noise);
     m.impl("bf_grad_noise", &bf_grad_noise);
     m.impl("bf_cross_noise", &bf_cross_noise);
+    m.impl("bf_sweep_sep", &bf_sweep_sep);
+    m.impl("bf_grad_sep", &bf_grad_sep);
+    m.impl("bf_cross_sep", &bf_cross_sep);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

@@ -28,6 +28,9 @@ DEFAULT_FUSE_WIDTH = 64
 
 def _check_cov(cov) -> Covariance:
     if not isinstance(cov, Covariance):
+        from .nngp import _refuse_sep
+
+        _refuse_sep(cov, "NNGPFactor")
         if isinstance(cov, AnisotropicCovariance):
             raise TypeError("NNGPFactor does not serve an AnisotropicCovariance (per-axis ranges); it takes a "
                             "pynngp_amd.Covariance")

@@ -102,6 +102,9 @@ def lanczos_quadrature(alpha, beta, f=np.log) -> float:
 
 def _check_cov(cov) -> Covariance:
     if not isinstance(cov, Covariance):
+        from .nngp import _refuse_sep
+
+        _refuse_sep(cov, "LatentPosterior")
         if isinstance(cov, AnisotropicCovariance):
             raise TypeError("LatentPosterior does not serve an AnisotropicCovariance (per-axis ranges); it takes a "
                             "pynngp_amd.Covariance")

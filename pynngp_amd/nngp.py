@@ -193,7 +193,76 @@ class AnisotropicCovariance:
         return self.scaled()[0](a.reshape(-1, d) * s, b.reshape(-1, d) * s)
 
 
+_SEP_KINDS = _ANISO_KINDS
+
+
+@dataclasses.dataclass(frozen=True)
+class SeparableCovariance:
+    """The separable space-time product ``sigma2 rho_s(phi_s |a_s - b_s|) rho_t(phi_t |a_t - b_t|) + tau2 delta_ab``:
+    the last coordinate column is time, the first dim - 1 columns (dim 2 or 3) are space.  ``kind_s`` and ``kind_t``
+    name the two correlations, ``exponential`` .. ``spherical`` each.  The sweeps evaluate it fused
+    (``nngp_bf_sweep_sep``, ``nngp_bf_cross_sep``, ``nngp_bf_grad_sep``); the gradient is in
+    (sigma2, phi_s, phi_t, tau2).  An :class:`AnisotropicCovariance` is the *metric* model
+    rho(sqrt(phi_s^2 d_s^2 + phi_t^2 d_t^2)) instead; the two agree only for gaussian x gaussian.  Called as
+    ``cov(a, b)`` on coordinate rows it returns the cross-covariance matrix without the nugget.
+
+    Neighbour sets come from the ordinary search on the coordinates scaled column by column by :meth:`scaled`
+    (phi_s, .., phi_s, phi_t).  For a product correlation that is a heuristic: the scaled Euclidean distance does not
+    order pairs by their correlation (it does for gaussian x gaussian only)."""
+
+    kind_s: str
+    kind_t: str
+    sigma2: float
+    phi_s: float
+    phi_t: float
+    tau2: float = 0.0
+
+    def __post_init__(self):
+        for k in (self.kind_s, self.kind_t):
+            if k not in _SEP_KINDS:
+                raise ValueError(f"SeparableCovariance serves the kinds {_SEP_KINDS} for each factor, got {k!r}")
+        th = (self.sigma2, self.phi_s, self.phi_t, self.tau2)
+        if not all(isinstance(x, (int, float, np.floating, np.integer)) and math.isfinite(x) for x in th):
+            raise ValueError(f"sigma2, phi_s, phi_t, tau2 must be finite numbers, got {th}")
+        if not (self.sigma2 > 0 and self.phi_s > 0 and self.phi_t > 0 and self.tau2 >= 0):
+            raise ValueError("need sigma2 > 0, phi_s > 0, phi_t > 0, tau2 >= 0")
+
+    nu = None
+    nu_arg = None
+
+    @property
+    def theta(self):
+        return (float(self.sigma2), float(self.phi_s), float(self.phi_t), float(self.tau2))
+
+    def replace(self, **kw) -> "SeparableCovariance":
+        return dataclasses.replace(self, **kw)
+
+    def scaled(self, dim: int = 3):
+        """The per-column scales (phi_s, .., phi_s, phi_t) for ``dim`` coordinate columns: the metric of the
+        neighbour search (a heuristic for a product correlation, see the class)."""
+        if dim not in (2, 3):
+            raise ValueError(f"SeparableCovariance serves 2 or 3 coordinate columns (space, then time), got {dim}")
+        return np.array([self.phi_s] * (dim - 1) + [self.phi_t], dtype=np.float64)
+
+    def __call__(self, a, b):
+        d = a.shape[-1] if a.ndim > 1 else b.shape[-1]
+        if d not in (2, 3) or (a.ndim > 1 and a.shape[-1] != d) or (b.ndim > 1 and b.shape[-1] != d):
+            raise ValueError("coordinate rows must have 2 or 3 columns (space, then time)")
+        a, b = a.reshape(-1, d), b.reshape(-1, d)
+        cs = Covariance(self.kind_s, 1.0, self.phi_s, 0.0)(a[:, :d - 1], b[:, :d - 1])
+        ct = Covariance(self.kind_t, 1.0, self.phi_t, 0.0)(a[:, d - 1:], b[:, d - 1:])
+        return self.sigma2 * cs * ct
+
+
+def _refuse_sep(cov, what: str) -> None:
+    if isinstance(cov, SeparableCovariance):
+        raise TypeError(f"{what} does not serve a SeparableCovariance (space x time product): use loglik / "
+                        "compute_BF / predict(query=) / profile_loglik / profile_loglik_grad / gls / loglik_grad / fit "
+                        "on refType='S=T'")
+
+
 def _refuse_aniso(cov, what: str) -> None:
+    _refuse_sep(cov, what)
     if isinstance(cov, AnisotropicCovariance):
         raise TypeError(f"{what} does not serve an AnisotropicCovariance (per-axis ranges): it would need the "
                         "range of every axis; use loglik / profile_loglik / loglik_grad / fit(anisotropic=True), or "
@@ -489,7 +558,19 @@ def _sweep_any(cv, coords, nbr, i0=0, values=None, want_bf=True, algo="auto", or
     :class:`CallableCovariance` (fn(a, b) on the joint blocks' rows -> nngp_bf_sweep_blocks;
     ``blocks``: already evaluated blocks of these rows, e.g. cached).  ``qcoords``
     given: the cross sweep of those query points against ``coords`` (prediction); ``qvalues``: the
-    values at the locations (S = T sweep: pass ``values``)."""
+    values at the locations (S = T sweep: pass ``values``).  A :class:`SeparableCovariance` runs on its own fused
+    sweeps (nngp_bf_sweep_sep / nngp_bf_cross_sep; ``algo`` is not used)."""
+    if isinstance(cv, SeparableCovariance):
+        want_r = R is not None
+        if qcoords is not None:
+            B, F, Rn, p = _lib.bf_cross_sep(coords, qcoords, nbr, cv.kind_s, cv.kind_t, *cv.theta, ref_values=values,
+                                            query_values=qvalues, q0=i0, order=order, want_r=want_r)
+        else:
+            B, F, Rn, p = _lib.bf_sweep_sep(coords, nbr, i0, cv.kind_s, cv.kind_t, *cv.theta, values=values,
+                                            want_bf=want_bf, order=order, want_r=want_r)
+        if want_r:
+            R.copy_(Rn)
+        return B, F, p
     if isinstance(cv, (IsotropicCovariance, CallableCovariance)):
         m = nbr.shape[1]
         if not 1 <= m <= _lib.BLOCKS_MAX_M:
@@ -575,7 +656,7 @@ class NNGP:
 
         self._init_s()
         # the metric of the neighbour search: the per-axis decays of an AnisotropicCovariance, else the plain one
-        self._nbr_phi = self._aniso_phi(cov) if isinstance(cov, AnisotropicCovariance) else None
+        self._nbr_phi = self._metric_phi(cov)
         self._init_wt()
         self._init_ws()
         self._make_s_neighbor_sets()
@@ -691,6 +772,26 @@ class NNGP:
                              "coordinates (len(phi) must equal the coordinate dimension)")
         return cov.phi
 
+    def _sep_model(self, cov: "SeparableCovariance") -> "SeparableCovariance":
+        """``cov`` checked against this instance: S = T, 2 or 3 coordinate columns, 1 <= m <= 32."""
+        if not self._same_sets():
+            _refuse_sep(cov, f"refType={self.refType!r}")
+        d = self._s_dev.shape[1]
+        if d not in (2, 3):
+            raise ValueError(f"a SeparableCovariance needs 2 or 3 coordinate columns (space, then time), got {d}")
+        if not 1 <= self.m <= _lib.GRAD_MAX_M:
+            raise NotImplementedError(f"the separable sweeps serve 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
+        return cov
+
+    def _metric_phi(self, cov):
+        """The per-column scales of the neighbour search: an :class:`AnisotropicCovariance`'s decays, a
+        :class:`SeparableCovariance`'s (phi_s, .., phi_s, phi_t), else None (the coordinates themselves)."""
+        if isinstance(cov, AnisotropicCovariance):
+            return self._aniso_phi(cov)
+        if isinstance(cov, SeparableCovariance):
+            return tuple(self._sep_model(cov).scaled(self._s_dev.shape[1]).tolist())
+        return None
+
     def _phi_dev(self, phi) -> torch.Tensor:
         return torch.tensor(phi, dtype=torch.float64, device=self.device)
 
@@ -713,6 +814,8 @@ class NNGP:
         c = self.cov if cov is None else cov
         if isinstance(c, AnisotropicCovariance):
             return c.scaled()[0], self._scaled_s(self._aniso_phi(c))
+        if isinstance(c, SeparableCovariance):  # its own fused sweeps, on the raw coordinates (_sweep_any)
+            return self._sep_model(c), self._s_dev
         return self._covariance(c), self._s_dev
 
     def _query_scale(self, cov, q: torch.Tensor) -> torch.Tensor:
@@ -721,10 +824,12 @@ class NNGP:
 
     def rebuild_neighbors(self, cov=None):
         """Rebuild the neighbour sets in the metric of ``cov`` (default ``self.cov``): the existing search on the
-        coordinates scaled by an :class:`AnisotropicCovariance`'s decays, on the coordinates themselves for any other
-        covariance.  Clears the kept factors and covariance blocks."""
+        coordinates scaled by an :class:`AnisotropicCovariance`'s decays or a :class:`SeparableCovariance`'s
+        (phi_s, .., phi_s, phi_t) -- for a product correlation a heuristic: the scaled Euclidean distance does not order
+        pairs by their correlation --, on the coordinates themselves for any other covariance.  Clears the kept
+        factors and covariance blocks."""
         c = self.cov if cov is None else cov
-        self._nbr_phi = self._aniso_phi(c) if isinstance(c, AnisotropicCovariance) else None
+        self._nbr_phi = self._metric_phi(c)
         self._make_s_neighbor_sets()
         self._make_t_neighbor_sets()
         self._B = self._F = None
@@ -809,6 +914,7 @@ class NNGP:
         if not self._same_sets():
             _refuse_noise(f"refType={self.refType!r}")
         c = self.cov if cov is None else cov
+        _refuse_sep(c, "per-point noise (noise=)")
         if isinstance(c, AnisotropicCovariance):
             _refuse_noise("an AnisotropicCovariance")
         if not isinstance(c, Covariance):
@@ -851,6 +957,7 @@ class NNGP:
         if X is not None:
             from . import regression
 
+            _refuse_sep(self.cov if cov is None else cov, "universal kriging (predict with X, X_query)")
             mean, var, _ = regression.universal_kriging(self, cov, X, X_query, values=values, query=query, algo=algo)
             return mean, var
         cv, sc = self._sweep_cov(cov)
@@ -867,6 +974,10 @@ class NNGP:
             k = min(self.m, self._s_dev.shape[0])
             nbr = None
         q = self._query_scale(cov, q)  # an AnisotropicCovariance: the query points in the scaled coordinates too
+        if nbr is None and isinstance(cv, SeparableCovariance):
+            # the search in the (phi_s, .., phi_s, phi_t) metric, the cross sweep on the coordinates themselves
+            ph = self._metric_phi(cv)
+            nbr = _lib.knn_query(self._scaled_s(ph), q * self._phi_dev(ph), k)
         if nbr is None:
             nbr = _lib.knn_query(sc, q, k)
         n = q.shape[0]
@@ -882,7 +993,7 @@ class NNGP:
             return (-R).cpu().numpy(), F.cpu().numpy()
         R = torch.empty(n, dtype=torch.float64, device=self.device)
         _, F, p = _sweep_any(cv, sc, nbr, 0, values=v, algo=algo, R=R, qcoords=q)
-        _raise_on_bad(p.cpu().numpy())
+        _raise_on_bad(p.cpu().numpy(), cv)
         return (-R).cpu().numpy(), F.cpu().numpy()
 
     # -- covariance plumbing ---------------------------------------------------
@@ -963,7 +1074,7 @@ class NNGP:
     def _row_bf(self, i):
         cv, sc = self._sweep_cov()
         B, F, p = _sweep_any(cv, sc, self.nbr[i: i + 1], int(i))
-        _raise_on_bad(p.cpu().numpy())
+        _raise_on_bad(p.cpu().numpy(), cv)
         k = min(int(i), self.m)
         return B[0, :k].cpu().numpy(), float(F[0].item())
 
@@ -981,7 +1092,7 @@ class NNGP:
         cv, sc = self._sweep_cov()
         B, F, p = _sweep_any(cv, sc, self._nbr_sorted, 0, algo=algo, order=self._order,
                              blocks=self._field_blocks(cv))
-        _raise_on_bad(p.cpu().numpy())
+        _raise_on_bad(p.cpu().numpy(), cv)
         self._B, self._F = B, F
         return B, F
 
@@ -1015,7 +1126,7 @@ class NNGP:
         _, _, p = _sweep_any(cv, sc, self._nbr_sorted, 0, values=v, qvalues=v, want_bf=False, algo=algo,
                              order=self._order, blocks=self._field_blocks(cv))
         ph = p.cpu().numpy()
-        _raise_on_bad(ph)
+        _raise_on_bad(ph, cv)
         n = self.nbr.shape[0]
         return -0.5 * (n * LOG_2PI + ph[0] + ph[1])
 
@@ -1029,6 +1140,8 @@ class NNGP:
 
         if noise is not None:
             _refuse_noise("gls (a regression mean)")
+        if reml:
+            _refuse_sep(self.cov if cov is None else cov, "the restricted likelihood (reml=True)")
         return regression.gls(self, cov, X, values=values, reml=reml, algo=algo)
 
     def conjugate(self, kind: str, phi: float, alpha: float, X, prior: Optional[dict] = None,
@@ -1103,7 +1216,7 @@ class NNGP:
         _, _, p1 = _sweep_any(cov, sc, self._nbr_sorted, 0, values=ones, qvalues=ones, R=r1, **kw)
         s_y1 = torch.sum(ry * r1 / F)
         sums = torch.stack([py[0], py[1], p1[1], s_y1, py[2], py[3]]).cpu().numpy()
-        _raise_on_bad(np.array([0.0, 0.0, sums[4], sums[5]]))
+        _raise_on_bad(np.array([0.0, 0.0, sums[4], sums[5]]), cov)
         logF, qyy, q11, qy1 = sums[:4]
         mu = qy1 / q11
         quad = qyy - 2.0 * mu * qy1 + mu * mu * q11
@@ -1112,6 +1225,10 @@ class NNGP:
     def _grad_cov(self, cov, aniso: bool = True):
         """The covariance of a gradient sweep: a fused kind other than the general-nu Matern, m >= 1."""
         cv = self.cov if cov is None else cov
+        if isinstance(cv, SeparableCovariance):
+            if not aniso:
+                _refuse_sep(cv, "the Fisher information (fisher_information, fit(method='fisher'), stderr=True)")
+            return self._sep_model(cv)
         if isinstance(cv, AnisotropicCovariance):
             self._aniso_phi(cv)
         else:
@@ -1159,6 +1276,12 @@ class NNGP:
             return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:7].copy()
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
+        if isinstance(cv, SeparableCovariance):  # (sigma2, phi_s, phi_t, tau2) from one nngp_bf_grad_sep sweep
+            p, g, _ = _lib.bf_grad_sep(self._s_dev, self._nbr_sorted, 0, cv.kind_s, cv.kind_t, *cv.theta, v,
+                                       order=self._order)
+            h = torch.cat([p, g]).cpu().numpy()
+            _raise_on_bad(h[:4], cv)
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:].copy()
         if isinstance(cv, MaternCovariance):
             p, g, _ = _lib.bf_grad_matern(self._s_dev, self._nbr_sorted, 0, cv.sigma2, cv.phi, cv.tau2, cv.nu, v,
                                           order=self._order, workspace=self._matern_grad_ws())
@@ -1351,7 +1474,8 @@ class NNGP:
 
     def fit(self, kind: Optional[str] = None, x0=None, mean: str = "constant", fix_tau2: Optional[float] = None,
             method: Optional[str] = None, maxiter: int = 400, algo: str = "auto", nu: Optional[float] = None,
-            gradient: bool = False, X=None, reml: bool = False, stderr: bool = False, tol: Optional[float] = None,
+            gradient: Optional[bool] = None, X=None, reml: bool = False, stderr: bool = False,
+            tol: Optional[float] = None,
             anisotropic: bool = False, reneighbor: int = 0, estimate_nu: Optional[bool] = None,
             nu_bounds=(0.05, 50.0), noise=None):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
@@ -1364,7 +1488,8 @@ class NNGP:
         ``gradient=True``: the objective also returns the analytic gradient
         (:meth:`profile_loglik_grad`, d/d log theta = theta d/d theta) and scipy runs with ``jac=True``,
         L-BFGS-B by default; fused kinds other than ``matern`` and 1 <= m <= 32 only.  The result gains
-        ``n_grad_evals``.
+        ``n_grad_evals``.  ``gradient=None``, the default, is ``False`` for every model but one built with a
+        :class:`SeparableCovariance` (last paragraph), where it is ``True``.
 
         ``mean="linear"`` with ``X`` (n, p): the regression mean X beta is profiled out (:meth:`gls`); the result
         gains ``beta`` and ``cov_beta`` at the estimate and ``mu`` is None.  ``reml=True`` (``mean="linear"``, or
@@ -1409,7 +1534,37 @@ class NNGP:
         ``gradient=True`` (``nngp_bf_grad_noise``; ``tol``, when given, is then L-BFGS-B's ``gtol`` and the only
         stopping rule beside ``maxiter``); the result gains ``grad``, the gradient in the free log-parameters at the
         estimate.  Constant and zero means; no ``stderr``, ``method="fisher"``, ``anisotropic``, ``reml``,
-        ``estimate_nu`` or the ``matern`` kind with it."""
+        ``estimate_nu`` or the ``matern`` kind with it.
+
+        A model built with a :class:`SeparableCovariance`: L-BFGS-B on the analytic gradient
+        (``nngp_bf_grad_sep``) over the free log-parameters of (sigma2, phi_s, phi_t, tau2), the two kinds fixed to
+        the model's.  ``x0`` = (sigma2, phi_s, phi_t, tau2) (default: the model's theta); ``fix_tau2``, ``mean``,
+        ``X``, ``tol`` (L-BFGS-B's ``gtol``, then the only stopping rule beside ``maxiter``), ``maxiter`` and
+        ``reneighbor=r`` as for ``anisotropic=True``.  ``gradient=None`` (the default) and ``True`` are this fit;
+        ``gradient=False``: Nelder-Mead on the forward sweep.  The result carries ``theta``, ``grad`` (the gradient in
+        the free log-parameters at the reported ``theta``), ``loglik``, ``n_evals``, ``n_grad_evals``, ``converged`` and
+        ``message``.  A neighbour index out of range raises :class:`NNGPIndexError` from this model's methods: an
+        ``NNGPNumericalError`` and an ``IndexError`` (what every other model raises) at once.
+        Every other option raises ``TypeError``."""
+        gradient_asked = gradient
+        gradient = bool(gradient)
+        if isinstance(getattr(self, "cov", None), SeparableCovariance):
+            # a SeparableCovariance model: L-BFGS-B on the analytic gradient over the free log-parameters of
+            # (sigma2, phi_s, phi_t, tau2) (nngp_bf_grad_sep), the kinds fixed to the model's; fix_tau2, mean, X, tol
+            # (L-BFGS-B's gtol), maxiter and reneighbor=r as for anisotropic=True.  gradient=False: Nelder-Mead on the
+            # forward sweep (``gradient`` left at None means True here, False for every other model).
+            for on, what in ((stderr, "stderr=True"), (method == "fisher", "method='fisher'"), (reml, "reml=True"),
+                             (noise is not None, "noise="), (anisotropic, "anisotropic=True"),
+                             (estimate_nu is not None, "estimate_nu"), (kind is not None, "kind="),
+                             (nu is not None, "nu=")):
+                if on:
+                    _refuse_sep(self.cov, f"fit with {what}")
+            if mean == "linear" and X is None:
+                raise ValueError("mean='linear' needs the design matrix X")
+            if mean != "linear" and X is not None:
+                raise ValueError("X is the design of mean='linear'")
+            return self._fit_sep(x0, mean, fix_tau2, method, maxiter, X, int(reneighbor), algo, tol,
+                                 gradient_asked is None or gradient)
         if noise is not None:
             for on, what in ((stderr, "stderr=True"), (method == "fisher", "method='fisher'"),
                              (anisotropic, "anisotropic=True"), (estimate_nu is not None, "estimate_nu"),
@@ -1631,6 +1786,120 @@ class NNGP:
                 "n_grad_evals": n_grad, "converged": bool(res.success) and not last_failed[0],
                 "message": str(res.message), "rounds": reneighbor + 1,
                 **self._fit_beta(X if linear else None, algo)}
+
+    def _fit_sep(self, x0, mean, fix_tau2, method, maxiter, X, reneighbor: int, algo: str, tol, gradient: bool) -> dict:
+        """``fit`` of a :class:`SeparableCovariance` model: _fit_aniso's scaffolding over (sigma2, phi_s, phi_t,
+        tau2), or Nelder-Mead on the forward sweep (``gradient`` False)."""
+        from scipy.optimize import minimize
+
+        if reneighbor < 0:
+            raise ValueError("reneighbor must be >= 0")
+        base = self._sep_model(self.cov)
+        if x0 is not None and len(x0) != 4:
+            raise ValueError("x0 must be (sigma2, phi_s, phi_t, tau2)")
+        s0, ps0, pt0, t0 = (float(v) for v in (x0 if x0 is not None else base.theta))
+        free_tau = fix_tau2 is None
+        linear = mean == "linear"
+        if mean not in ("constant", "zero", "linear"):
+            raise ValueError("mean must be 'constant', 'zero' or 'linear'")
+        if linear:
+            from . import regression
+
+            X = regression.design(self, X, self.nbr.shape[0])
+        if method is None:
+            method = "L-BFGS-B" if gradient else "Nelder-Mead"
+        nz = 3 + (1 if free_tau else 0)
+
+        def cov_of(z):
+            return SeparableCovariance(base.kind_s, base.kind_t, math.exp(z[0]), math.exp(z[1]), math.exp(z[2]),
+                                       math.exp(z[3]) if free_tau else float(fix_tau2))
+
+        start = SeparableCovariance(base.kind_s, base.kind_t, s0, ps0, pt0,
+                                    max(t0, 1e-6) if free_tau else float(fix_tau2))
+        n_evals = n_grad = 0
+        if gradient:
+            options = {"maxiter": maxiter}
+            if tol is not None and method == "L-BFGS-B":
+                options.update(gtol=float(tol), ftol=1e-15)  # the gradient rule alone
+            elif tol is not None:
+                options["gtol"] = float(tol)
+        else:
+            options = {"maxiter": maxiter}
+            if method == "Nelder-Mead":
+                options.update(xatol=1e-6 if tol is None else float(tol), fatol=1e-9)
+        for rnd in range(reneighbor + 1):
+            if rnd > 0:
+                self.rebuild_neighbors(start)
+            best, seen, last_failed = {"ll": -math.inf}, {}, [False]
+
+            def cov_at(z):
+                """The covariance at log-parameters z, or None where exp(z) leaves the positive finite doubles (a line
+                search's far step): both objectives then return the penalty value."""
+                try:
+                    return cov_of(z)
+                except (OverflowError, ValueError):
+                    return None
+
+            def obj_grad(z):
+                cv = cov_at(z)
+                try:
+                    if cv is None:
+                        raise NNGPNumericalError("theta outside the positive finite doubles")
+                    ll, mu, g = self.profile_loglik_grad(cv, mean=mean, X=X)
+                except NNGPIndexError:  # a bad neighbour index is no property of theta
+                    raise
+                except NNGPNumericalError:
+                    last_failed[0] = True
+                    return 1e300, np.zeros(len(z))
+                last_failed[0] = False
+                th = cv.theta
+                gz = np.array([th[k] * g[k] for k in range(len(z))])
+                seen[tuple(z)] = gz
+                if ll > best["ll"]:
+                    best.update(ll=ll, mu=None if linear else mu, cov=cv, grad=gz)
+                return -ll, -gz
+
+            def obj(z):
+                cv = cov_at(z)
+                try:
+                    if cv is None:
+                        raise NNGPNumericalError("theta outside the positive finite doubles")
+                    ll, mu = self.profile_loglik(cv, mean=mean, X=X)
+                except NNGPIndexError:
+                    raise
+                except NNGPNumericalError:
+                    return 1e300
+                if ll > best["ll"]:
+                    best.update(ll=ll, mu=None if linear else mu, cov=cv)
+                return -ll
+
+            z0 = np.log(np.array(start.theta[:nz]))
+            if gradient:
+                res = minimize(obj_grad, z0, jac=True, method=method, options=options)
+            else:
+                res = minimize(obj, z0, method=method, options=options)
+            n_evals += int(res.nfev)
+            n_grad += len(seen)
+            if "cov" not in best:
+                raise NNGPNumericalError("fit (SeparableCovariance): no parameter value the optimiser tried was "
+                                         "positive definite")
+            start = best["cov"]
+        self.cov = start
+        self._B = self._F = None
+        if reneighbor > 0:
+            # as fit(anisotropic=True): the sets in the estimate's own metric, the likelihood on them
+            self.rebuild_neighbors(start)
+            if linear:
+                best["ll"] = self.gls(start, X, algo=algo).loglik
+            else:
+                best["ll"], best["mu"] = self.profile_loglik(start, mean=mean, algo=algo)
+        out = {"theta": start.theta, "sigma2": start.sigma2, "phi_s": start.phi_s, "phi_t": start.phi_t,
+               "tau2": start.tau2, "mu": best["mu"], "loglik": best["ll"], "n_evals": n_evals, "n_grad_evals": n_grad,
+               "converged": bool(res.success) and not last_failed[0], "message": str(res.message),
+               "rounds": reneighbor + 1, **self._fit_beta(X if linear else None, algo)}
+        if gradient:
+            out["grad"] = best["grad"]  # at the reported theta (the best point seen, the last round's)
+        return out
 
     def _fit_matern(self, kind, x0, mean, fix_tau2, method, maxiter, X, algo, tol, nu, free_nu: bool,
                     nu_bounds) -> dict:
@@ -1978,7 +2247,14 @@ class NNGPNumericalError(ArithmeticError):
     """A location's neighbour covariance was not positive definite."""
 
 
-def _raise_on_bad(partials_host) -> None:
+class NNGPIndexError(NNGPNumericalError, IndexError):
+    """A neighbour index was out of range, as a :class:`SeparableCovariance` model reports it: both of the sweep's
+    flags surface as :class:`NNGPNumericalError` there (it is an ``IndexError`` too, what every other model raises)."""
+
+
+def _raise_on_bad(partials_host, cov=None) -> None:
+    if partials_host[3] >= 0 and isinstance(cov, SeparableCovariance):
+        raise NNGPIndexError(f"neighbour index out of range at location {int(partials_host[3])}")
     if partials_host[3] >= 0:
         raise IndexError(f"neighbour index out of range at location {int(partials_host[3])}")
     if partials_host[2] >= 0:

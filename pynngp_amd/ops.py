@@ -27,6 +27,12 @@ for tracing.
         -> (partials, grad, G)                                         # bf_grad of that model
     torch.ops.nngp.bf_cross_noise(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, noise_ref, noise_query)
         -> (B, F, mean)                                                # bf_cross of that model; noise_query None: 1
+    torch.ops.nngp.bf_sweep_sep(coords, nbr, order, i0, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, values, want_bf)
+        -> (B, F, R, partials)   # separable space x time (time in the last column); B, F empty without want_bf
+    torch.ops.nngp.bf_grad_sep(coords, nbr, order, i0, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, values, want_rows)
+        -> (partials, grad, G)                                         # grad (4,), G (rows, 4): sigma2, phi_s, phi_t, tau2
+    torch.ops.nngp.bf_cross_sep(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values)
+        -> (B, F, mean)                                                # bf_cross of that model
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -169,6 +175,22 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_noise")
     def _(ref, query, nbr, kind, sigma2, phi, tau2, ref_values, noise_ref, noise_query):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_sep")
+    def _(coords, nbr, order, i0, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, values, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_grad_sep")
+    def _(coords, nbr, order, i0, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, values, want_rows):
+        return (coords.new_empty((4,)), coords.new_empty((4,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, 4)))
+
+    @fake("bf_cross_sep")
+    def _(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 

@@ -186,7 +186,7 @@ def whitened_gram(nngp, cov, X: torch.Tensor, v: torch.Tensor, algo: str = "auto
     V = torch.cat([v[:, None], X], dim=1).contiguous()
     _, G = _lib.whiten_gram(nngp._nbr_sorted, B, F, V, 0, order=nngp._order)
     host = torch.cat([p, G.reshape(-1)]).cpu().numpy()  # one copy: the partials and the Gram matrix
-    _raise_on_bad(host[:4])
+    _raise_on_bad(host[:4], cv)
     k = V.shape[1]
     return float(host[0]), host[4:].reshape(k, k).copy(), B, F
 

@@ -186,6 +186,9 @@ class ShardedLogLik:
     def local_partials(self, cov: Covariance, values: Optional[torch.Tensor], want_bf: bool = True,
                        values_layout: str = "input", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stream-ordered partials of this shard (no host sync); into ``out`` (4,) if given."""
+        from .nngp import _refuse_sep
+
+        _refuse_sep(cov, "the multi-GPU sweep (ShardedLogLik)")
         if self.layout == "storage" and values is not None and values_layout == "input":
             values = self.to_storage(values, out=self._vstore)
         if self._compute is not None:
