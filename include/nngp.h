@@ -72,6 +72,7 @@ int32_t nngp_resolve_algo_nu(int32_t algo, int32_t m, int32_t kind, int32_t dim,
 
 #define NNGP_MAX_M 63
 #define NNGP_MAX_DIM 3
+#define NNGP_ND_MAX_DIM 16 /* the n-dimensional path (nngp_*_nd): 4 <= dim <= NNGP_ND_MAX_DIM */
 
 /* Library version string, e.g. "pynngp_amd 0.3.0 gfx950". */
 const char *nngp_version(void);
@@ -263,6 +264,51 @@ int nngp_bf_grad_sep(const double *coords, int64_t n_points, int32_t dim, const 
                      int64_t n_rows, int32_t m, int64_t i0, int32_t kind_s, int32_t kind_t, double sigma2,
                      double phi_s, double phi_t, double tau2, const double *values, double *G, double *partials,
                      double *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Points in 4 .. NNGP_ND_MAX_DIM dimensions (added within revision 4; nothing earlier moved).  Every entry point
+ * above keeps its 1 <= dim <= NNGP_MAX_DIM; these take 4 <= dim <= NNGP_ND_MAX_DIM and nothing else.
+ *
+ * Neighbour sets, exact, by tiled brute force (N^2 / 2 * dim for the prior form), the ordering key of nngp_knn_prior:
+ *   nngp_knn_prior_nd: the contract of nngp_knn_prior (rows [q0, q1), coords[0:i] for row i, -1 padding);
+ *   nngp_knn_query_nd: the contract of nngp_knn_query (every query searches all n_ref points).
+ * 0 <= m (k) <= 32.  workspace: nngp_knn_nd_workspace_bytes(n_points, dim, m), 256-B aligned (the searches use
+ * none of it; the size is 0 only for unsupported arguments).
+ *
+ * Sweeps under one decay per axis (ARD):
+ *   C(a, b) = sigma2 rho(u) + tau2 delta_ab,  u = sqrt(sum_k (phi[k] (a_k - b_k))^2),
+ * phi a HOST array of dim decays, kind NNGP_COV_EXPONENTIAL, MATERN32, MATERN52 or GAUSSIAN.  NNGP_COV_SPHERICAL is
+ * refused with NNGP_EUNSUP: it is not positive definite above three dimensions.
+ *   nngp_bf_sweep_nd: the contract of nngp_bf_sweep_noise without the weights (B, F, R, partials[4] required, order,
+ *     i0, -1 padding, the two flags, NaN rows on a bad pivot, a fixed-order fold).
+ *   nngp_bf_cross_nd: the contract of nngp_bf_cross_noise without the weights (reference points, query points).
+ *   nngp_bf_grad_nd: the contract of nngp_bf_grad_aniso with G (n_rows, dim + 2) and grad[dim + 2] in
+ *     (sigma2, phi_1..phi_dim, tau2): dC_ab/dphi_k = sigma2 rho'(u) (phi_k (a_k - b_k))^2 / (u phi_k), exactly 0 for
+ *     coincident points.
+ * Scope: 1 <= m <= 32, 4 <= dim <= NNGP_ND_MAX_DIM, kinds as above, else NNGP_EUNSUP.  NNGP_EINVAL for sigma2 <= 0,
+ * tau2 < 0, a non-positive or non-finite phi[k], a null pointer.
+ * workspace: nngp_bf_sweep_nd_workspace_bytes(n_rows, m, dim) serves all three (0 for unsupported arguments);
+ * 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_knn_nd_workspace_bytes(int64_t n_points, int32_t dim, int32_t m);
+int nngp_knn_prior_nd(const double *coords, int64_t n_points, int32_t dim, int32_t m, int64_t q0, int64_t q1,
+                      int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_knn_query_nd(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query, int32_t k,
+                      int32_t *nbr, void *workspace, size_t workspace_bytes, void *stream);
+size_t nngp_bf_sweep_nd_workspace_bytes(int64_t n_rows, int32_t m, int32_t dim);
+int nngp_bf_sweep_nd(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double *phi, double tau2,
+                     const double *values, double *B, double *F, double *R, double *partials, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int nngp_bf_cross_nd(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                     const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                     double sigma2, const double *phi, double tau2, const double *ref_values,
+                     const double *query_values, double *B, double *F, double *R, double *partials, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int nngp_bf_grad_nd(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                    int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double *phi, double tau2,
+                    const double *values, double *G, double *partials, double *grad, void *workspace,
+                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,

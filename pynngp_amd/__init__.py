@@ -12,6 +12,8 @@ from .autograd import loglik, loglik_matern  # noqa: F401
 from .nngp import MaternCovariance  # noqa: F401
 from .nngp import SeparableCovariance, NNGPIndexError  # noqa: F401
 from .autograd import loglik_sep  # noqa: F401
+from .nd import ARDCovariance, NNGPnd  # noqa: F401
+from .autograd import loglik_ard  # noqa: F401
 from .sweep import ShardedLogLik, shard_range, combine_partials  # noqa: F401
 from .gibbs import SeqNNGP, SeqNNGPChains, Priors  # noqa: F401
 from .gibbs_sharded import ShardedSeqNNGP  # noqa: F401

@@ -78,6 +78,13 @@ SYMBOLS = (
     "nngp_bf_sweep_sep",
     "nngp_bf_cross_sep",
     "nngp_bf_grad_sep",
+    "nngp_knn_nd_workspace_bytes",
+    "nngp_knn_prior_nd",
+    "nngp_knn_query_nd",
+    "nngp_bf_sweep_nd_workspace_bytes",
+    "nngp_bf_sweep_nd",
+    "nngp_bf_cross_nd",
+    "nngp_bf_grad_nd",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
     "nngp_bf_grad_matern_workspace_bytes",
@@ -132,6 +139,9 @@ MATERN_NU_MAX = 50.0
 ALGO_CODES = {"auto": 0, "lane": 1, "wave": 2, "quad": 4, "pairb": 5}
 MAX_M = 63
 MAX_DIM = 3
+ND_MIN_DIM = 4   # the n-dimensional path (nngp_*_nd): MAX_DIM < dim <= ND_MAX_DIM
+ND_MAX_DIM = 16  # NNGP_ND_MAX_DIM
+ND_KINDS = ("exponential", "matern32", "matern52", "gaussian")
 ABI_VERSION = 4  # NNGP_ABI_VERSION of include/nngp.h this binding's signatures follow
 PLAN_INFO_LEN = 10  # NNGP_PLAN_INFO_LEN
 CERT_INFO_LEN = 16  # NNGP_CERT_INFO_LEN
@@ -200,6 +210,20 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_cross_sep.restype = ctypes.c_int
     lib.nngp_bf_grad_sep.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, I32, D, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_sep.restype = ctypes.c_int
+    lib.nngp_knn_nd_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_knn_nd_workspace_bytes.restype = SZ
+    lib.nngp_knn_prior_nd.argtypes = [P, I64, I32, I32, I64, I64, P, P, SZ, P]
+    lib.nngp_knn_prior_nd.restype = ctypes.c_int
+    lib.nngp_knn_query_nd.argtypes = [P, I64, I32, P, I64, I32, P, P, SZ, P]
+    lib.nngp_knn_query_nd.restype = ctypes.c_int
+    lib.nngp_bf_sweep_nd_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_sweep_nd_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_nd.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_nd.restype = ctypes.c_int
+    lib.nngp_bf_cross_nd.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_cross_nd.restype = ctypes.c_int
+    lib.nngp_bf_grad_nd.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_nd.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
     lib.nngp_bf_grad_aniso_workspace_bytes.restype = SZ
     lib.nngp_bf_grad_aniso.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
@@ -1323,6 +1347,168 @@ def bf_cross_sep(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind
                                  float(phi_t), float(tau2), _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F),
                                  _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_cross_sep")
+    return B, F, R, partials
+
+
+# ---------------------------------------------------------------- points in 4 .. 16 dimensions (nngp_*_nd)
+def _as_coords_nd(coords: torch.Tensor) -> torch.Tensor:
+    """float64 (N, dim) ordinates, ND_MIN_DIM <= dim <= ND_MAX_DIM."""
+    if coords.dim() != 2 or not ND_MIN_DIM <= coords.shape[1] <= ND_MAX_DIM or coords.dtype != torch.float64:
+        raise ValueError(f"coords must be float64 (N, dim), {ND_MIN_DIM} <= dim <= {ND_MAX_DIM}, got "
+                         f"{tuple(coords.shape)} {coords.dtype}")
+    return coords.contiguous()
+
+
+def _nd_checks(kind: str, m: int, dim: int, phi) -> "ctypes.Array":
+    """The scope of the n-dimensional sweeps (nngp_bf_*_nd); returns the decays as a C array."""
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind == "spherical":
+        raise NotImplementedError("the spherical correlation is not positive definite above three dimensions: the "
+                                  "n-dimensional sweeps refuse it")
+    if kind not in ND_KINDS:
+        raise NotImplementedError(f"the n-dimensional sweeps serve the kinds {ND_KINDS}, not {kind!r}")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the n-dimensional sweeps serve 1 <= m <= {GRAD_MAX_M} (m={m})")
+    phi = [float(x) for x in phi]
+    if len(phi) != dim:
+        raise ValueError(f"phi must hold one decay per coordinate column ({dim}), got {len(phi)}")
+    return (ctypes.c_double * dim)(*phi)
+
+
+def knn_prior_nd(coords: torch.Tensor, m: int, q0: int = 0, q1: Optional[int] = None) -> torch.Tensor:
+    """:func:`knn_prior` for 4 .. 16 coordinate columns (``nngp_knn_prior_nd``: exact, tiled brute force)."""
+    coords = _as_coords_nd(coords)
+    dev = _require_gpu(coords)
+    n, d = coords.shape
+    q1 = n if q1 is None else int(q1)
+    if not 0 <= q0 <= q1 <= n:
+        raise ValueError(f"query rows [{q0}, {q1}) outside [0, {n})")
+    out = torch.empty((q1 - q0, m), dtype=torch.int32, device=dev)
+    lib = load()
+    ws = _workspace(lib.nngp_knn_nd_workspace_bytes(n, d, m), dev)
+    _check(lib.nngp_knn_prior_nd(_ptr(coords), n, d, m, q0, q1, _ptr(out), _ptr(ws), ws.numel(), _stream(dev)),
+           "nngp_knn_prior_nd")
+    return out
+
+
+def knn_query_nd(ref: torch.Tensor, query: torch.Tensor, k: int) -> torch.Tensor:
+    """:func:`knn_query` for 4 .. 16 coordinate columns (``nngp_knn_query_nd``)."""
+    ref, query = _as_coords_nd(ref), _as_coords_nd(query)
+    d = _same_dim(ref, query)
+    dev = _require_gpu(ref, query)
+    out = torch.empty((query.shape[0], k), dtype=torch.int32, device=dev)
+    lib = load()
+    ws = _workspace(lib.nngp_knn_nd_workspace_bytes(ref.shape[0], d, k), dev)
+    _check(lib.nngp_knn_query_nd(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], k, _ptr(out), _ptr(ws),
+                                 ws.numel(), _stream(dev)), "nngp_knn_query_nd")
+    return out
+
+
+def bf_sweep_nd(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi, tau2: float,
+                values: Optional[torch.Tensor] = None, want_bf: bool = True, order: Optional[torch.Tensor] = None,
+                want_r: bool = False, workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep` for 4 .. 16 coordinate columns with one decay per column (``nngp_bf_sweep_nd``,
+    include/nngp.h): ``sigma2 rho(sqrt(sum_k (phi_k d_k)^2)) + tau2 delta_ab``.  ``phi`` is a sequence of ``dim``
+    floats.  Returns ``(B, F, R, partials)`` (B, F None without ``want_bf``; R None without ``want_r``, which needs
+    ``values``).  Kinds exponential, matern32, matern52, gaussian; 1 <= m <= 32; ``order`` as in :func:`bf_sweep`."""
+    coords = _as_coords_nd(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n, d = coords.shape
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (n,):
+            raise ValueError("values must be float64 (N,)")
+        values = values.contiguous()
+    rows, m = nbr.shape
+    cphi = _nd_checks(kind, m, d, phi)
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and values is None:
+        raise ValueError("want_r needs values")
+    lib = load()
+    need = lib.nngp_bf_sweep_nd_workspace_bytes(rows, m, d)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev) if want_bf else None
+    F = torch.empty((rows,), dtype=torch.float64, device=dev) if want_bf else None
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_nd(_ptr(coords), n, d, _ptr(nbr), _ptr(order), rows, m, int(i0), KIND_CODES[kind],
+                                float(sigma2), cphi, float(tau2), _ptr(values), _ptr(B), _ptr(F), _ptr(R),
+                                _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_sweep_nd")
+    return B, F, R, partials
+
+
+def bf_grad_nd(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2: float, phi, tau2: float,
+               values: torch.Tensor, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`bf_grad_aniso` for 4 .. 16 coordinate columns (``nngp_bf_grad_nd``): ``(partials, grad, G)`` with grad
+    (dim + 2,) and G (rows, dim + 2) in (sigma2, phi_1..phi_dim, tau2)."""
+    coords = _as_coords_nd(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n, d = coords.shape
+    if values is None or values.dtype != torch.float64 or values.shape != (n,):
+        raise ValueError("values must be float64 (N,)")
+    values = values.contiguous()
+    rows, m = nbr.shape
+    cphi = _nd_checks(kind, m, d, phi)
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_sweep_nd_workspace_bytes(rows, m, d)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(d + 2, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, d + 2), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_nd(_ptr(coords), n, d, _ptr(nbr), _ptr(order), rows, m, int(i0), KIND_CODES[kind],
+                               float(sigma2), cphi, float(tau2), _ptr(values), _ptr(G), _ptr(partials), _ptr(grad),
+                               _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_grad_nd")
+    return partials, grad, G
+
+
+def bf_cross_nd(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: str, sigma2: float, phi, tau2: float,
+                ref_values: Optional[torch.Tensor] = None, query_values: Optional[torch.Tensor] = None, q0: int = 0,
+                order: Optional[torch.Tensor] = None, want_r: bool = False):
+    """:func:`bf_cross` for 4 .. 16 coordinate columns (``nngp_bf_cross_nd``).  Returns ``(B, F, R, partials)`` (R None
+    without ``want_r``, which needs ``ref_values``)."""
+    ref, query = _as_coords_nd(ref), _as_coords_nd(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if ref_values is not None:
+        if ref_values.dtype != torch.float64 or ref_values.shape != (ref.shape[0],):
+            raise ValueError("ref_values must be float64 (n_ref,)")
+        ref_values = ref_values.contiguous()
+    if query_values is not None:
+        if query_values.dtype != torch.float64 or query_values.shape != (query.shape[0],):
+            raise ValueError("query_values must be float64 (n_query,)")
+        query_values = query_values.contiguous()
+    rows, m = nbr.shape
+    cphi = _nd_checks(kind, m, d, phi)
+    dev = _require_gpu(ref, query, nbr, ref_values, query_values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and ref_values is None:
+        raise ValueError("want_r needs ref_values")
+    lib = load()
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev)
+    F = torch.empty((rows,), dtype=torch.float64, device=dev)
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_nd_workspace_bytes(rows, m, d), dev)
+    _check(lib.nngp_bf_cross_nd(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order), rows, m,
+                                int(q0), KIND_CODES[kind], float(sigma2), cphi, float(tau2), _ptr(ref_values),
+                                _ptr(query_values), _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace),
+                                workspace.numel(), _stream(dev)), "nngp_bf_cross_nd")
     return B, F, R, partials
 
 

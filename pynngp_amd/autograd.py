@@ -221,6 +221,70 @@ def loglik_sep(coords, nbr, kind_s, kind_t, theta4, values, order=None):
     return ll
 
 
+class _LogLikArd(torch.autograd.Function):
+    """theta = (sigma2, phi_1 .. phi_dim, tau2): the n-dimensional sweep (``torch.ops.nngp.bf_grad_nd``)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, kind, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_nd(coords, nbr, order, 0, _lib.KIND_CODES[kind], th[0], th[1:-1], th[-1],
+                                            values.detach(), False)
+        ctx.save_for_backward(coords, nbr, values, g)
+        ctx.meta = (kind, order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g = ctx.saved_tensors
+        kind, order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLik: one ordinary sweep (B, F, R) of the same model
+            B, F, R, _ = _lib.bf_sweep_nd(coords, nbr, 0, kind, th[0], th[1:-1], th[-1], values=values.detach(),
+                                          order=order, want_r=True)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None, None
+
+
+def loglik_ard(coords, nbr, kind, theta, values, order=None):
+    """NNGP log-likelihood of ``values`` on S = T for 4 .. 16 coordinate columns under one decay per column,
+    ``sigma2 rho(sqrt(sum_k (phi_k d_k)^2)) + tau2 delta``, at ``theta`` = (sigma2, phi_1 .. phi_dim, tau2), a float64
+    (dim + 2,) tensor, differentiable in ``theta`` and, when ``values.requires_grad``, in ``values``.
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_nd``) and synchronises with the host as
+    :func:`loglik` does; backward returns ``grad_out * grad`` for theta with no further launch.  ``nbr`` (N, m) int32
+    with 1 <= m <= 32; kinds exponential, matern32, matern52, gaussian; the not-PD and bad-index flags raise.
+    """
+    if kind not in _lib.KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in _lib.ND_KINDS:
+        raise NotImplementedError(f"loglik_ard serves the kinds {_lib.ND_KINDS}")
+    if coords.dim() != 2 or not _lib.ND_MIN_DIM <= coords.shape[1] <= _lib.ND_MAX_DIM:
+        raise NotImplementedError(f"loglik_ard serves {_lib.ND_MIN_DIM} .. {_lib.ND_MAX_DIM} coordinate columns")
+    if theta.dtype != torch.float64 or theta.shape != (coords.shape[1] + 2,):
+        raise ValueError("theta must be a float64 (dim + 2,) tensor (sigma2, phi_1 .. phi_dim, tau2)")
+    if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
+        raise NotImplementedError(f"loglik_ard's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
+    if nbr.shape[0] != coords.shape[0]:
+        raise ValueError("loglik_ard is an S = T sweep: one nbr row per location")
+    ll, p = _LogLikArd.apply(coords, nbr, theta, values, kind, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 def loglik_matern(coords, nbr, theta, values, order=None):
     """NNGP log-likelihood of ``values`` on S = T under the general-smoothness Matern covariance at ``theta`` =
     (sigma2, phi, tau2, nu), a float64 (4,) tensor, differentiable in all four entries of ``theta`` and, when

@@ -14,6 +14,7 @@
 #include "bf_grad.h"
 #include "bf_noise.h"
 #include "bf_sep.h"
+#include "bf_nd.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -391,6 +392,98 @@ int nngp_bf_grad_sep(const double* coords, int64_t n_points, int32_t dim, const 
                     coords, values, nullptr, nullptr, nullptr, G, (double*)workspace};
     hipError_t e = nngp::bf_sep_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_sep launch");
+    return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- points in 4 .. 16 dimensions (bf_nd.h, knn_nd.hip)
+// the checks live in nd_host.h (no HIP in it); their message becomes the thread's last error
+static int nd_report(const nngp::NdError& e) { return fail(e.code, "%s", e.msg); }
+
+size_t nngp_knn_nd_workspace_bytes(int64_t n_points, int32_t dim, int32_t m) {
+    return nngp::nd_knn_workspace_bytes(n_points, dim, m);
+}
+
+int nngp_knn_prior_nd(const double* coords, int64_t n_points, int32_t dim, int32_t m, int64_t q0, int64_t q1,
+                      int32_t* nbr, void* workspace, size_t workspace_bytes, void* stream) {
+    nngp::NdError err;
+    if (nngp::nd_knn_check(err, coords, n_points, dim, m, workspace, workspace_bytes) != NNGP_OK) return nd_report(err);
+    if (q0 < 0 || q1 < q0 || q1 > n_points)
+        return fail(NNGP_EINVAL, "query rows [%lld, %lld) invalid", (long long)q0, (long long)q1);
+    if (q1 > q0 && m > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (q1 == q0 || m == 0) return NNGP_OK;
+    hipError_t e = nngp::knn_nd_launch(true, coords, n_points, dim, m, coords, q0, q1, nbr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "knn_prior_nd launch");
+    return NNGP_OK;
+}
+
+int nngp_knn_query_nd(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query, int32_t k,
+                      int32_t* nbr, void* workspace, size_t workspace_bytes, void* stream) {
+    nngp::NdError err;
+    if (nngp::nd_knn_check(err, ref, n_ref, dim, k, workspace, workspace_bytes) != NNGP_OK) return nd_report(err);
+    if (n_query < 0) return fail(NNGP_EINVAL, "n_query < 0");
+    if (n_query > 0 && k > 0 && (query == nullptr || nbr == nullptr))
+        return fail(NNGP_EINVAL, "query and nbr must be non-null");
+    if (n_query == 0 || k == 0) return NNGP_OK;
+    hipError_t e = nngp::knn_nd_launch(false, ref, n_ref, dim, k, query, 0, n_query, nbr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "knn_query_nd launch");
+    return NNGP_OK;
+}
+
+size_t nngp_bf_sweep_nd_workspace_bytes(int64_t n_rows, int32_t m, int32_t dim) {
+    return nngp::nd_workspace_bytes(n_rows, m, dim);
+}
+
+static int nd_forward(const double* coords, int64_t n_points, int32_t dim, const double* qcoords, int64_t n_locs,
+                      const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
+                      double sigma2, const double* phi, double tau2, const double* values, const double* qvalues,
+                      double* B, double* F, double* R, double* partials, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    nngp::NdError err;
+    if (nngp::nd_sweep_check(err, coords, n_points, dim, nbr, n_rows, m, i0, n_locs, kind, sigma2, phi, tau2, partials,
+                             workspace, workspace_bytes) != NNGP_OK)
+        return nd_report(err);
+    if (qcoords == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (B != nullptr && F == nullptr) return fail(NNGP_EINVAL, "B given without F");
+    if (F != nullptr && B == nullptr && n_rows > 0) return fail(NNGP_EINVAL, "F given without B");
+    if (R != nullptr && values == nullptr) return fail(NNGP_EINVAL, "R (residuals) needs values");
+    nngp::NdArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, tau2, phi, values,
+                   qcoords, qvalues, B, F, R, nullptr, (double*)workspace};
+    hipError_t e = nngp::bf_nd_launch(a, partials, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_nd launch");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_nd(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double* phi, double tau2,
+                     const double* values, double* B, double* F, double* R, double* partials, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    return nd_forward(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2, values,
+                      values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_cross_nd(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,
+                     const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                     double sigma2, const double* phi, double tau2, const double* ref_values,
+                     const double* query_values, double* B, double* F, double* R, double* partials, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (query_values != nullptr && ref_values == nullptr) return fail(NNGP_EINVAL, "query_values need ref_values");
+    return nd_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, m, q0, kind, sigma2, phi, tau2, ref_values,
+                      query_values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_grad_nd(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                    int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double* phi, double tau2,
+                    const double* values, double* G, double* partials, double* grad, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    nngp::NdError err;
+    if (nngp::nd_sweep_check(err, coords, n_points, dim, nbr, n_rows, m, i0, n_points, kind, sigma2, phi, tau2, partials,
+                             workspace, workspace_bytes) != NNGP_OK)
+        return nd_report(err);
+    if (values == nullptr || grad == nullptr) return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    nngp::NdArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, sigma2, tau2, phi, values,
+                   coords, values, nullptr, nullptr, nullptr, G, (double*)workspace};
+    hipError_t e = nngp::bf_nd_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_nd launch");
     return NNGP_OK;
 }
 

@@ -548,6 +548,124 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_sep(const at::Tensor& re
     return {B, F, mean};
 }
 
+// ---------------------------------------------------------------- points in 4 .. 16 dimensions (nngp_*_nd)
+void check_coords_nd(const at::Tensor& c, const char* name) {
+    TORCH_CHECK(c.is_cuda(), name, " must be a ROCm GPU tensor (there is no CPU fallback)");
+    TORCH_CHECK(c.scalar_type() == at::kDouble && c.dim() == 2 && c.size(1) > NNGP_MAX_DIM && c.size(1) <= NNGP_ND_MAX_DIM,
+                name, " must be float64 (N, dim), ", NNGP_MAX_DIM + 1, " <= dim <= ", NNGP_ND_MAX_DIM);
+    TORCH_CHECK(c.is_contiguous(), name, " must be contiguous");
+}
+
+void check_phi_nd(at::ArrayRef<double> phi, const at::Tensor& coords) {
+    TORCH_CHECK((int64_t)phi.size() == coords.size(1), "phi must hold one decay per coordinate column (", coords.size(1),
+                "), got ", phi.size());
+}
+
+at::Tensor knn_prior_nd(const at::Tensor& coords, int64_t m, int64_t q0, int64_t q1) {
+    check_coords_nd(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    const int64_t n = coords.size(0), d = coords.size(1);
+    TORCH_CHECK(0 <= q0 && q0 <= q1 && q1 <= n, "query rows [", q0, ", ", q1, ") outside [0, ", n, ")");
+    auto out = at::empty({q1 - q0, m}, coords.options().dtype(at::kInt));
+    auto ws = workspace((int64_t)nngp_knn_nd_workspace_bytes(n, (int32_t)d, (int32_t)m), coords);
+    check_rc(nngp_knn_prior_nd(coords.data_ptr<double>(), n, (int32_t)d, (int32_t)m, q0, q1, out.data_ptr<int32_t>(),
+                               ws.data_ptr(), ws.numel(), stream(coords)),
+             "nngp_knn_prior_nd");
+    return out;
+}
+
+at::Tensor knn_query_nd(const at::Tensor& ref, const at::Tensor& query, int64_t k) {
+    check_coords_nd(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords_nd(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    const int64_t d = ref.size(1);
+    auto out = at::empty({query.size(0), k}, ref.options().dtype(at::kInt));
+    auto ws = workspace((int64_t)nngp_knn_nd_workspace_bytes(ref.size(0), (int32_t)d, (int32_t)k), ref);
+    check_rc(nngp_knn_query_nd(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(), query.size(0),
+                               (int32_t)k, out.data_ptr<int32_t>(), ws.data_ptr(), ws.numel(), stream(ref)),
+             "nngp_knn_query_nd");
+    return out;
+}
+
+// (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_nd(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    double sigma2, at::ArrayRef<double> phi, double tau2, const c10::optional<at::Tensor>& values, bool want_bf) {
+    check_coords_nd(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    check_phi_nd(phi, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool wr = values.has_value();
+    at::Tensor B = at::empty({want_bf ? rows : 0, m}, f64), F = at::empty({want_bf ? rows : 0}, f64);
+    at::Tensor R = at::empty({wr ? rows : 0}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_nd_workspace_bytes(rows, (int32_t)m, (int32_t)d), coords);
+    check_rc(nngp_bf_sweep_nd(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows,
+                              (int32_t)m, i0, (int32_t)kind, sigma2, phi.data(), tau2, ptr<double>(values),
+                              want_bf ? B.data_ptr<double>() : nullptr, want_bf ? F.data_ptr<double>() : nullptr,
+                              wr ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(), ws.data_ptr(),
+                              (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_nd");
+    return {B, F, R, p};
+}
+
+// (partials (4,), grad (dim + 2,) in (sigma2, phi_1..phi_dim, tau2), G (rows, dim + 2) or (0, dim + 2))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_nd(const at::Tensor& coords, const at::Tensor& nbr,
+                                                          const c10::optional<at::Tensor>& order, int64_t i0,
+                                                          int64_t kind, double sigma2, at::ArrayRef<double> phi,
+                                                          double tau2, const at::Tensor& values, bool want_rows) {
+    check_coords_nd(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    check_phi_nd(phi, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({d + 2}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, d + 2}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_nd_workspace_bytes(rows, (int32_t)m, (int32_t)d), coords);
+    check_rc(nngp_bf_grad_nd(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows,
+                             (int32_t)m, i0, (int32_t)kind, sigma2, phi.data(), tau2, values.data_ptr<double>(),
+                             want_rows ? G.data_ptr<double>() : nullptr, p.data_ptr<double>(), g.data_ptr<double>(),
+                             ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_grad_nd");
+    return {p, g, G};
+}
+
+// (B, F, kriging mean), as bf_cross
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_nd(const at::Tensor& ref, const at::Tensor& query,
+                                                           const at::Tensor& nbr, int64_t kind, double sigma2,
+                                                           at::ArrayRef<double> phi, double tau2,
+                                                           const c10::optional<at::Tensor>& ref_values) {
+    check_coords_nd(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords_nd(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    check_phi_nd(phi, ref);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    check_f64(ref_values, {ref.size(0)}, ref, "ref_values");
+    auto f64 = ref.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64), R = at::empty({rows}, f64);
+    at::Tensor p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_nd_workspace_bytes(rows, (int32_t)m, (int32_t)d), ref);
+    check_rc(nngp_bf_cross_nd(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(), query.size(0),
+                              nbr.data_ptr<int32_t>(), nullptr, rows, (int32_t)m, 0, (int32_t)kind, sigma2, phi.data(),
+                              tau2, ptr<double>(ref_values), nullptr, B.data_ptr<double>(), F.data_ptr<double>(),
+                              ref_values.has_value() ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(),
+                              ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_nd");
+    at::Tensor mean = ref_values.has_value() ? R.neg() : at::zeros({rows}, f64);
+    return {B, F, mean};
+}
+
 // the wave pair plan of a sweep over nbr (include/nngp.h nngp_pair_plan_build): (plan bytes on the GPU,
 // CPU int64 info).  A setup call: it synchronises the tensors' stream once.
 std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0,
@@ -1032,6 +1150,14 @@ TORCH_LIBRARY(nngp, m) {
           "float phi_s, float phi_t, float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_cross_sep(Tensor ref, Tensor query, Tensor nbr, int kind_s, int kind_t, float sigma2, float phi_s, "
           "float phi_t, float tau2, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
+    m.def("knn_prior_nd(Tensor coords, int m, int q0, int q1) -> Tensor");
+    m.def("knn_query_nd(Tensor ref, Tensor query, int k) -> Tensor");
+    m.def("bf_sweep_nd(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float[] phi, "
+          "float tau2, Tensor? values, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_grad_nd(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float[] phi, "
+          "float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_cross_nd(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float[] phi, float tau2, "
+          "Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
     m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
@@ -1054,6 +1180,11 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_sep", &bf_sweep_sep);
     m.impl("bf_grad_sep", &bf_grad_sep);
     m.impl("bf_cross_sep", &bf_cross_sep);
+    m.impl("knn_prior_nd", &knn_prior_nd);
+    m.impl("knn_query_nd", &knn_query_nd);
+    m.impl("bf_sweep_nd", &bf_sweep_nd);
+    m.impl("bf_grad_nd", &bf_grad_nd);
+    m.impl("bf_cross_nd", &bf_cross_nd);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

@@ -637,6 +637,16 @@ class NNGP:
     order: distinct, space-filling points (``('subset', nRef)`` draws with replacement).
     """
 
+    def __new__(cls, t=None, *args, **kw):
+        # ordinates of 4 .. 16 columns run on a second, self-contained path (pynngp_amd.nd.NNGPnd, a subclass whose
+        # own __init__ Python then calls); everything else is this class as before
+        if cls is NNGP:
+            from . import nd
+
+            if nd.is_nd_points(t) and np.shape(t)[1] <= _lib.ND_MAX_DIM:
+                return object.__new__(nd.NNGPnd)
+        return object.__new__(cls)
+
     def __init__(self, t, y, eps, refType, m, cov: CovLike, device=None, ordering=None):
         self.t = t  # ordinates (held by reference, nngp.py:7)
         self.y = y  # abscissae

@@ -33,6 +33,13 @@ for tracing.
         -> (partials, grad, G)                                         # grad (4,), G (rows, 4): sigma2, phi_s, phi_t, tau2
     torch.ops.nngp.bf_cross_sep(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values)
         -> (B, F, mean)                                                # bf_cross of that model
+    torch.ops.nngp.knn_prior_nd(coords, m, q0, q1) -> nbr              # 4 <= dim <= 16: exact, tiled brute force
+    torch.ops.nngp.knn_query_nd(ref, query, k) -> nbr
+    torch.ops.nngp.bf_sweep_nd(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
+        -> (B, F, R, partials)   # 4 <= dim <= 16, phi a list of dim decays (ARD); B, F empty without want_bf
+    torch.ops.nngp.bf_grad_nd(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
+        -> (partials, grad, G)   # grad (dim + 2,), G (rows, dim + 2): sigma2, phi_1..phi_dim, tau2
+    torch.ops.nngp.bf_cross_nd(ref, query, nbr, kind, sigma2, phi, tau2, ref_values) -> (B, F, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -191,6 +198,31 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_sep")
     def _(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("knn_prior_nd")
+    def _(coords, m, q0, q1):
+        return coords.new_empty((q1 - q0, m), dtype=torch.int32)
+
+    @fake("knn_query_nd")
+    def _(ref, query, k):
+        return ref.new_empty((query.shape[0], k), dtype=torch.int32)
+
+    @fake("bf_sweep_nd")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_grad_nd")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
+        d = coords.shape[1]
+        return (coords.new_empty((4,)), coords.new_empty((d + 2,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, d + 2)))
+
+    @fake("bf_cross_nd")
+    def _(ref, query, nbr, kind, sigma2, phi, tau2, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 
