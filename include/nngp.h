@@ -73,6 +73,8 @@ int32_t nngp_resolve_algo_nu(int32_t algo, int32_t m, int32_t kind, int32_t dim,
 #define NNGP_MAX_M 63
 #define NNGP_MAX_DIM 3
 #define NNGP_ND_MAX_DIM 16 /* the n-dimensional path (nngp_*_nd): 4 <= dim <= NNGP_ND_MAX_DIM */
+#define NNGP_MV_MAX_Q 4    /* the multivariate path (nngp_*_mv): 2 <= q <= NNGP_MV_MAX_Q outcomes, (m + 1) q <= 64 */
+#define NNGP_MV_MAX_COLS 8 /* ... and 1 <= c <= NNGP_MV_MAX_COLS value columns */
 
 /* Library version string, e.g. "pynngp_amd 0.3.0 gfx950". */
 const char *nngp_version(void);
@@ -309,6 +311,45 @@ int nngp_bf_grad_nd(const double *coords, int64_t n_points, int32_t dim, const i
                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2, const double *phi, double tau2,
                     const double *values, double *G, double *partials, double *grad, void *workspace,
                     size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Several outcomes per location under the linear model of coregionalisation (added within revision 4; nothing
+ * earlier moved).  q outcomes, 2 <= q <= NNGP_MV_MAX_Q, all observed at every point:
+ *   Cov(y_a(s), y_b(s')) = sum_k A[a][k] A[b][k] rho(phi[k] |s - s'|) + tau2[a] delta_ab delta_ss',
+ * A (q, q) row-major lower-triangular with a positive diagonal, phi (q,) > 0, tau2 (q,) >= 0: HOST arrays.  kind
+ * NNGP_COV_EXPONENTIAL, MATERN32, MATERN52 or GAUSSIAN, the same for every component.  coords, nbr, order, i0 and
+ * the -1 padding as nngp_bf_sweep_nd with 1 <= dim <= NNGP_MAX_DIM; the neighbour sets are those of nngp_knn_prior.
+ * Per location i, with the neighbours' q m values slot-major (slot 0's q outcomes first):
+ *   B  (n_rows, q, m q)  E[y_i | y_N] = B_i y_N; exactly 0 in the columns of a slot without a point
+ *   LF (n_rows, q, q)    the lower Cholesky factor of the conditional covariance F_i, zeros above the diagonal
+ *   E  (n_rows, q, c)    LF_i^-1 (V_i - B_i V_N) for each of the c columns of values (n_points, q, c),
+ *                        1 <= c <= NNGP_MV_MAX_COLS
+ *   partials[4]          sum_i 2 sum_a log LF_i[a][a], sum_i |E_i[:, 0]|^2, the first bad-pivot row or -1, the first
+ *                        bad-index row or -1, folded in a fixed order: bit-reproducible and independent of `order`.
+ *                        log-likelihood = -(n_rows q log 2 pi + partials[0] + partials[1]) / 2
+ * B, LF and E may each be NULL (a likelihood-only call skips the back-substitution that B needs); values may be NULL
+ * when E is (the value columns are then zeros).  An out-of-range index is flagged and masked like -1; a non-positive
+ * pivot is flagged and makes that location's outputs NaN.
+ *   nngp_bf_cross_mv: queries at arbitrary points with neighbours among the reference points (the contract of
+ *     nngp_bf_cross_nd).  target_noise != 0 adds tau2 to the q target rows (predicting y), 0 leaves it out (the
+ *     noiseless field).  `mean` (n_rows, q, c) receives the conditional mean B V_N per column of ref_values;
+ *     partials[1] is 0.
+ * Scope: m >= 1 and (m + 1) q <= 64, else NNGP_EUNSUP, as for q outside 2..4 and the spherical and general-nu kinds.
+ * NNGP_EINVAL for a non-finite or non-positive phi, a negative tau2, a non-positive diagonal of A, a non-zero above
+ * A's diagonal, c outside 1..NNGP_MV_MAX_COLS, a null pointer.
+ * workspace: nngp_bf_sweep_mv_workspace_bytes(n_rows, m, q) serves both (0 for unsupported arguments); 256-B aligned,
+ * no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_mv_workspace_bytes(int64_t n_rows, int32_t m, int32_t q);
+int nngp_bf_sweep_mv(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                     int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double *A, const double *phi,
+                     const double *tau2, const double *values, int32_t c, double *B, double *LF, double *E,
+                     double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_mv(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                     const int32_t *nbr, const int32_t *order, int64_t n_rows, int64_t q0, int32_t m, int32_t q,
+                     int32_t kind, const double *A, const double *phi, const double *tau2, int32_t target_noise,
+                     const double *ref_values, int32_t c, double *B, double *LF, double *mean, double *partials,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,

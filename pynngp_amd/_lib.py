@@ -8,6 +8,7 @@ tensor is not on a ROCm GPU: there is no CPU fallback for the hot path.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional, Tuple
 
@@ -84,6 +85,9 @@ SYMBOLS = (
     "nngp_bf_sweep_nd_workspace_bytes",
     "nngp_bf_sweep_nd",
     "nngp_bf_cross_nd",
+    "nngp_bf_sweep_mv_workspace_bytes",
+    "nngp_bf_sweep_mv",
+    "nngp_bf_cross_mv",
     "nngp_bf_grad_nd",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
@@ -222,6 +226,13 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_sweep_nd.restype = ctypes.c_int
     lib.nngp_bf_cross_nd.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, P, P, SZ, P]
     lib.nngp_bf_cross_nd.restype = ctypes.c_int
+    lib.nngp_bf_sweep_mv_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_sweep_mv_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_mv.argtypes = [P, I64, I32, P, P, I64, I64, I32, I32, I32, P, P, P, P, I32, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_mv.restype = ctypes.c_int
+    lib.nngp_bf_cross_mv.argtypes = [P, I64, I32, P, I64, P, P, I64, I64, I32, I32, I32, P, P, P, I32, P, I32, P, P, P,
+                                     P, P, SZ, P]
+    lib.nngp_bf_cross_mv.restype = ctypes.c_int
     lib.nngp_bf_grad_nd.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_nd.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
@@ -1510,6 +1521,111 @@ def bf_cross_nd(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind:
                                 _ptr(query_values), _ptr(B), _ptr(F), _ptr(R), _ptr(partials), _ptr(workspace),
                                 workspace.numel(), _stream(dev)), "nngp_bf_cross_nd")
     return B, F, R, partials
+
+
+MV_KINDS = ("exponential", "matern32", "matern52", "gaussian")
+MV_MAX_Q = 4
+MV_MAX_ROWS = 64
+MV_MAX_COLS = 8
+
+
+def _mv_checks(kind: str, m: int, A, phi, tau2):
+    """The scope of the multivariate sweeps (nngp_bf_*_mv) and their LMC parameters; returns ``(q, A, phi, tau2)``
+    with the three as C arrays."""
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in MV_KINDS:
+        raise NotImplementedError(f"the multivariate sweeps serve the kinds {MV_KINDS}, not {kind!r}")
+    A = [[float(x) for x in row] for row in A]
+    q = len(A)
+    if not 2 <= q <= MV_MAX_Q:
+        raise NotImplementedError(f"the multivariate sweeps serve 2 <= q <= {MV_MAX_Q} outcomes (q={q})")
+    if m < 1 or (m + 1) * q > MV_MAX_ROWS:
+        raise NotImplementedError(f"the multivariate sweeps serve m >= 1 and (m + 1) q <= {MV_MAX_ROWS} (m={m}, q={q})")
+    phi, tau2 = [float(x) for x in phi], [float(x) for x in tau2]
+    if any(len(row) != q for row in A) or len(phi) != q or len(tau2) != q:
+        raise ValueError(f"A must be ({q}, {q}), phi and tau2 ({q},)")
+    if not all(math.isfinite(x) for row in A for x in row) or not all(A[a][a] > 0.0 for a in range(q)):
+        raise ValueError("A must be finite with a positive diagonal")
+    if any(A[a][b] != 0.0 for a in range(q) for b in range(a + 1, q)):
+        raise ValueError("A must be lower-triangular")
+    if not all(math.isfinite(x) and x > 0.0 for x in phi):
+        raise ValueError("phi must be positive and finite")
+    if not all(math.isfinite(x) and x >= 0.0 for x in tau2):
+        raise ValueError("tau2 must be non-negative and finite")
+    flat = [x for row in A for x in row]
+    return q, (ctypes.c_double * (q * q))(*flat), (ctypes.c_double * q)(*phi), (ctypes.c_double * q)(*tau2)
+
+
+def _mv_values(values: Optional[torch.Tensor], n: int, q: int, name: str):
+    if values is None:
+        return None, 1
+    if values.dtype != torch.float64 or values.dim() != 3 or values.shape[:2] != (n, q) or \
+            not 1 <= values.shape[2] <= MV_MAX_COLS:
+        raise ValueError(f"{name} must be float64 ({n}, {q}, c), 1 <= c <= {MV_MAX_COLS}")
+    return values.contiguous(), values.shape[2]
+
+
+def bf_sweep_mv(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, A, phi, tau2,
+                values: Optional[torch.Tensor] = None, want_b: bool = True, want_lf: bool = True,
+                order: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """The multivariate (coregionalised) sweep ``nngp_bf_sweep_mv`` (include/nngp.h): q outcomes per point with
+    ``Cov(y_a(s), y_b(s')) = sum_k A[a][k] A[b][k] rho(phi[k] |s - s'|) + tau2[a] delta_ab delta_ss'``.  ``values`` is
+    float64 (N, q, c), column 0 the data.  Returns ``(B, LF, E, partials)``: B (rows, q, m q) or None, LF (rows, q, q)
+    or None, E (rows, q, c) or None without values.  2 <= q <= 4, m >= 1, (m + 1) q <= 64."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n, d = coords.shape
+    rows, m = nbr.shape
+    q, cA, cphi, ctau = _mv_checks(kind, m, A, phi, tau2)
+    values, c = _mv_values(values, n, q, "values")
+    dev = _require_gpu(coords, nbr, values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    need = lib.nngp_bf_sweep_mv_workspace_bytes(rows, m, q)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, q, m * q), dtype=torch.float64, device=dev) if want_b else None
+    LF = torch.empty((rows, q, q), dtype=torch.float64, device=dev) if want_lf else None
+    E = torch.empty((rows, q, c), dtype=torch.float64, device=dev) if values is not None else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_mv(_ptr(coords), n, d, _ptr(nbr), _ptr(order), rows, int(i0), m, q, KIND_CODES[kind], cA,
+                                cphi, ctau, _ptr(values), c, _ptr(B), _ptr(LF), _ptr(E), _ptr(partials),
+                                _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_sweep_mv")
+    return B, LF, E, partials
+
+
+def bf_cross_mv(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: str, A, phi, tau2,
+                ref_values: Optional[torch.Tensor] = None, target_noise: bool = True, q0: int = 0,
+                order: Optional[torch.Tensor] = None):
+    """The cross form ``nngp_bf_cross_mv``: queries at arbitrary points, neighbours among ``ref``.  ``target_noise``
+    adds tau2 to the target (predicting y) or leaves it out (the noiseless field).  Returns ``(B, LF, mean, partials)``
+    with mean (rows, q, c) = B V_N per column of ``ref_values`` (n_ref, q, c), or None without them."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    rows, m = nbr.shape
+    q, cA, cphi, ctau = _mv_checks(kind, m, A, phi, tau2)
+    ref_values, c = _mv_values(ref_values, ref.shape[0], q, "ref_values")
+    dev = _require_gpu(ref, query, nbr, ref_values, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    lib = load()
+    B = torch.empty((rows, q, m * q), dtype=torch.float64, device=dev)
+    LF = torch.empty((rows, q, q), dtype=torch.float64, device=dev)
+    mean = torch.empty((rows, q, c), dtype=torch.float64, device=dev) if ref_values is not None else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_mv_workspace_bytes(rows, m, q), dev)
+    _check(lib.nngp_bf_cross_mv(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order), rows,
+                                int(q0), m, q, KIND_CODES[kind], cA, cphi, ctau, int(bool(target_noise)),
+                                _ptr(ref_values), c, _ptr(B), _ptr(LF), _ptr(mean), _ptr(partials), _ptr(workspace),
+                                workspace.numel(), _stream(dev)), "nngp_bf_cross_mv")
+    return B, LF, mean, partials
 
 
 def joint_dist(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, qcoords: Optional[torch.Tensor] = None,

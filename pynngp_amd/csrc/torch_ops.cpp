@@ -666,6 +666,72 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_nd(const at::Tensor& ref
     return {B, F, mean};
 }
 
+// several outcomes per location (nngp_bf_sweep_mv): A (q, q), phi (q,), tau2 (q,) as flat float lists, values
+// (N, q, c).  (B (rows, q, m q), LF (rows, q, q), E (rows, q, c), partials (4,)); B empty without want_b, E empty
+// without values
+static int64_t check_mv(at::ArrayRef<double> A, at::ArrayRef<double> phi, at::ArrayRef<double> tau2) {
+    const int64_t q = (int64_t)phi.size();
+    TORCH_CHECK(q >= 2 && q <= NNGP_MV_MAX_Q && (int64_t)A.size() == q * q && (int64_t)tau2.size() == q,
+                "A must hold q * q, phi and tau2 q numbers, 2 <= q <= ", NNGP_MV_MAX_Q);
+    return q;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_mv(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    at::ArrayRef<double> A, at::ArrayRef<double> phi, at::ArrayRef<double> tau2,
+    const c10::optional<at::Tensor>& values, bool want_b) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t q = check_mv(A, phi, tau2);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    const int64_t c = values.has_value() && values->dim() == 3 ? values->size(2) : 1;
+    check_f64(values, {n, q, c}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool we = values.has_value();
+    at::Tensor B = at::empty({want_b ? rows : 0, q, m * q}, f64), LF = at::empty({rows, q, q}, f64);
+    at::Tensor E = at::empty({we ? rows : 0, q, c}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_mv_workspace_bytes(rows, (int32_t)m, (int32_t)q), coords);
+    check_rc(nngp_bf_sweep_mv(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows,
+                              i0, (int32_t)m, (int32_t)q, (int32_t)kind, A.data(), phi.data(), tau2.data(),
+                              ptr<double>(values), (int32_t)c, want_b ? B.data_ptr<double>() : nullptr,
+                              LF.data_ptr<double>(), we ? E.data_ptr<double>() : nullptr, p.data_ptr<double>(),
+                              ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_mv");
+    return {B, LF, E, p};
+}
+
+// (B, LF, conditional mean (rows, q, c)), as bf_cross
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_mv(const at::Tensor& ref, const at::Tensor& query,
+                                                           const at::Tensor& nbr, int64_t kind, at::ArrayRef<double> A,
+                                                           at::ArrayRef<double> phi, at::ArrayRef<double> tau2,
+                                                           bool target_noise,
+                                                           const c10::optional<at::Tensor>& ref_values) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t q = check_mv(A, phi, tau2);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    const int64_t c = ref_values.has_value() && ref_values->dim() == 3 ? ref_values->size(2) : 1;
+    check_f64(ref_values, {ref.size(0), q, c}, ref, "ref_values");
+    auto f64 = ref.options();
+    const bool wm = ref_values.has_value();
+    at::Tensor B = at::empty({rows, q, m * q}, f64), LF = at::empty({rows, q, q}, f64);
+    at::Tensor mean = wm ? at::empty({rows, q, c}, f64) : at::zeros({rows, q, c}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_mv_workspace_bytes(rows, (int32_t)m, (int32_t)q), ref);
+    check_rc(nngp_bf_cross_mv(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(), query.size(0),
+                              nbr.data_ptr<int32_t>(), nullptr, rows, 0, (int32_t)m, (int32_t)q, (int32_t)kind, A.data(),
+                              phi.data(), tau2.data(), target_noise ? 1 : 0, ptr<double>(ref_values), (int32_t)c,
+                              B.data_ptr<double>(), LF.data_ptr<double>(), wm ? mean.data_ptr<double>() : nullptr,
+                              p.data_ptr<double>(), ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_mv");
+    return {B, LF, mean};
+}
+
 // the wave pair plan of a sweep over nbr (include/nngp.h nngp_pair_plan_build): (plan bytes on the GPU,
 // CPU int64 info).  A setup call: it synchronises the tensors' stream once.
 std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0,
@@ -1158,6 +1224,10 @@ TORCH_LIBRARY(nngp, m) {
           "float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_cross_nd(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float[] phi, float tau2, "
           "Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_mv(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float[] A, float[] phi, "
+          "float[] tau2, Tensor? values, bool want_b) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_cross_mv(Tensor ref, Tensor query, Tensor nbr, int kind, float[] A, float[] phi, float[] tau2, "
+          "bool target_noise, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
     m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
@@ -1185,6 +1255,8 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_nd", &bf_sweep_nd);
     m.impl("bf_grad_nd", &bf_grad_nd);
     m.impl("bf_cross_nd", &bf_cross_nd);
+    m.impl("bf_sweep_mv", &bf_sweep_mv);
+    m.impl("bf_cross_mv", &bf_cross_mv);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

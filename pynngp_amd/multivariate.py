@@ -1,0 +1,231 @@
+"""Several correlated outcomes at the same sites: :class:`LMCCovariance` and :class:`MultivariateNNGP`.
+
+The model is the linear model of coregionalisation (spBayes' ``spMvLM``), q outcomes (2..4) all observed at every
+location::
+
+    Cov(y_a(s), y_b(s')) = sum_k A[a, k] A[b, k] rho(phi_k |s - s'|) + tau2_a delta_ab delta_ss'
+
+with A lower-triangular.  The conditioning sets are the ordinary prior neighbour sets on the coordinates (the
+components share one Euclidean metric), and the factors come from ``nngp_bf_sweep_mv`` / ``nngp_bf_cross_mv``: one
+wavefront per location, the joint block of (m + 1) q <= 64 rows factorised on the fp64 matrix instruction
+(DESIGN.md 4.3j).  There is no analytic gradient in the LMC parameters: :meth:`MultivariateNNGP.fit` differences
+the sweep.  Outcomes missing at some sites, a reference set other than the data, per-component kinds, per-point noise
+and the latent / Gibbs forms are not built.
+"""
+import dataclasses
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .nngp import LOG_2PI, Covariance, NNGPNumericalError, _default_device, _raise_on_bad
+
+
+@dataclasses.dataclass(frozen=True)
+class LMCCovariance:
+    """``kind`` one of exponential, matern32, matern52, gaussian (every component the same); ``A`` (q, q)
+    lower-triangular with a positive diagonal; ``phi`` (q,) > 0; ``tau2`` (q,) >= 0; 2 <= q <= 4.  Called as
+    ``cov(a, b)`` on host coordinate rows it returns the dense (n_a q, n_b q) cross-covariance, point-major (a point's
+    q outcomes adjacent), without the nugget."""
+
+    kind: str
+    A: tuple
+    phi: tuple
+    tau2: tuple
+
+    def __post_init__(self):
+        if self.kind not in _lib.KIND_CODES:
+            raise ValueError(f"unknown covariance kind {self.kind!r}")
+        if self.kind not in _lib.MV_KINDS:
+            raise NotImplementedError(f"LMCCovariance serves the kinds {_lib.MV_KINDS}, not {self.kind!r}")
+        A = np.array(self.A, dtype=np.float64)
+        phi = tuple(float(p) for p in np.ravel(self.phi))
+        tau2 = tuple(float(t) for t in np.ravel(self.tau2))
+        q = len(phi)
+        if not 2 <= q <= _lib.MV_MAX_Q:
+            raise NotImplementedError(f"LMCCovariance serves 2 <= q <= {_lib.MV_MAX_Q} outcomes (q={q})")
+        if A.shape != (q, q) or len(tau2) != q:
+            raise ValueError(f"A must be ({q}, {q}) and tau2 ({q},) for {q} decays")
+        if not np.all(np.isfinite(A)) or not np.all(np.diag(A) > 0):
+            raise ValueError("A must be finite with a positive diagonal")
+        if np.any(np.triu(A, 1) != 0):
+            raise ValueError("A must be lower-triangular")
+        if not all(p > 0 and math.isfinite(p) for p in phi):
+            raise ValueError(f"every phi_k must be positive and finite, got {phi}")
+        if not all(t >= 0 and math.isfinite(t) for t in tau2):
+            raise ValueError(f"every tau2_a must be non-negative and finite, got {tau2}")
+        object.__setattr__(self, "A", tuple(tuple(float(x) for x in row) for row in A))
+        object.__setattr__(self, "phi", phi)
+        object.__setattr__(self, "tau2", tau2)
+
+    @property
+    def q(self) -> int:
+        return len(self.phi)
+
+    @property
+    def theta(self):
+        """Flat: A's lower triangle row-major, phi, tau2."""
+        return (*(self.A[a][b] for a in range(self.q) for b in range(a + 1)), *self.phi, *self.tau2)
+
+    def replace(self, **kw) -> "LMCCovariance":
+        return dataclasses.replace(self, **kw)
+
+    def __call__(self, a, b):
+        a, b = np.atleast_2d(np.asarray(a, dtype=np.float64)), np.atleast_2d(np.asarray(b, dtype=np.float64))
+        A, q = np.array(self.A), self.q
+        out = np.zeros((a.shape[0], q, b.shape[0], q))
+        for k in range(q):
+            rho = Covariance(self.kind, 1.0, self.phi[k], 0.0)(a, b)
+            out += rho[:, None, :, None] * np.outer(A[:, k], A[:, k])[None, :, None, :]
+        return out.reshape(a.shape[0] * q, b.shape[0] * q)
+
+
+def _from_theta(kind: str, q: int, x) -> LMCCovariance:
+    """The optimiser's vector (A: log diagonal, raw below it, row-major; log phi; log tau2) as a covariance."""
+    A = np.zeros((q, q))
+    k = 0
+    for a in range(q):
+        for b in range(a + 1):
+            A[a, b] = math.exp(x[k]) if a == b else x[k]
+            k += 1
+    return LMCCovariance(kind, A, np.exp(x[k:k + q]), np.exp(x[k + q:k + 2 * q]))
+
+
+def _to_theta(cov: LMCCovariance) -> np.ndarray:
+    q = cov.q
+    x = [math.log(cov.A[a][b]) if a == b else cov.A[a][b] for a in range(q) for b in range(a + 1)]
+    return np.array(x + [math.log(p) for p in cov.phi] + [math.log(max(t, 1e-12)) for t in cov.tau2])
+
+
+class MultivariateNNGP:
+    """NNGP for ``Y`` (N, q) at the points ``t`` (N, 1..3) under an :class:`LMCCovariance`, ``(m + 1) q <= 64``.
+    ``ordering`` None, "random", "maxmin" or a permutation, as for :class:`NNGP`; rows are held in that order
+    (``perm`` maps positions to input rows)."""
+
+    def __init__(self, t, Y, m, cov: LMCCovariance, ordering=None, device=None):
+        if not isinstance(cov, LMCCovariance):
+            raise TypeError("cov must be an LMCCovariance")
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        t = t[:, None] if t.ndim == 1 else t
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if t.ndim != 2 or not 1 <= t.shape[1] <= _lib.MAX_DIM or Y.shape != (t.shape[0], cov.q):
+            raise ValueError(f"t must be (N, 1..{_lib.MAX_DIM}) and Y (N, {cov.q}), got {t.shape} and {Y.shape}")
+        if not (np.all(np.isfinite(t)) and np.all(np.isfinite(Y))):
+            raise ValueError("Input contains NaN or infinity")
+        self.m, self.cov, self.q = int(m), cov, cov.q
+        _lib._mv_checks(cov.kind, self.m, cov.A, cov.phi, cov.tau2)
+        self.device = _default_device(device)
+        self.perm = None
+        if ordering is not None:
+            from . import ordering as _ordering
+
+            self.perm = _ordering.resolve(ordering, torch.as_tensor(t).to(self.device))
+            t, Y = np.ascontiguousarray(t[self.perm]), np.ascontiguousarray(Y[self.perm])
+        self.t, self.Y = t, Y
+        self._t_dev = torch.as_tensor(t).to(self.device)
+        self._nbr = _lib.knn_prior(self._t_dev, self.m)
+        self._B = self._LF = None
+
+    def _sweep(self, cov, cols, want_b=False, want_lf=False):
+        """One sweep over every location with the value columns ``cols`` (N, q, c); raises on either flag."""
+        cov = self.cov if cov is None else cov
+        vals = torch.as_tensor(np.ascontiguousarray(cols)).to(self.device)
+        B, LF, E, p = _lib.bf_sweep_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals,
+                                       want_b=want_b, want_lf=want_lf)
+        ph = p.cpu().numpy()
+        _raise_on_bad(ph, cov)
+        return B, LF, E, ph
+
+    def loglik(self, cov=None, mean=None):
+        """The NNGP log-likelihood of Y.  ``mean`` None (zero), an array broadcastable to (N, q) in the instance's
+        row order, or "constant": a per-outcome GLS mean from one sweep over Y and the q indicator columns, whitened
+        together; then ``(loglik, mu)`` is returned."""
+        n, q = self.Y.shape
+        if isinstance(mean, str):
+            if mean != "constant":
+                raise ValueError(f"mean must be None, 'constant' or an array, got {mean!r}")
+            cols = np.zeros((n, q, 1 + q))
+            cols[:, :, 0] = self.Y
+            cols[:, np.arange(q), 1 + np.arange(q)] = 1.0
+            _, _, E, ph = self._sweep(cov, cols)
+            E = E.reshape(n * q, 1 + q)
+            G = (E.T @ E).cpu().numpy()  # [[y'y, y'X], [X'y, X'X]] in the whitened metric
+            mu = np.linalg.solve(G[1:, 1:], G[1:, 0])
+            quad = G[0, 0] - G[0, 1:] @ mu
+            return -0.5 * (n * q * LOG_2PI + ph[0] + quad), mu
+        resid = self.Y if mean is None else self.Y - np.broadcast_to(np.asarray(mean, dtype=np.float64), (n, q))
+        ph = self._sweep(cov, resid[:, :, None])[3]
+        return -0.5 * (n * q * LOG_2PI + ph[0] + ph[1])
+
+    def compute_BF(self, cov=None):
+        """B (N, q, m q) and LF (N, q, q) on the GPU (also the properties ``B`` and ``LF``)."""
+        self._B, self._LF, _, _ = self._sweep(cov, self.Y[:, :, None], want_b=True, want_lf=True)
+        return self._B, self._LF
+
+    @property
+    def B(self):
+        if self._B is None:
+            self.compute_BF()
+        return self._B
+
+    @property
+    def LF(self):
+        if self._LF is None:
+            self.compute_BF()
+        return self._LF
+
+    def predict(self, query, noise=True, cov=None, mean=None):
+        """Conditional mean (n_q, q) and covariance (n_q, q, q) at ``query`` given each point's m nearest data
+        points; ``noise`` False predicts the noiseless field.  ``mean`` (q,) is subtracted from Y and added back."""
+        cov = self.cov if cov is None else cov
+        query = np.ascontiguousarray(query, dtype=np.float64)
+        query = query[:, None] if query.ndim == 1 else query
+        qd = torch.as_tensor(query).to(self.device)
+        mu = np.zeros(self.q) if mean is None else np.asarray(mean, dtype=np.float64)
+        vals = torch.as_tensor(np.ascontiguousarray((self.Y - mu)[:, :, None])).to(self.device)
+        nbr = _lib.knn_query(self._t_dev, qd, self.m)
+        _, LF, pm, p = _lib.bf_cross_mv(self._t_dev, qd, nbr, cov.kind, cov.A, cov.phi, cov.tau2, vals,
+                                        target_noise=noise)
+        _raise_on_bad(p.cpu().numpy(), cov)
+        return pm[:, :, 0].cpu().numpy() + mu, (LF @ LF.transpose(1, 2)).cpu().numpy()
+
+    def fit(self, start=None, tol=1e-6, maxiter=200, step=1e-5):
+        """Maximum likelihood (zero mean) by L-BFGS-B on log diag A, raw off-diagonal A, log phi, log tau2, with
+        central differences of the sweep (2 (q (q + 1) / 2 + 2 q) sweeps per gradient: there is no analytic gradient
+        in the LMC parameters).  Sets and returns ``self.cov``; ``self.fit_result`` keeps scipy's result."""
+        from scipy import optimize
+
+        kind, q = self.cov.kind, self.q
+
+        def nll(x):
+            try:
+                return -self.loglik(_from_theta(kind, q, x))
+            except (NNGPNumericalError, ValueError, OverflowError):
+                return 1e300
+
+        def grad(x):
+            g = np.empty_like(x)
+            for k in range(x.size):
+                e = np.zeros_like(x)
+                e[k] = step
+                g[k] = (nll(x + e) - nll(x - e)) / (2.0 * step)
+            return g
+
+        x0 = _to_theta(self.cov if start is None else start)
+        self.fit_result = optimize.minimize(nll, x0, jac=grad, method="L-BFGS-B",
+                                            options={"maxiter": maxiter, "ftol": tol, "gtol": tol})
+        self.cov = _from_theta(kind, q, self.fit_result.x)
+        self._B = self._LF = None
+        return self.cov
+
+    def simulate(self, seed=0, cov=None):
+        """A sequential draw (N, q) from the NNGP prior of ``cov``, from B and LF on the host."""
+        B, LF, _, _ = self._sweep(cov, self.Y[:, :, None], want_b=True, want_lf=True)
+        B, LF, nbr = B.cpu().numpy(), LF.cpu().numpy(), self._nbr.cpu().numpy()
+        z = np.random.default_rng(seed).standard_normal(self.Y.shape)
+        out = np.zeros_like(self.Y)
+        for i in range(out.shape[0]):
+            yn = np.where(nbr[i, :, None] >= 0, out[np.maximum(nbr[i], 0)], 0.0).reshape(-1)
+            out[i] = B[i] @ yn + LF[i] @ z[i]
+        return out

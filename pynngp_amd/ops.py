@@ -40,6 +40,9 @@ for tracing.
     torch.ops.nngp.bf_grad_nd(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
         -> (partials, grad, G)   # grad (dim + 2,), G (rows, dim + 2): sigma2, phi_1..phi_dim, tau2
     torch.ops.nngp.bf_cross_nd(ref, query, nbr, kind, sigma2, phi, tau2, ref_values) -> (B, F, mean)
+    torch.ops.nngp.bf_sweep_mv(coords, nbr, order, i0, kind, A, phi, tau2, values, want_b)
+        -> (B, LF, E, partials)  # q outcomes per point (LMC): A q*q floats row-major, values (N, q, c); (m + 1) q <= 64
+    torch.ops.nngp.bf_cross_mv(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values) -> (B, LF, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -225,6 +228,19 @@ def _register_fakes() -> None:
     def _(ref, query, nbr, kind, sigma2, phi, tau2, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_mv")
+    def _(coords, nbr, order, i0, kind, A, phi, tau2, values, want_b):
+        (rows, m), q = nbr.shape, len(phi)
+        c = values.shape[2] if values is not None else 1
+        return (coords.new_empty((rows if want_b else 0, q, m * q)), coords.new_empty((rows, q, q)),
+                coords.new_empty((rows if values is not None else 0, q, c)), coords.new_empty((4,)))
+
+    @fake("bf_cross_mv")
+    def _(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values):
+        (rows, m), q = nbr.shape, len(phi)
+        c = ref_values.shape[2] if ref_values is not None else 1
+        return query.new_empty((rows, q, m * q)), query.new_empty((rows, q, q)), query.new_empty((rows, q, c))
 
     @fake("row_order")
     def _(coords, i0, rows, nbr):
