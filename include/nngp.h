@@ -352,6 +352,25 @@ int nngp_bf_cross_mv(const double *ref, int64_t n_ref, int32_t dim, const double
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The log-likelihood of the model above and its gradient in the LMC parameters, one fused sweep over locations
+ * i0 .. i0 + n_rows - 1 (added within revision 4; nothing earlier moved).  Arguments, scope and errors are those of
+ * nngp_bf_sweep_mv (S = T); values (n_points, q, 1) is required.  P = q (q + 1) / 2 + 2 q natural parameters in the
+ * order: A's lower triangle row-major (A[0][0], A[1][0], A[1][1], ...), phi[0..q), tau2[0..q).
+ *   partials[4]  as nngp_bf_sweep_mv, equal to that sweep's to its own tolerance
+ *   grad[P]      sum_i d l_i / d theta
+ *   G            NULL or (n_rows, P): the term of location i0 + r in row r (r = order[t] for nbr row t, else t)
+ * Both sums are folded over the locations in index order: bit-reproducible run to run and independent of `order`.
+ * A slot without a point adds exactly 0; a location flagged in partials[2] has NaN terms (in G and in grad).
+ * workspace: nngp_bf_grad_mv_workspace_bytes(n_rows, m, q) (0 for unsupported arguments; it exceeds the sweep's),
+ * 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_grad_mv_workspace_bytes(int64_t n_rows, int32_t m, int32_t q);
+int nngp_bf_grad_mv(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                    int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double *A, const double *phi,
+                    const double *tau2, const double *values, double *G, double *partials, double *grad,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,
  * order and i0 as nngp_bf_sweep).  With D_ab = sigma2 d_ab rho'(phi d_ab) and u = [-B_i; 1]:
  *   B  (n_rows, m), F (n_rows,): the factors of nngp_bf_sweep at this theta, equal to that sweep's to its own

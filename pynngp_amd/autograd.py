@@ -285,6 +285,67 @@ def loglik_ard(coords, nbr, kind, theta, values, order=None):
     return ll
 
 
+class _LogLikLmc(torch.autograd.Function):
+    """The multivariate (LMC) sweep (``torch.ops.nngp.bf_grad_mv``): A (q, q), phi (q,), tau2 (q,)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, A, phi, tau2, Y, kind, order):
+        from . import load_ops
+
+        load_ops()
+        q = phi.shape[0]
+        host = [[float(x) for x in t.detach().cpu().reshape(-1).tolist()] for t in (A, phi, tau2)]  # host synchronisation
+        p, g, _ = torch.ops.nngp.bf_grad_mv(coords, nbr, order, 0, _lib.KIND_CODES[kind], *host,
+                                            Y.detach().reshape(-1, q, 1).contiguous(), False)
+        ctx.save_for_backward(g)
+        ctx.meta = (q, A.device, phi.device, tau2.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * q * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        (g,) = ctx.saved_tensors
+        q, adev, pdev, tdev = ctx.meta
+        g = grad_out * g
+        ntq = q * (q + 1) // 2
+        gA = None
+        if ctx.needs_input_grad[2]:
+            low = torch.tril_indices(q, q, device=g.device)  # row-major: the order of the sweep's gradient
+            gA = torch.zeros((q, q), dtype=g.dtype, device=g.device).index_put((low[0], low[1]), g[:ntq]).to(adev)
+        gphi = g[ntq:ntq + q].to(pdev) if ctx.needs_input_grad[3] else None
+        gtau = g[ntq + q:].to(tdev) if ctx.needs_input_grad[4] else None
+        return None, None, gA, gphi, gtau, None, None, None
+
+
+def loglik_lmc(coords, nbr, kind, A, phi, tau2, Y, order=None):
+    """NNGP log-likelihood of ``Y`` (N, q) on S = T under the linear model of coregionalisation
+    (:class:`LMCCovariance`): ``A`` (q, q) lower-triangular, ``phi`` (q,) and ``tau2`` (q,) float64 tensors,
+    differentiable in all three (zeros above A's diagonal get zero gradient).
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_mv``) and synchronises with the host as :func:`loglik`
+    does; backward returns ``grad_out * grad`` with no further launch.  ``nbr`` (N, m) int32, 2 <= q <= 4,
+    (m + 1) q <= 64; kinds exponential, matern32, matern52, gaussian; the not-PD and bad-index flags raise.
+    """
+    if kind not in _lib.KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if any(t.dtype != torch.float64 for t in (A, phi, tau2)) or A.dim() != 2 or phi.dim() != 1 or \
+            A.shape != (phi.shape[0],) * 2 or tau2.shape != phi.shape:
+        raise ValueError("A must be a float64 (q, q) tensor, phi and tau2 float64 (q,)")
+    if nbr.dim() != 2:
+        raise ValueError("nbr must be int32 (N, m)")
+    _lib._mv_checks(kind, nbr.shape[1], A.detach().cpu().tolist(), phi.detach().cpu().tolist(),
+                    tau2.detach().cpu().tolist())
+    if nbr.shape[0] != coords.shape[0] or Y.shape != (coords.shape[0], phi.shape[0]):
+        raise ValueError("loglik_lmc is an S = T sweep: one nbr row and one row of Y (N, q) per location")
+    _lib._require_gpu(coords, nbr, Y, order)
+    ll, p = _LogLikLmc.apply(coords, nbr, A, phi, tau2, Y, kind, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 def loglik_matern(coords, nbr, theta, values, order=None):
     """NNGP log-likelihood of ``values`` on S = T under the general-smoothness Matern covariance at ``theta`` =
     (sigma2, phi, tau2, nu), a float64 (4,) tensor, differentiable in all four entries of ``theta`` and, when

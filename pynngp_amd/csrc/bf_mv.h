@@ -403,22 +403,28 @@ __global__ __launch_bounds__(64 * kMvWaves) void bf_mv(const double* __restrict_
                          lead && bad_index ? (double)i : INFINITY, rec, blk);
 }
 
-template <int Q, int NT>
-static bool launch_mv_if(const MvArgs& a, hipStream_t s) {
-    if (a.q != Q || mv_tiles(a.m, a.q) != NT) return false;
+// the kernels' parameters from the host arrays A (q, q) row-major, phi (q,), tau2 (q,)
+inline MvParams mv_params(int q, int kind, const double* A, const double* phi, const double* tau2) {
     MvParams P;
     P.dmin = INFINITY;
-    for (int k = 0; k < Q; ++k) {
-        double d = a.tau2[k];
-        for (int b = 0; b <= k; ++b) d += a.A[k * Q + b] * a.A[k * Q + b];
+    for (int k = 0; k < q; ++k) {
+        double d = tau2[k];
+        for (int b = 0; b <= k; ++b) d += A[k * q + b] * A[k * q + b];
         P.dmin = fmin(P.dmin, d);
     }
     P.pivmin = ldexp(P.dmin, -44);
     for (int k = 0; k < kMvMaxQ; ++k) {
-        P.pc[k] = nngp_cov_params(a.kind, 1.0, k < Q ? a.phi[k] : 1.0, 0.0);
-        P.tau2[k] = k < Q ? a.tau2[k] : 0.0;
-        for (int b = 0; b < kMvMaxQ; ++b) P.A[k][b] = (k < Q && b <= k) ? a.A[k * Q + b] : 0.0;
+        P.pc[k] = nngp_cov_params(kind, 1.0, k < q ? phi[k] : 1.0, 0.0);
+        P.tau2[k] = k < q ? tau2[k] : 0.0;
+        for (int b = 0; b < kMvMaxQ; ++b) P.A[k][b] = (k < q && b <= k) ? A[k * q + b] : 0.0;
     }
+    return P;
+}
+
+template <int Q, int NT>
+static bool launch_mv_if(const MvArgs& a, hipStream_t s) {
+    if (a.q != Q || mv_tiles(a.m, a.q) != NT) return false;
+    const MvParams P = mv_params(Q, a.kind, a.A, a.phi, a.tau2);
     hipLaunchKernelGGL((bf_mv<Q, NT>), dim3((unsigned)mv_blocks(a.n_rows)), dim3(64 * kMvWaves), 0, s, a.coords,
                        a.n_points, a.nbr, a.order, a.n_rows, a.i0, a.m, a.dim, P, a.values, a.qcoords, a.qvalues, a.c,
                        a.cross, a.target_noise, a.B, a.LF, a.E, a.rec);

@@ -1,0 +1,11 @@
+// bf_mv_grad<2, NT> for NT = 1..4 tile rows of neighbours (bf_mv_grad.h)
+#include "bf_mv_grad.h"
+
+namespace nngp {
+
+bool bf_mv_grad_launch_q2(const MvGradArgs& a, hipStream_t s) {
+    return launch_mv_grad_if<2, 1>(a, s) || launch_mv_grad_if<2, 2>(a, s) || launch_mv_grad_if<2, 3>(a, s) ||
+           launch_mv_grad_if<2, 4>(a, s);
+}
+
+}  // namespace nngp

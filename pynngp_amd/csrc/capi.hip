@@ -16,6 +16,7 @@
 #include "bf_sep.h"
 #include "bf_nd.h"
 #include "bf_mv.h"
+#include "bf_mv_grad.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -528,6 +529,25 @@ int nngp_bf_cross_mv(const double* ref, int64_t n_ref, int32_t dim, const double
     return mv_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, q0, m, q, kind, A, phi, tau2, 1,
                       target_noise != 0, ref_values, nullptr, c, B, LF, mean, partials, workspace, workspace_bytes,
                       stream);
+}
+
+size_t nngp_bf_grad_mv_workspace_bytes(int64_t n_rows, int32_t m, int32_t q) {
+    return nngp::mv_grad_workspace_bytes(n_rows, m, q);
+}
+
+int nngp_bf_grad_mv(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                    int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double* A, const double* phi,
+                    const double* tau2, const double* values, double* G, double* partials, double* grad,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    nngp::MvError err;
+    if (nngp::mv_grad_check(err, coords, n_points, dim, nbr, n_rows, m, q, i0, kind, A, phi, tau2, values, partials,
+                            grad, workspace, workspace_bytes) != NNGP_OK)
+        return fail(err.code, "%s", err.msg);
+    nngp::MvGradArgs a{coords, n_points, nbr, order, n_rows, i0, m, q, kind, dim, A, phi, tau2, values, G,
+                       (double*)workspace};
+    hipError_t e = nngp::bf_mv_grad_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_mv launch");
+    return NNGP_OK;
 }
 
 size_t nngp_bf_grad_aniso_workspace_bytes(int64_t n_rows, int32_t m, int32_t dim) {

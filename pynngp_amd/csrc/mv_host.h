@@ -33,6 +33,20 @@ inline size_t mv_workspace_bytes(int64_t n_rows, int m, int q) {
     return ((size_t)nb * 4 * sizeof(double) + 255) & ~(size_t)255;
 }
 
+// the gradient sweep (bf_mv_grad.h): P = q (q + 1) / 2 + 2 q parameters (A's lower triangle row-major, phi, tau2); a
+// record of 4 + P doubles per location, folded in chunks of kMvGradChunk locations (a record per chunk), each part
+// in 256-byte granules and at least one record; 0 outside the scope
+constexpr int mv_grad_len(int q) { return q * (q + 1) / 2 + 2 * q; }
+constexpr int kMvGradChunk = 1024;
+inline int64_t mv_grad_chunks(int64_t n_rows) { return (n_rows + kMvGradChunk - 1) / kMvGradChunk; }
+inline size_t mv_grad_rows_bytes(int64_t n_rows, int q) {
+    return ((size_t)(n_rows > 0 ? n_rows : 1) * (4 + mv_grad_len(q)) * sizeof(double) + 255) & ~(size_t)255;
+}
+inline size_t mv_grad_workspace_bytes(int64_t n_rows, int m, int q) {
+    if (!mv_scope(n_rows, m, q) || n_rows > ((int64_t)1 << 47)) return 0;
+    return mv_grad_rows_bytes(n_rows, q) + mv_grad_rows_bytes(mv_grad_chunks(n_rows), q);
+}
+
 struct MvError {
     int code = NNGP_OK;
     char msg[320] = "";
@@ -90,6 +104,21 @@ inline int mv_sweep_check(MvError& e, const void* coords, int64_t n_points, int 
     if (((uintptr_t)workspace & 255) != 0) return mv_fail(e, NNGP_EINVAL, "workspace must be 256-byte aligned");
     const size_t need = mv_workspace_bytes(n_rows, m, q);
     if (need == 0) return mv_fail(e, NNGP_EINVAL, "n_rows=%lld is too large", (long long)n_rows);
+    if (workspace_bytes < need)
+        return mv_fail(e, NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return NNGP_OK;
+}
+
+// nngp_bf_grad_mv: the sweep's checks (S = T, one value column), the pointers of its own and its larger workspace
+inline int mv_grad_check(MvError& e, const void* coords, int64_t n_points, int dim, const void* nbr, int64_t n_rows,
+                         int m, int q, int64_t i0, int kind, const double* A, const double* phi, const double* tau2,
+                         const void* values, const void* partials, const void* grad, const void* workspace,
+                         size_t workspace_bytes) {
+    if (mv_sweep_check(e, coords, n_points, dim, nbr, n_rows, m, q, i0, n_points, kind, A, phi, tau2, 1, partials,
+                       workspace, workspace_bytes) != NNGP_OK)
+        return e.code;
+    if (values == nullptr || grad == nullptr) return mv_fail(e, NNGP_EINVAL, "values and grad must be non-null");
+    const size_t need = mv_grad_workspace_bytes(n_rows, m, q);
     if (workspace_bytes < need)
         return mv_fail(e, NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
     return NNGP_OK;

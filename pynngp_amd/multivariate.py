@@ -8,8 +8,8 @@ location::
 with A lower-triangular.  The conditioning sets are the ordinary prior neighbour sets on the coordinates (the
 components share one Euclidean metric), and the factors come from ``nngp_bf_sweep_mv`` / ``nngp_bf_cross_mv``: one
 wavefront per location, the joint block of (m + 1) q <= 64 rows factorised on the fp64 matrix instruction
-(DESIGN.md 4.3j).  There is no analytic gradient in the LMC parameters: :meth:`MultivariateNNGP.fit` differences
-the sweep.  Outcomes missing at some sites, a reference set other than the data, per-component kinds, per-point noise
+(DESIGN.md 4.3j).  The analytic gradient in the LMC parameters is one more fused sweep, ``nngp_bf_grad_mv`` (DESIGN.md
+4.3k): :meth:`MultivariateNNGP.loglik_grad`, and ``fit(gradient=True)``; ``fit`` differences the sweep by default.  Outcomes missing at some sites, a reference set other than the data, per-component kinds, per-point noise
 and the latent / Gibbs forms are not built.
 """
 import dataclasses
@@ -158,6 +158,25 @@ class MultivariateNNGP:
         ph = self._sweep(cov, resid[:, :, None])[3]
         return -0.5 * (n * q * LOG_2PI + ph[0] + ph[1])
 
+    def loglik_grad(self, cov=None, mean=None):
+        """:meth:`loglik` and its gradient (P,) in ``cov.theta``'s order (A's lower triangle row-major, phi, tau2) from
+        one ``nngp_bf_grad_mv`` sweep: ``(loglik, grad)``.  ``mean`` as in :meth:`loglik`; for "constant" the GLS mean
+        comes from the whitening sweep and the gradient sweep runs on Y - mu: the gradient of the profile likelihood
+        (mu maximises it, so its own derivative drops out), returned as ``(loglik, mu, grad)``."""
+        cov = self.cov if cov is None else cov
+        n, q = self.Y.shape
+        mu = None
+        if isinstance(mean, str):
+            mu = self.loglik(cov, mean)[1]
+        resid = self.Y - (0.0 if mean is None else np.broadcast_to(np.asarray(mu if mu is not None else mean,
+                                                                              dtype=np.float64), (n, q)))
+        vals = torch.as_tensor(np.ascontiguousarray(resid[:, :, None])).to(self.device)
+        p, g, _ = _lib.bf_grad_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals)
+        ph = p.cpu().numpy()
+        _raise_on_bad(ph, cov)
+        ll, g = -0.5 * (n * q * LOG_2PI + ph[0] + ph[1]), g.cpu().numpy()
+        return (ll, g) if mu is None else (ll, mu, g)
+
     def compute_BF(self, cov=None):
         """B (N, q, m q) and LF (N, q, q) on the GPU (also the properties ``B`` and ``LF``)."""
         self._B, self._LF, _, _ = self._sweep(cov, self.Y[:, :, None], want_b=True, want_lf=True)
@@ -190,15 +209,38 @@ class MultivariateNNGP:
         _raise_on_bad(p.cpu().numpy(), cov)
         return pm[:, :, 0].cpu().numpy() + mu, (LF @ LF.transpose(1, 2)).cpu().numpy()
 
-    def fit(self, start=None, tol=1e-6, maxiter=200, step=1e-5):
+    def fit(self, start=None, tol=1e-6, maxiter=200, step=1e-5, gradient=False):
         """Maximum likelihood (zero mean) by L-BFGS-B on log diag A, raw off-diagonal A, log phi, log tau2, with
-        central differences of the sweep (2 (q (q + 1) / 2 + 2 q) sweeps per gradient: there is no analytic gradient
-        in the LMC parameters).  Sets and returns ``self.cov``; ``self.fit_result`` keeps scipy's result."""
+        central differences of the sweep (2 (q (q + 1) / 2 + 2 q) sweeps per gradient), or with ``gradient=True`` on
+        the analytic gradient: one :meth:`loglik_grad` sweep per evaluation gives the value and the gradient.  Sets and
+        returns ``self.cov``; ``self.fit_result`` keeps scipy's result and ``self.fit_sweeps`` the number of sweep
+        launches."""
         from scipy import optimize
 
         kind, q = self.cov.kind, self.q
+        self.fit_sweeps = 0
+
+        def value_and_grad(x):
+            self.fit_sweeps += 1
+            try:
+                cov = _from_theta(kind, q, x)
+                ll, g = self.loglik_grad(cov)
+            except (NNGPNumericalError, ValueError, OverflowError):
+                return 1e300, np.zeros_like(x)
+            # the optimiser's vector: x A_aa for log diag A, x phi_k, x tau2_a
+            scale = [cov.A[a][a] if a == b else 1.0 for a in range(q) for b in range(a + 1)]
+            return -ll, -g * np.array(scale + list(cov.phi) + list(cov.tau2))
+
+        if gradient:
+            x0 = _to_theta(self.cov if start is None else start)
+            self.fit_result = optimize.minimize(value_and_grad, x0, jac=True, method="L-BFGS-B",
+                                                options={"maxiter": maxiter, "ftol": tol, "gtol": tol})
+            self.cov = _from_theta(kind, q, self.fit_result.x)
+            self._B = self._LF = None
+            return self.cov
 
         def nll(x):
+            self.fit_sweeps += 1
             try:
                 return -self.loglik(_from_theta(kind, q, x))
             except (NNGPNumericalError, ValueError, OverflowError):

@@ -43,6 +43,8 @@ for tracing.
     torch.ops.nngp.bf_sweep_mv(coords, nbr, order, i0, kind, A, phi, tau2, values, want_b)
         -> (B, LF, E, partials)  # q outcomes per point (LMC): A q*q floats row-major, values (N, q, c); (m + 1) q <= 64
     torch.ops.nngp.bf_cross_mv(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values) -> (B, LF, mean)
+    torch.ops.nngp.bf_grad_mv(coords, nbr, order, i0, kind, A, phi, tau2, values, want_rows)
+        -> (partials, grad, G)   # grad (P,), G (rows, P), P = q (q + 1) / 2 + 2 q: A's lower triangle, phi, tau2
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -235,6 +237,12 @@ def _register_fakes() -> None:
         c = values.shape[2] if values is not None else 1
         return (coords.new_empty((rows if want_b else 0, q, m * q)), coords.new_empty((rows, q, q)),
                 coords.new_empty((rows if values is not None else 0, q, c)), coords.new_empty((4,)))
+
+    @fake("bf_grad_mv")
+    def _(coords, nbr, order, i0, kind, A, phi, tau2, values, want_rows):
+        npar = len(phi) * (len(phi) + 1) // 2 + 2 * len(phi)
+        return (coords.new_empty((4,)), coords.new_empty((npar,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, npar)))
 
     @fake("bf_cross_mv")
     def _(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values):
