@@ -352,6 +352,44 @@ int nngp_bf_cross_mv(const double *ref, int64_t n_ref, int32_t dim, const double
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The model above with outcomes missing at some sites (added within revision 4; nothing earlier moved).  obs
+ * (n_points,) uint8 on the device: bit a of obs[p] is set iff outcome a is observed at point p (bits q.. are ignored).
+ * Only observed (point, outcome) rows enter a location's joint block, packed: the block has as many neighbour rows as
+ * its neighbours have set bits, n_N, not m q.  Entries of `values` under a clear bit are never read.  rows_max is the
+ * caller's bound on n_N over the swept rows, 1 <= rows_max <= 64.  Arguments otherwise as nngp_bf_sweep_mv /
+ * nngp_bf_cross_mv; outputs in their shapes:
+ *   B  (n_rows, q, m q)  slot-major; exactly 0 in the column of a row that is not observed, in the columns of a slot
+ *                        without a point and in the row of a target outcome that is not observed
+ *   LF (n_rows, q, q)    the lower Cholesky factor over the target's observed outcomes, zeros in the row and the column
+ *                        of one that is not observed
+ *   E  (n_rows, q, c)    the whitened residuals of the observed target outcomes, 0 in the rows of the others
+ *   partials[4]          as nngp_bf_sweep_mv, over the observed target outcomes; folded from one record per location in
+ *                        location order: bit-reproducible and independent of `order`.
+ *                        log-likelihood = -(n_obs log 2 pi + partials[0] + partials[1]) / 2, n_obs the number of set
+ *                        bits over the swept locations
+ * A location with no observed neighbour row has F = C_tt.  A location whose n_N exceeds 16 ceil(rows_max / 16) keeps
+ * the longest prefix of its slots that fits, masks the others like -1 and is reported in partials[3] like an
+ * out-of-range index.
+ *   nngp_bf_cross_mv_obs: obs describes the reference points; every outcome of a query is computed.
+ * Scope: 1 <= m <= 63, 1 <= rows_max <= 64, else NNGP_EUNSUP, as for q outside 2..4 and the spherical and general-nu
+ * kinds.  NNGP_EINVAL as nngp_bf_sweep_mv, and for a null obs.
+ * workspace: nngp_bf_sweep_mv_obs_workspace_bytes(n_rows, m, q) serves both (0 for unsupported arguments; a record
+ * per location, larger than nngp_bf_sweep_mv's); 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_mv_obs_workspace_bytes(int64_t n_rows, int32_t m, int32_t q);
+int nngp_bf_sweep_mv_obs(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                         int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double *A,
+                         const double *phi, const double *tau2, const double *values, int32_t c, const uint8_t *obs,
+                         int32_t rows_max, double *B, double *LF, double *E, double *partials, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int nngp_bf_cross_mv_obs(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                         const int32_t *nbr, const int32_t *order, int64_t n_rows, int64_t q0, int32_t m, int32_t q,
+                         int32_t kind, const double *A, const double *phi, const double *tau2, int32_t target_noise,
+                         const double *ref_values, int32_t c, const uint8_t *obs, int32_t rows_max, double *B,
+                         double *LF, double *mean, double *partials, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------
  * The log-likelihood of the model above and its gradient in the LMC parameters, one fused sweep over locations
  * i0 .. i0 + n_rows - 1 (added within revision 4; nothing earlier moved).  Arguments, scope and errors are those of
  * nngp_bf_sweep_mv (S = T); values (n_points, q, 1) is required.  P = q (q + 1) / 2 + 2 q natural parameters in the

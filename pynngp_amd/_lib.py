@@ -90,6 +90,9 @@ SYMBOLS = (
     "nngp_bf_cross_mv",
     "nngp_bf_grad_mv_workspace_bytes",
     "nngp_bf_grad_mv",
+    "nngp_bf_sweep_mv_obs_workspace_bytes",
+    "nngp_bf_sweep_mv_obs",
+    "nngp_bf_cross_mv_obs",
     "nngp_bf_grad_nd",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
@@ -239,6 +242,14 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_grad_mv_workspace_bytes.restype = SZ
     lib.nngp_bf_grad_mv.argtypes = [P, I64, I32, P, P, I64, I64, I32, I32, I32, P, P, P, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_mv.restype = ctypes.c_int
+    lib.nngp_bf_sweep_mv_obs_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_sweep_mv_obs_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_mv_obs.argtypes = [P, I64, I32, P, P, I64, I64, I32, I32, I32, P, P, P, P, I32, P, I32, P, P, P, P,
+                                         P, SZ, P]
+    lib.nngp_bf_sweep_mv_obs.restype = ctypes.c_int
+    lib.nngp_bf_cross_mv_obs.argtypes = [P, I64, I32, P, I64, P, P, I64, I64, I32, I32, I32, P, P, P, I32, P, I32, P, I32,
+                                         P, P, P, P, P, SZ, P]
+    lib.nngp_bf_cross_mv_obs.restype = ctypes.c_int
     lib.nngp_bf_grad_nd.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_nd.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
@@ -1666,6 +1677,95 @@ def bf_grad_mv(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, A, p
                                cphi, ctau, _ptr(values), _ptr(G), _ptr(partials), _ptr(grad), _ptr(workspace),
                                workspace.numel(), _stream(dev)), "nngp_bf_grad_mv")
     return partials, grad, G
+
+
+MV_OBS_MAX_M = 63
+
+
+def _mv_obs_checks(kind: str, m: int, A, phi, tau2, obs, n: int, rows_max: int):
+    """The scope of the packed-row sweeps (nngp_bf_*_mv_obs): the LMC parameters as :func:`_mv_checks` (which is
+    asked about m = 1: the bound on m here is on the slots, not on (m + 1) q), 1 <= m <= 63, 1 <= rows_max <= 64."""
+    if not 1 <= m <= MV_OBS_MAX_M:
+        raise NotImplementedError(f"the packed-row multivariate sweeps serve 1 <= m <= {MV_OBS_MAX_M} (m={m})")
+    if not 1 <= int(rows_max) <= MV_MAX_ROWS:
+        raise NotImplementedError(f"the packed-row multivariate sweeps serve 1 <= rows_max <= {MV_MAX_ROWS} observed "
+                                  f"neighbour rows per location (rows_max={rows_max})")
+    if obs is None or obs.dtype != torch.uint8 or obs.shape != (n,):
+        raise ValueError(f"obs must be uint8 ({n},)")
+    return _mv_checks(kind, 1, A, phi, tau2)
+
+
+def mv_obs_rows(nbr: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+    """The observed neighbour rows of every row of ``nbr`` (rows,): gather, popcount, row sum (-1 and out-of-range
+    slots count 0).  Its maximum is the ``rows_max`` of :func:`bf_sweep_mv_obs`."""
+    pop = torch.tensor([bin(v & 15).count("1") for v in range(256)], dtype=torch.int64, device=obs.device)[obs.long()]
+    ok = (nbr >= 0) & (nbr < obs.shape[0])
+    return (pop[nbr.long().clamp(0, obs.shape[0] - 1)] * ok).sum(1)
+
+
+def bf_sweep_mv_obs(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, A, phi, tau2, obs: torch.Tensor,
+                    rows_max: int, values: Optional[torch.Tensor] = None, want_b: bool = True, want_lf: bool = True,
+                    order: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep_mv` with outcomes missing at some sites (``nngp_bf_sweep_mv_obs``): ``obs`` uint8 (N,), bit a
+    set iff outcome a is observed at that point; entries of ``values`` under a clear bit are never read (they may be
+    NaN).  ``rows_max`` bounds the observed neighbour rows of a location (:func:`mv_obs_rows`), at most 64; 1 <= m <=
+    63.  Returns ``(B, LF, E, partials)`` in :func:`bf_sweep_mv`'s shapes, zeros where a row is not observed."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n, d = coords.shape
+    rows, m = nbr.shape
+    q, cA, cphi, ctau = _mv_obs_checks(kind, m, A, phi, tau2, obs, n, rows_max)
+    values, c = _mv_values(values, n, q, "values")
+    dev = _require_gpu(coords, nbr, values, order, obs)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    obs = obs.contiguous()
+    lib = load()
+    need = lib.nngp_bf_sweep_mv_obs_workspace_bytes(rows, m, q)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, q, m * q), dtype=torch.float64, device=dev) if want_b else None
+    LF = torch.empty((rows, q, q), dtype=torch.float64, device=dev) if want_lf else None
+    E = torch.empty((rows, q, c), dtype=torch.float64, device=dev) if values is not None else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_mv_obs(_ptr(coords), n, d, _ptr(nbr), _ptr(order), rows, int(i0), m, q, KIND_CODES[kind],
+                                    cA, cphi, ctau, _ptr(values), c, _ptr(obs), int(rows_max), _ptr(B), _ptr(LF),
+                                    _ptr(E), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_sweep_mv_obs")
+    return B, LF, E, partials
+
+
+def bf_cross_mv_obs(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: str, A, phi, tau2,
+                    obs: torch.Tensor, rows_max: int, ref_values: Optional[torch.Tensor] = None,
+                    target_noise: bool = True, q0: int = 0, order: Optional[torch.Tensor] = None):
+    """:func:`bf_cross_mv` with ``obs`` (n_ref,) describing the reference points (``nngp_bf_cross_mv_obs``): every
+    outcome of a query is predicted from its neighbours' observed outcomes only."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    rows, m = nbr.shape
+    q, cA, cphi, ctau = _mv_obs_checks(kind, m, A, phi, tau2, obs, ref.shape[0], rows_max)
+    ref_values, c = _mv_values(ref_values, ref.shape[0], q, "ref_values")
+    dev = _require_gpu(ref, query, nbr, ref_values, order, obs)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    obs = obs.contiguous()
+    lib = load()
+    B = torch.empty((rows, q, m * q), dtype=torch.float64, device=dev)
+    LF = torch.empty((rows, q, q), dtype=torch.float64, device=dev)
+    mean = torch.empty((rows, q, c), dtype=torch.float64, device=dev) if ref_values is not None else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_mv_obs_workspace_bytes(rows, m, q), dev)
+    _check(lib.nngp_bf_cross_mv_obs(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order),
+                                    rows, int(q0), m, q, KIND_CODES[kind], cA, cphi, ctau, int(bool(target_noise)),
+                                    _ptr(ref_values), c, _ptr(obs), int(rows_max), _ptr(B), _ptr(LF), _ptr(mean),
+                                    _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_cross_mv_obs")
+    return B, LF, mean, partials
 
 
 def joint_dist(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, qcoords: Optional[torch.Tensor] = None,

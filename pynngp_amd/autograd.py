@@ -339,6 +339,9 @@ def loglik_lmc(coords, nbr, kind, A, phi, tau2, Y, order=None):
     if nbr.shape[0] != coords.shape[0] or Y.shape != (coords.shape[0], phi.shape[0]):
         raise ValueError("loglik_lmc is an S = T sweep: one nbr row and one row of Y (N, q) per location")
     _lib._require_gpu(coords, nbr, Y, order)
+    if bool(torch.isnan(Y).any()):
+        raise NotImplementedError("loglik_lmc is not built for outcomes missing at some sites (NaN in Y): the gradient "
+                                  "sweep serves full Y only; MultivariateNNGP.loglik serves the packed-row sweep")
     ll, p = _LogLikLmc.apply(coords, nbr, A, phi, tau2, Y, kind, order)
     from .nngp import _raise_on_bad
 

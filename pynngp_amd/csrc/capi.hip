@@ -17,6 +17,7 @@
 #include "bf_nd.h"
 #include "bf_mv.h"
 #include "bf_mv_grad.h"
+#include "bf_mv_obs.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -529,6 +530,51 @@ int nngp_bf_cross_mv(const double* ref, int64_t n_ref, int32_t dim, const double
     return mv_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, q0, m, q, kind, A, phi, tau2, 1,
                       target_noise != 0, ref_values, nullptr, c, B, LF, mean, partials, workspace, workspace_bytes,
                       stream);
+}
+
+// ---------------------------------------------------------------- outcomes missing at some sites (bf_mv_obs.h)
+// the checks live in mv_obs_host.h (no HIP in it)
+size_t nngp_bf_sweep_mv_obs_workspace_bytes(int64_t n_rows, int32_t m, int32_t q) {
+    return nngp::mv_obs_workspace_bytes(n_rows, m, q);
+}
+
+static int mv_obs_forward(const double* coords, int64_t n_points, int32_t dim, const double* qcoords, int64_t n_locs,
+                          const int32_t* nbr, const int32_t* order, int64_t n_rows, int64_t i0, int32_t m, int32_t q,
+                          int32_t kind, const double* A, const double* phi, const double* tau2, int cross,
+                          int target_noise, const double* values, const double* qvalues, int32_t c,
+                          const uint8_t* obs, int32_t rows_max, double* B, double* LF, double* E, double* partials,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    nngp::MvError err;
+    if (nngp::mv_obs_check(err, coords, n_points, dim, nbr, n_rows, m, q, i0, n_locs, kind, A, phi, tau2, c, obs,
+                           rows_max, partials, workspace, workspace_bytes) != NNGP_OK)
+        return fail(err.code, "%s", err.msg);
+    if (qcoords == nullptr) return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (E != nullptr && values == nullptr) return fail(NNGP_EINVAL, "E needs values");
+    nngp::MvObsArgs a{{coords, n_points, nbr, order, n_rows, i0, m, q, kind, dim, A, phi, tau2, values, qcoords,
+                       qvalues, c, cross, target_noise, B, LF, E, (double*)workspace}, obs, rows_max};
+    hipError_t e = nngp::bf_mv_obs_launch(a, partials, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_mv_obs launch");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_mv_obs(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                         int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double* A,
+                         const double* phi, const double* tau2, const double* values, int32_t c, const uint8_t* obs,
+                         int32_t rows_max, double* B, double* LF, double* E, double* partials, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return mv_obs_forward(coords, n_points, dim, coords, n_points, nbr, order, n_rows, i0, m, q, kind, A, phi, tau2, 0,
+                          1, values, values, c, obs, rows_max, B, LF, E, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_cross_mv_obs(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,
+                         const int32_t* nbr, const int32_t* order, int64_t n_rows, int64_t q0, int32_t m, int32_t q,
+                         int32_t kind, const double* A, const double* phi, const double* tau2, int32_t target_noise,
+                         const double* ref_values, int32_t c, const uint8_t* obs, int32_t rows_max, double* B,
+                         double* LF, double* mean, double* partials, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    return mv_obs_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, q0, m, q, kind, A, phi, tau2, 1,
+                          target_noise != 0, ref_values, nullptr, c, obs, rows_max, B, LF, mean, partials, workspace,
+                          workspace_bytes, stream);
 }
 
 size_t nngp_bf_grad_mv_workspace_bytes(int64_t n_rows, int32_t m, int32_t q) {

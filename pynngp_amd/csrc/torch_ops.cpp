@@ -758,6 +758,74 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_mv(const at::Tensor& ref
     return {B, LF, mean};
 }
 
+// outcomes missing at some sites (nngp_bf_sweep_mv_obs): as bf_sweep_mv with obs (N,) uint8 (bit a: outcome a observed)
+// and rows_max, the caller's bound on the observed neighbour rows of a location
+static void check_obs(const at::Tensor& obs, int64_t n, const at::Tensor& like) {
+    TORCH_CHECK(obs.scalar_type() == at::kByte && obs.dim() == 1 && obs.size(0) == n && obs.is_contiguous(),
+                "obs must be a contiguous uint8 tensor of shape (", n, ",)");
+    check_same_device(like, obs, "obs");
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_mv_obs(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    at::ArrayRef<double> A, at::ArrayRef<double> phi, at::ArrayRef<double> tau2,
+    const c10::optional<at::Tensor>& values, const at::Tensor& obs, int64_t rows_max, bool want_b) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t q = check_mv(A, phi, tau2);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    const int64_t c = values.has_value() && values->dim() == 3 ? values->size(2) : 1;
+    check_f64(values, {n, q, c}, coords, "values");
+    check_order(order, rows, coords);
+    check_obs(obs, n, coords);
+    auto f64 = coords.options();
+    const bool we = values.has_value();
+    at::Tensor B = at::empty({want_b ? rows : 0, q, m * q}, f64), LF = at::empty({rows, q, q}, f64);
+    at::Tensor E = at::empty({we ? rows : 0, q, c}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_mv_obs_workspace_bytes(rows, (int32_t)m, (int32_t)q), coords);
+    check_rc(nngp_bf_sweep_mv_obs(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order),
+                                  rows, i0, (int32_t)m, (int32_t)q, (int32_t)kind, A.data(), phi.data(), tau2.data(),
+                                  ptr<double>(values), (int32_t)c, obs.data_ptr<uint8_t>(), (int32_t)rows_max,
+                                  want_b ? B.data_ptr<double>() : nullptr, LF.data_ptr<double>(),
+                                  we ? E.data_ptr<double>() : nullptr, p.data_ptr<double>(), ws.data_ptr(),
+                                  (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_mv_obs");
+    return {B, LF, E, p};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_mv_obs(const at::Tensor& ref, const at::Tensor& query,
+                                                               const at::Tensor& nbr, int64_t kind,
+                                                               at::ArrayRef<double> A, at::ArrayRef<double> phi,
+                                                               at::ArrayRef<double> tau2, bool target_noise,
+                                                               const c10::optional<at::Tensor>& ref_values,
+                                                               const at::Tensor& obs, int64_t rows_max) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t q = check_mv(A, phi, tau2);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    const int64_t c = ref_values.has_value() && ref_values->dim() == 3 ? ref_values->size(2) : 1;
+    check_f64(ref_values, {ref.size(0), q, c}, ref, "ref_values");
+    check_obs(obs, ref.size(0), ref);
+    auto f64 = ref.options();
+    const bool wm = ref_values.has_value();
+    at::Tensor B = at::empty({rows, q, m * q}, f64), LF = at::empty({rows, q, q}, f64);
+    at::Tensor mean = wm ? at::empty({rows, q, c}, f64) : at::zeros({rows, q, c}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_mv_obs_workspace_bytes(rows, (int32_t)m, (int32_t)q), ref);
+    check_rc(nngp_bf_cross_mv_obs(ref.data_ptr<double>(), ref.size(0), (int32_t)d, query.data_ptr<double>(),
+                                  query.size(0), nbr.data_ptr<int32_t>(), nullptr, rows, 0, (int32_t)m, (int32_t)q,
+                                  (int32_t)kind, A.data(), phi.data(), tau2.data(), target_noise ? 1 : 0,
+                                  ptr<double>(ref_values), (int32_t)c, obs.data_ptr<uint8_t>(), (int32_t)rows_max,
+                                  B.data_ptr<double>(), LF.data_ptr<double>(), wm ? mean.data_ptr<double>() : nullptr,
+                                  p.data_ptr<double>(), ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_mv_obs");
+    return {B, LF, mean};
+}
+
 // the wave pair plan of a sweep over nbr (include/nngp.h nngp_pair_plan_build): (plan bytes on the GPU,
 // CPU int64 info).  A setup call: it synchronises the tensors' stream once.
 std::tuple<at::Tensor, at::Tensor> pair_plan(const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0,
@@ -1254,6 +1322,10 @@ TORCH_LIBRARY(nngp, m) {
           "float[] tau2, Tensor? values, bool want_b) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("bf_cross_mv(Tensor ref, Tensor query, Tensor nbr, int kind, float[] A, float[] phi, float[] tau2, "
           "bool target_noise, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_mv_obs(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float[] A, float[] phi, "
+          "float[] tau2, Tensor? values, Tensor obs, int rows_max, bool want_b) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_cross_mv_obs(Tensor ref, Tensor query, Tensor nbr, int kind, float[] A, float[] phi, float[] tau2, "
+          "bool target_noise, Tensor? ref_values, Tensor obs, int rows_max) -> (Tensor, Tensor, Tensor)");
     m.def("bf_grad_mv(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float[] A, float[] phi, "
           "float[] tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
@@ -1286,6 +1358,8 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_mv", &bf_sweep_mv);
     m.impl("bf_cross_mv", &bf_cross_mv);
     m.impl("bf_grad_mv", &bf_grad_mv);
+    m.impl("bf_sweep_mv_obs", &bf_sweep_mv_obs);
+    m.impl("bf_cross_mv_obs", &bf_cross_mv_obs);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

@@ -9,8 +9,13 @@ with A lower-triangular.  The conditioning sets are the ordinary prior neighbour
 components share one Euclidean metric), and the factors come from ``nngp_bf_sweep_mv`` / ``nngp_bf_cross_mv``: one
 wavefront per location, the joint block of (m + 1) q <= 64 rows factorised on the fp64 matrix instruction
 (DESIGN.md 4.3j).  The analytic gradient in the LMC parameters is one more fused sweep, ``nngp_bf_grad_mv`` (DESIGN.md
-4.3k): :meth:`MultivariateNNGP.loglik_grad`, and ``fit(gradient=True)``; ``fit`` differences the sweep by default.  Outcomes missing at some sites, a reference set other than the data, per-component kinds, per-point noise
-and the latent / Gibbs forms are not built.
+4.3k): :meth:`MultivariateNNGP.loglik_grad`, and ``fit(gradient=True)``; ``fit`` differences the sweep by default.
+
+Outcomes missing at some sites (NaN in ``Y``; co-kriging, spBayes' ``spMisalignLM``) run on the packed-row sweep
+``nngp_bf_sweep_mv_obs`` / ``nngp_bf_cross_mv_obs``: a location conditions on its neighbours'
+*observed* outcomes only, at most 64 of them over m <= 63 neighbour sites; :meth:`MultivariateNNGP.impute` predicts the
+missing entries.  A reference set other than the data, per-component kinds, per-point noise and the latent / Gibbs
+forms are not built.
 """
 import dataclasses
 import math
@@ -101,9 +106,15 @@ def _to_theta(cov: LMCCovariance) -> np.ndarray:
 class MultivariateNNGP:
     """NNGP for ``Y`` (N, q) at the points ``t`` (N, 1..3) under an :class:`LMCCovariance`, ``(m + 1) q <= 64``.
     ``ordering`` None, "random", "maxmin" or a permutation, as for :class:`NNGP`; rows are held in that order
-    (``perm`` maps positions to input rows)."""
+    (``perm`` maps positions to input rows).
 
-    def __init__(self, t, Y, m, cov: LMCCovariance, ordering=None, device=None):
+    NaN in ``Y`` means "not observed" (``self.obs`` (N,) uint8 holds the masks, bit a for outcome a).  Such an
+    instance serves ``m <= 63`` and at most 64 observed neighbour rows per location; ``loglik``, ``compute_BF``,
+    ``predict``, ``fit()`` and :meth:`impute` work on it, the gradient sweep and ``simulate`` do not yet.  ``nbr``
+    (N, m) int32, -1 padded, replaces the m nearest prior sites as the conditioning sets (indices in the instance's
+    row order, every entry below its row), e.g. with sets chosen per outcome."""
+
+    def __init__(self, t, Y, m, cov: LMCCovariance, ordering=None, device=None, nbr=None):
         if not isinstance(cov, LMCCovariance):
             raise TypeError("cov must be an LMCCovariance")
         t = np.ascontiguousarray(t, dtype=np.float64)
@@ -111,10 +122,13 @@ class MultivariateNNGP:
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         if t.ndim != 2 or not 1 <= t.shape[1] <= _lib.MAX_DIM or Y.shape != (t.shape[0], cov.q):
             raise ValueError(f"t must be (N, 1..{_lib.MAX_DIM}) and Y (N, {cov.q}), got {t.shape} and {Y.shape}")
-        if not (np.all(np.isfinite(t)) and np.all(np.isfinite(Y))):
+        if not (np.all(np.isfinite(t)) and not np.any(np.isinf(Y))):
             raise ValueError("Input contains NaN or infinity")
         self.m, self.cov, self.q = int(m), cov, cov.q
-        _lib._mv_checks(cov.kind, self.m, cov.A, cov.phi, cov.tau2)
+        self.misaligned = bool(np.isnan(Y).any())
+        if self.misaligned and not 1 <= self.m <= _lib.MV_OBS_MAX_M:
+            raise NotImplementedError(f"outcomes missing at some sites: 1 <= m <= {_lib.MV_OBS_MAX_M} (m={self.m})")
+        _lib._mv_checks(cov.kind, 1 if self.misaligned else self.m, cov.A, cov.phi, cov.tau2)
         self.device = _default_device(device)
         self.perm = None
         if ordering is not None:
@@ -123,16 +137,47 @@ class MultivariateNNGP:
             self.perm = _ordering.resolve(ordering, torch.as_tensor(t).to(self.device))
             t, Y = np.ascontiguousarray(t[self.perm]), np.ascontiguousarray(Y[self.perm])
         self.t, self.Y = t, Y
+        self._mask = ~np.isnan(Y)
+        self.obs = (self._mask << np.arange(self.q)).sum(axis=1).astype(np.uint8)
+        self.n_obs = int(self._mask.sum())
+        if nbr is not None:
+            nbr = np.ascontiguousarray(nbr)
+            if nbr.dtype != np.int32 or nbr.shape != (t.shape[0], self.m):
+                raise ValueError(f"nbr must be int32 ({t.shape[0]}, {self.m}), got {nbr.dtype} {nbr.shape}")
+            if np.any(nbr < -1) or np.any(nbr >= np.arange(t.shape[0])[:, None]):
+                raise ValueError("nbr must hold prior indices: -1 <= nbr[i, s] < i")
         self._t_dev = torch.as_tensor(t).to(self.device)
-        self._nbr = _lib.knn_prior(self._t_dev, self.m)
+        self._nbr = _lib.knn_prior(self._t_dev, self.m) if nbr is None else torch.as_tensor(nbr).to(self.device)
         self._B = self._LF = None
+        if self.misaligned:
+            self._obs_dev = torch.as_tensor(self.obs).to(self.device)
+            self._rows_max = self._rows_bound(self._nbr, "location")
+
+    def _rows_bound(self, nbr, what):
+        """The largest number of observed neighbour rows over ``nbr``'s rows, refused above 64 before any launch."""
+        rows = _lib.mv_obs_rows(nbr, self._obs_dev)
+        worst = int(rows.argmax()) if rows.numel() else 0
+        count = int(rows[worst]) if rows.numel() else 0
+        if count > _lib.MV_MAX_ROWS:
+            raise ValueError(f"{what} {worst} conditions on {count} observed neighbour rows; the packed-row sweep "
+                             f"serves at most {_lib.MV_MAX_ROWS}: use a smaller m or pass nbr=")
+        return max(count, 1)
+
+    def _refuse_misaligned(self, what):
+        if self.misaligned:
+            raise NotImplementedError(f"{what} is not built for outcomes missing at some sites (NaN in Y): the "
+                                      "packed-row sweep serves loglik, compute_BF, predict, impute and fit()")
 
     def _sweep(self, cov, cols, want_b=False, want_lf=False):
         """One sweep over every location with the value columns ``cols`` (N, q, c); raises on either flag."""
         cov = self.cov if cov is None else cov
         vals = torch.as_tensor(np.ascontiguousarray(cols)).to(self.device)
-        B, LF, E, p = _lib.bf_sweep_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals,
-                                       want_b=want_b, want_lf=want_lf)
+        if self.misaligned:
+            B, LF, E, p = _lib.bf_sweep_mv_obs(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2,
+                                               self._obs_dev, self._rows_max, vals, want_b=want_b, want_lf=want_lf)
+        else:
+            B, LF, E, p = _lib.bf_sweep_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals,
+                                           want_b=want_b, want_lf=want_lf)
         ph = p.cpu().numpy()
         _raise_on_bad(ph, cov)
         return B, LF, E, ph
@@ -147,22 +192,23 @@ class MultivariateNNGP:
                 raise ValueError(f"mean must be None, 'constant' or an array, got {mean!r}")
             cols = np.zeros((n, q, 1 + q))
             cols[:, :, 0] = self.Y
-            cols[:, np.arange(q), 1 + np.arange(q)] = 1.0
+            cols[:, np.arange(q), 1 + np.arange(q)] = self._mask  # E is 0 in the rows that are not observed
             _, _, E, ph = self._sweep(cov, cols)
             E = E.reshape(n * q, 1 + q)
             G = (E.T @ E).cpu().numpy()  # [[y'y, y'X], [X'y, X'X]] in the whitened metric
             mu = np.linalg.solve(G[1:, 1:], G[1:, 0])
             quad = G[0, 0] - G[0, 1:] @ mu
-            return -0.5 * (n * q * LOG_2PI + ph[0] + quad), mu
+            return -0.5 * (self.n_obs * LOG_2PI + ph[0] + quad), mu
         resid = self.Y if mean is None else self.Y - np.broadcast_to(np.asarray(mean, dtype=np.float64), (n, q))
         ph = self._sweep(cov, resid[:, :, None])[3]
-        return -0.5 * (n * q * LOG_2PI + ph[0] + ph[1])
+        return -0.5 * (self.n_obs * LOG_2PI + ph[0] + ph[1])
 
     def loglik_grad(self, cov=None, mean=None):
         """:meth:`loglik` and its gradient (P,) in ``cov.theta``'s order (A's lower triangle row-major, phi, tau2) from
         one ``nngp_bf_grad_mv`` sweep: ``(loglik, grad)``.  ``mean`` as in :meth:`loglik`; for "constant" the GLS mean
         comes from the whitening sweep and the gradient sweep runs on Y - mu: the gradient of the profile likelihood
         (mu maximises it, so its own derivative drops out), returned as ``(loglik, mu, grad)``."""
+        self._refuse_misaligned("loglik_grad")
         cov = self.cov if cov is None else cov
         n, q = self.Y.shape
         mu = None
@@ -204,10 +250,29 @@ class MultivariateNNGP:
         mu = np.zeros(self.q) if mean is None else np.asarray(mean, dtype=np.float64)
         vals = torch.as_tensor(np.ascontiguousarray((self.Y - mu)[:, :, None])).to(self.device)
         nbr = _lib.knn_query(self._t_dev, qd, self.m)
-        _, LF, pm, p = _lib.bf_cross_mv(self._t_dev, qd, nbr, cov.kind, cov.A, cov.phi, cov.tau2, vals,
-                                        target_noise=noise)
+        if self.misaligned:
+            _, LF, pm, p = _lib.bf_cross_mv_obs(self._t_dev, qd, nbr, cov.kind, cov.A, cov.phi, cov.tau2,
+                                                self._obs_dev, self._rows_bound(nbr, "query"), vals,
+                                                target_noise=noise)
+        else:
+            _, LF, pm, p = _lib.bf_cross_mv(self._t_dev, qd, nbr, cov.kind, cov.A, cov.phi, cov.tau2, vals,
+                                            target_noise=noise)
         _raise_on_bad(p.cpu().numpy(), cov)
         return pm[:, :, 0].cpu().numpy() + mu, (LF @ LF.transpose(1, 2)).cpu().numpy()
+
+    def impute(self, noise=True, cov=None, mean=None):
+        """The entries of ``Y`` that are not observed, predicted at their own site from its m nearest data sites'
+        observed outcomes; the site itself is among them, so what is observed there enters at distance 0 (co-located
+        co-kriging).  Returns ``(mean (N, q), sd (N, q))`` in the instance's row order: observed entries as they are
+        with sd 0.  ``noise``, ``cov`` and ``mean`` as in :meth:`predict`."""
+        out, sd = self.Y.copy(), np.zeros_like(self.Y)
+        rows = np.nonzero(~self._mask.all(axis=1))[0]
+        if rows.size:
+            pm, pc = self.predict(self.t[rows], noise=noise, cov=cov, mean=mean)
+            miss = ~self._mask[rows]
+            out[rows] = np.where(miss, pm, out[rows])
+            sd[rows] = np.where(miss, np.sqrt(np.diagonal(pc, axis1=1, axis2=2)), 0.0)
+        return out, sd
 
     def fit(self, start=None, tol=1e-6, maxiter=200, step=1e-5, gradient=False):
         """Maximum likelihood (zero mean) by L-BFGS-B on log diag A, raw off-diagonal A, log phi, log tau2, with
@@ -232,6 +297,7 @@ class MultivariateNNGP:
             return -ll, -g * np.array(scale + list(cov.phi) + list(cov.tau2))
 
         if gradient:
+            self._refuse_misaligned("fit(gradient=True)")
             x0 = _to_theta(self.cov if start is None else start)
             self.fit_result = optimize.minimize(value_and_grad, x0, jac=True, method="L-BFGS-B",
                                                 options={"maxiter": maxiter, "ftol": tol, "gtol": tol})
@@ -263,6 +329,7 @@ class MultivariateNNGP:
 
     def simulate(self, seed=0, cov=None):
         """A sequential draw (N, q) from the NNGP prior of ``cov``, from B and LF on the host."""
+        self._refuse_misaligned("simulate")
         B, LF, _, _ = self._sweep(cov, self.Y[:, :, None], want_b=True, want_lf=True)
         B, LF, nbr = B.cpu().numpy(), LF.cpu().numpy(), self._nbr.cpu().numpy()
         z = np.random.default_rng(seed).standard_normal(self.Y.shape)

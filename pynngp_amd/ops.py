@@ -45,6 +45,10 @@ for tracing.
     torch.ops.nngp.bf_cross_mv(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values) -> (B, LF, mean)
     torch.ops.nngp.bf_grad_mv(coords, nbr, order, i0, kind, A, phi, tau2, values, want_rows)
         -> (partials, grad, G)   # grad (P,), G (rows, P), P = q (q + 1) / 2 + 2 q: A's lower triangle, phi, tau2
+    torch.ops.nngp.bf_sweep_mv_obs(coords, nbr, order, i0, kind, A, phi, tau2, values, obs, rows_max, want_b)
+        -> (B, LF, E, partials)  # outcomes missing at some sites: obs (N,) uint8 masks, m <= 63, rows_max <= 64
+    torch.ops.nngp.bf_cross_mv_obs(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values, obs, rows_max)
+        -> (B, LF, mean)
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -246,6 +250,19 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_mv")
     def _(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values):
+        (rows, m), q = nbr.shape, len(phi)
+        c = ref_values.shape[2] if ref_values is not None else 1
+        return query.new_empty((rows, q, m * q)), query.new_empty((rows, q, q)), query.new_empty((rows, q, c))
+
+    @fake("bf_sweep_mv_obs")
+    def _(coords, nbr, order, i0, kind, A, phi, tau2, values, obs, rows_max, want_b):
+        (rows, m), q = nbr.shape, len(phi)
+        c = values.shape[2] if values is not None else 1
+        return (coords.new_empty((rows if want_b else 0, q, m * q)), coords.new_empty((rows, q, q)),
+                coords.new_empty((rows if values is not None else 0, q, c)), coords.new_empty((4,)))
+
+    @fake("bf_cross_mv_obs")
+    def _(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values, obs, rows_max):
         (rows, m), q = nbr.shape, len(phi)
         c = ref_values.shape[2] if ref_values is not None else 1
         return query.new_empty((rows, q, m * q)), query.new_empty((rows, q, q)), query.new_empty((rows, q, c))
