@@ -409,6 +409,28 @@ int nngp_bf_grad_mv(const double *coords, int64_t n_points, int32_t dim, const i
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * nngp_bf_grad_mv with outcomes missing at some sites (added within revision 4; nothing earlier moved): the
+ * log-likelihood of nngp_bf_sweep_mv_obs (S = T) and its gradient in the same P parameters, one fused sweep on the
+ * packed rows.  Arguments are nngp_bf_grad_mv's plus obs and rows_max as in nngp_bf_sweep_mv_obs; entries of values
+ * under a clear bit are never read.
+ *   partials[4]  as nngp_bf_sweep_mv_obs, equal to that sweep's to its own tolerance
+ *   grad[P], G   as nngp_bf_grad_mv; a location with nothing observed has a zero row, one with no observed neighbour
+ *                row the gradient of its own marginal density, one over 16 ceil(rows_max / 16) rows that of the kept
+ *                prefix of its slots (and is reported in partials[3])
+ * Folded in location order: bit-reproducible run to run and independent of `order`.
+ * Scope and errors: those of nngp_bf_sweep_mv_obs (1 <= m <= 63, 1 <= rows_max <= 64, 2 <= q <= 4, four kinds), and
+ * NNGP_EINVAL for a null values or grad.
+ * workspace: nngp_bf_grad_mv_obs_workspace_bytes(n_rows, m, q) (0 for unsupported arguments; a record of 4 + P doubles
+ * per location), 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_grad_mv_obs_workspace_bytes(int64_t n_rows, int32_t m, int32_t q);
+int nngp_bf_grad_mv_obs(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                        int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double *A,
+                        const double *phi, const double *tau2, const double *values, const uint8_t *obs,
+                        int32_t rows_max, double *G, double *partials, double *grad, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * The factors and their phi-derivatives, one fused sweep over locations i0 .. i0 + n_rows - 1 (coords, nbr,
  * order and i0 as nngp_bf_sweep).  With D_ab = sigma2 d_ab rho'(phi d_ab) and u = [-B_i; 1]:
  *   B  (n_rows, m), F (n_rows,): the factors of nngp_bf_sweep at this theta, equal to that sweep's to its own

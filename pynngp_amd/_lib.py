@@ -93,6 +93,8 @@ SYMBOLS = (
     "nngp_bf_sweep_mv_obs_workspace_bytes",
     "nngp_bf_sweep_mv_obs",
     "nngp_bf_cross_mv_obs",
+    "nngp_bf_grad_mv_obs_workspace_bytes",
+    "nngp_bf_grad_mv_obs",
     "nngp_bf_grad_nd",
     "nngp_bf_grad_aniso_workspace_bytes",
     "nngp_bf_grad_aniso",
@@ -250,6 +252,10 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_cross_mv_obs.argtypes = [P, I64, I32, P, I64, P, P, I64, I64, I32, I32, I32, P, P, P, I32, P, I32, P, I32,
                                          P, P, P, P, P, SZ, P]
     lib.nngp_bf_cross_mv_obs.restype = ctypes.c_int
+    lib.nngp_bf_grad_mv_obs_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_grad_mv_obs_workspace_bytes.restype = SZ
+    lib.nngp_bf_grad_mv_obs.argtypes = [P, I64, I32, P, P, I64, I64, I32, I32, I32, P, P, P, P, P, I32, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_mv_obs.restype = ctypes.c_int
     lib.nngp_bf_grad_nd.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, P, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_nd.restype = ctypes.c_int
     lib.nngp_bf_grad_aniso_workspace_bytes.argtypes = [I64, I32, I32]
@@ -1766,6 +1772,42 @@ def bf_cross_mv_obs(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, k
                                     _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_cross_mv_obs")
     return B, LF, mean, partials
+
+
+def bf_grad_mv_obs(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, A, phi, tau2, obs: torch.Tensor,
+                   rows_max: int, values: torch.Tensor, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`bf_grad_mv` with outcomes missing at some sites (``nngp_bf_grad_mv_obs``): one fused sweep on the packed
+    rows gives :func:`bf_sweep_mv_obs`'s partials and their gradient, ``(partials, grad, G)`` in :func:`bf_grad_mv`'s
+    shapes.  ``obs`` and ``rows_max`` as in :func:`bf_sweep_mv_obs`; ``values`` is float64 (N, q) or (N, q, 1) and may
+    hold NaN under a clear bit."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n, d = coords.shape
+    rows, m = nbr.shape
+    q, cA, cphi, ctau = _mv_obs_checks(kind, m, A, phi, tau2, obs, n, rows_max)
+    if values is None or values.dtype != torch.float64 or tuple(values.shape) not in ((n, q), (n, q, 1)):
+        raise ValueError(f"values must be float64 ({n}, {q}, 1)")
+    values = values.contiguous()
+    dev = _require_gpu(coords, nbr, values, order, obs)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    obs = obs.contiguous()
+    lib = load()
+    need = lib.nngp_bf_grad_mv_obs_workspace_bytes(rows, m, q)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    npar = q * (q + 1) // 2 + 2 * q
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(npar, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, npar), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_mv_obs(_ptr(coords), n, d, _ptr(nbr), _ptr(order), rows, int(i0), m, q, KIND_CODES[kind],
+                                   cA, cphi, ctau, _ptr(values), _ptr(obs), int(rows_max), _ptr(G), _ptr(partials),
+                                   _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_grad_mv_obs")
+    return partials, grad, G
 
 
 def joint_dist(coords: torch.Tensor, nbr: torch.Tensor, i0: int = 0, qcoords: Optional[torch.Tensor] = None,

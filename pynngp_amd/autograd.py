@@ -286,21 +286,27 @@ def loglik_ard(coords, nbr, kind, theta, values, order=None):
 
 
 class _LogLikLmc(torch.autograd.Function):
-    """The multivariate (LMC) sweep (``torch.ops.nngp.bf_grad_mv``): A (q, q), phi (q,), tau2 (q,)."""
+    """The multivariate (LMC) sweep (``torch.ops.nngp.bf_grad_mv``): A (q, q), phi (q,), tau2 (q,); with ``obs``
+    (masks, rows_max, n_obs) the packed-row sweep ``torch.ops.nngp.bf_grad_mv_obs``."""
 
     @staticmethod
-    def forward(ctx, coords, nbr, A, phi, tau2, Y, kind, order):
+    def forward(ctx, coords, nbr, A, phi, tau2, Y, kind, order, obs=None):
         from . import load_ops
 
         load_ops()
         q = phi.shape[0]
         host = [[float(x) for x in t.detach().cpu().reshape(-1).tolist()] for t in (A, phi, tau2)]  # host synchronisation
-        p, g, _ = torch.ops.nngp.bf_grad_mv(coords, nbr, order, 0, _lib.KIND_CODES[kind], *host,
-                                            Y.detach().reshape(-1, q, 1).contiguous(), False)
+        vals, n_obs = Y.detach().reshape(-1, q, 1).contiguous(), nbr.shape[0] * q
+        if obs is None:
+            p, g, _ = torch.ops.nngp.bf_grad_mv(coords, nbr, order, 0, _lib.KIND_CODES[kind], *host, vals, False)
+        else:
+            masks, rows_max, n_obs = obs
+            p, g, _ = torch.ops.nngp.bf_grad_mv_obs(coords, nbr, order, 0, _lib.KIND_CODES[kind], *host, vals, masks,
+                                                    rows_max, False)
         ctx.save_for_backward(g)
         ctx.meta = (q, A.device, phi.device, tau2.device)
         ctx.mark_non_differentiable(p)
-        ll = -0.5 * (nbr.shape[0] * q * math.log(2.0 * math.pi) + p[0] + p[1])
+        ll = -0.5 * (n_obs * math.log(2.0 * math.pi) + p[0] + p[1])
         return ll, p
 
     @staticmethod
@@ -315,7 +321,7 @@ class _LogLikLmc(torch.autograd.Function):
             gA = torch.zeros((q, q), dtype=g.dtype, device=g.device).index_put((low[0], low[1]), g[:ntq]).to(adev)
         gphi = g[ntq:ntq + q].to(pdev) if ctx.needs_input_grad[3] else None
         gtau = g[ntq + q:].to(tdev) if ctx.needs_input_grad[4] else None
-        return None, None, gA, gphi, gtau, None, None, None
+        return None, None, gA, gphi, gtau, None, None, None, None
 
 
 def loglik_lmc(coords, nbr, kind, A, phi, tau2, Y, order=None):
@@ -326,6 +332,10 @@ def loglik_lmc(coords, nbr, kind, A, phi, tau2, Y, order=None):
     Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_mv``) and synchronises with the host as :func:`loglik`
     does; backward returns ``grad_out * grad`` with no further launch.  ``nbr`` (N, m) int32, 2 <= q <= 4,
     (m + 1) q <= 64; kinds exponential, matern32, matern52, gaussian; the not-PD and bad-index flags raise.
+
+    NaN in ``Y`` means "not observed": the packed-row gradient sweep (``torch.ops.nngp.bf_grad_mv_obs``) runs instead,
+    over the observed entries only, with 1 <= m <= 63 and at most 64 observed neighbour rows per location (more is a
+    ``ValueError`` before any launch).
     """
     if kind not in _lib.KIND_CODES:
         raise ValueError(f"unknown covariance kind {kind!r}")
@@ -334,15 +344,26 @@ def loglik_lmc(coords, nbr, kind, A, phi, tau2, Y, order=None):
         raise ValueError("A must be a float64 (q, q) tensor, phi and tau2 float64 (q,)")
     if nbr.dim() != 2:
         raise ValueError("nbr must be int32 (N, m)")
-    _lib._mv_checks(kind, nbr.shape[1], A.detach().cpu().tolist(), phi.detach().cpu().tolist(),
-                    tau2.detach().cpu().tolist())
     if nbr.shape[0] != coords.shape[0] or Y.shape != (coords.shape[0], phi.shape[0]):
         raise ValueError("loglik_lmc is an S = T sweep: one nbr row and one row of Y (N, q) per location")
+    host = [t.detach().cpu().tolist() for t in (A, phi, tau2)]
+    seen = ~torch.isnan(Y)
+    obs = None
+    if not bool(seen.all()):
+        # bit a of a site's mask: outcome a observed; the bound on the packed rows before any launch
+        masks = (seen.to(torch.int32) << torch.arange(phi.shape[0], dtype=torch.int32, device=Y.device)).sum(1)
+        masks = masks.to(torch.uint8)
+        rows = _lib.mv_obs_rows(nbr, masks)
+        rows_max = int(rows.max()) if rows.numel() else 0
+        if rows_max > _lib.MV_MAX_ROWS:
+            raise ValueError(f"location {int(rows.argmax())} conditions on {rows_max} observed neighbour rows; the "
+                             f"packed-row sweep serves at most {_lib.MV_MAX_ROWS}: use a smaller m")
+        obs = (masks, max(rows_max, 1), int(seen.sum()))
+        _lib._mv_obs_checks(kind, nbr.shape[1], *host, masks, coords.shape[0], obs[1])
+    else:
+        _lib._mv_checks(kind, nbr.shape[1], *host)
     _lib._require_gpu(coords, nbr, Y, order)
-    if bool(torch.isnan(Y).any()):
-        raise NotImplementedError("loglik_lmc is not built for outcomes missing at some sites (NaN in Y): the gradient "
-                                  "sweep serves full Y only; MultivariateNNGP.loglik serves the packed-row sweep")
-    ll, p = _LogLikLmc.apply(coords, nbr, A, phi, tau2, Y, kind, order)
+    ll, p = _LogLikLmc.apply(coords, nbr, A, phi, tau2, Y, kind, order, obs)
     from .nngp import _raise_on_bad
 
     _raise_on_bad(p.detach().cpu().numpy())

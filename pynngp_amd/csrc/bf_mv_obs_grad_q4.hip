@@ -1,0 +1,11 @@
+// bf_mv_obs_grad<4, NTMAX> for NTMAX = 1..4 tile rows of packed neighbour rows (bf_mv_obs_grad.h)
+#include "bf_mv_obs_grad.h"
+
+namespace nngp {
+
+bool bf_mv_obs_grad_launch_q4(const MvObsGradArgs& a, hipStream_t s) {
+    return launch_mv_obs_grad_if<4, 1>(a, s) || launch_mv_obs_grad_if<4, 2>(a, s) ||
+           launch_mv_obs_grad_if<4, 3>(a, s) || launch_mv_obs_grad_if<4, 4>(a, s);
+}
+
+}  // namespace nngp

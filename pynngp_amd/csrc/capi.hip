@@ -18,6 +18,7 @@
 #include "bf_mv.h"
 #include "bf_mv_grad.h"
 #include "bf_mv_obs.h"
+#include "bf_mv_obs_grad.h"
 #include "bf_grad_aniso.h"
 #include "bf_grad_matern.h"
 #include "bf_dphi.h"
@@ -593,6 +594,27 @@ int nngp_bf_grad_mv(const double* coords, int64_t n_points, int32_t dim, const i
                        (double*)workspace};
     hipError_t e = nngp::bf_mv_grad_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_mv launch");
+    return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- the gradient sweep on packed rows (bf_mv_obs_grad.h)
+size_t nngp_bf_grad_mv_obs_workspace_bytes(int64_t n_rows, int32_t m, int32_t q) {
+    return nngp::mv_obs_grad_workspace_bytes(n_rows, m, q);
+}
+
+int nngp_bf_grad_mv_obs(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                        int64_t n_rows, int64_t i0, int32_t m, int32_t q, int32_t kind, const double* A,
+                        const double* phi, const double* tau2, const double* values, const uint8_t* obs,
+                        int32_t rows_max, double* G, double* partials, double* grad, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    nngp::MvError err;
+    if (nngp::mv_obs_grad_check(err, coords, n_points, dim, nbr, n_rows, m, q, i0, kind, A, phi, tau2, obs, rows_max,
+                                values, partials, grad, workspace, workspace_bytes) != NNGP_OK)
+        return fail(err.code, "%s", err.msg);
+    nngp::MvObsGradArgs a{{coords, n_points, nbr, order, n_rows, i0, m, q, kind, dim, A, phi, tau2, values, G,
+                           (double*)workspace}, obs, rows_max};
+    hipError_t e = nngp::bf_mv_obs_grad_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_mv_obs launch");
     return NNGP_OK;
 }
 

@@ -46,4 +46,27 @@ inline int mv_obs_check(MvError& e, const void* coords, int64_t n_points, int di
     return NNGP_OK;
 }
 
+// the gradient sweep on packed rows (bf_mv_obs_grad.h): bf_mv_grad's records (4 + P doubles per location, then per
+// chunk of kMvGradChunk locations) in this sweep's scope; 0 outside it
+inline size_t mv_obs_grad_workspace_bytes(int64_t n_rows, int m, int q) {
+    if (!mv_obs_scope(n_rows, m, q) || n_rows > ((int64_t)1 << 47)) return 0;
+    return mv_grad_rows_bytes(n_rows, q) + mv_grad_rows_bytes(mv_grad_chunks(n_rows), q);
+}
+
+// nngp_bf_grad_mv_obs: the packed sweep's checks (S = T, one value column), the pointers of its own and its larger
+// workspace
+inline int mv_obs_grad_check(MvError& e, const void* coords, int64_t n_points, int dim, const void* nbr, int64_t n_rows,
+                             int m, int q, int64_t i0, int kind, const double* A, const double* phi, const double* tau2,
+                             const void* obs, int rows_max, const void* values, const void* partials, const void* grad,
+                             const void* workspace, size_t workspace_bytes) {
+    if (mv_obs_check(e, coords, n_points, dim, nbr, n_rows, m, q, i0, n_points, kind, A, phi, tau2, 1, obs, rows_max,
+                     partials, workspace, workspace_bytes) != NNGP_OK)
+        return e.code;
+    if (values == nullptr || grad == nullptr) return mv_fail(e, NNGP_EINVAL, "values and grad must be non-null");
+    const size_t need = mv_obs_grad_workspace_bytes(n_rows, m, q);
+    if (workspace_bytes < need)
+        return mv_fail(e, NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return NNGP_OK;
+}
+
 }  // namespace nngp

@@ -794,6 +794,35 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_mv_obs(
     return {B, LF, E, p};
 }
 
+// the gradient sweep on packed rows (nngp_bf_grad_mv_obs): bf_grad_mv's outputs; values (N, q, 1), NaN allowed under a
+// clear bit of obs
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_mv_obs(const at::Tensor& coords, const at::Tensor& nbr,
+                                                              const c10::optional<at::Tensor>& order, int64_t i0,
+                                                              int64_t kind, at::ArrayRef<double> A,
+                                                              at::ArrayRef<double> phi, at::ArrayRef<double> tau2,
+                                                              const at::Tensor& values, const at::Tensor& obs,
+                                                              int64_t rows_max, bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t q = check_mv(A, phi, tau2);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0), d = coords.size(1);
+    check_f64(values, {n, q, 1}, coords, "values");
+    check_order(order, rows, coords);
+    check_obs(obs, n, coords);
+    auto f64 = coords.options();
+    const int64_t np = q * (q + 1) / 2 + 2 * q;
+    at::Tensor p = at::empty({4}, f64), g = at::empty({np}, f64), G = at::empty({want_rows ? rows : 0, np}, f64);
+    auto ws = workspace((int64_t)nngp_bf_grad_mv_obs_workspace_bytes(rows, (int32_t)m, (int32_t)q), coords);
+    check_rc(nngp_bf_grad_mv_obs(coords.data_ptr<double>(), n, (int32_t)d, nbr.data_ptr<int32_t>(), ptr<int32_t>(order),
+                                 rows, i0, (int32_t)m, (int32_t)q, (int32_t)kind, A.data(), phi.data(), tau2.data(),
+                                 values.data_ptr<double>(), obs.data_ptr<uint8_t>(), (int32_t)rows_max,
+                                 want_rows ? G.data_ptr<double>() : nullptr, p.data_ptr<double>(), g.data_ptr<double>(),
+                                 ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_grad_mv_obs");
+    return {p, g, G};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_mv_obs(const at::Tensor& ref, const at::Tensor& query,
                                                                const at::Tensor& nbr, int64_t kind,
                                                                at::ArrayRef<double> A, at::ArrayRef<double> phi,
@@ -1328,6 +1357,8 @@ TORCH_LIBRARY(nngp, m) {
           "bool target_noise, Tensor? ref_values, Tensor obs, int rows_max) -> (Tensor, Tensor, Tensor)");
     m.def("bf_grad_mv(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float[] A, float[] phi, "
           "float[] tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_grad_mv_obs(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float[] A, float[] phi, "
+          "float[] tau2, Tensor values, Tensor obs, int rows_max, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("row_order(Tensor coords, int i0, int rows, Tensor? nbr) -> (Tensor, Tensor)");
     m.def("order_maxmin(Tensor coords, int seed) -> (Tensor, Tensor)");
     m.def("combine_partials_out(Tensor gathered, Tensor(a!) out) -> ()");
@@ -1360,6 +1391,7 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_grad_mv", &bf_grad_mv);
     m.impl("bf_sweep_mv_obs", &bf_sweep_mv_obs);
     m.impl("bf_cross_mv_obs", &bf_cross_mv_obs);
+    m.impl("bf_grad_mv_obs", &bf_grad_mv_obs);
     m.impl("bf_grad_aniso", &bf_grad_aniso);
     m.impl("bf_grad_matern", &bf_grad_matern);
     m.impl("matern_eval_d", &matern_eval_d);

@@ -14,7 +14,8 @@ wavefront per location, the joint block of (m + 1) q <= 64 rows factorised on th
 Outcomes missing at some sites (NaN in ``Y``; co-kriging, spBayes' ``spMisalignLM``) run on the packed-row sweep
 ``nngp_bf_sweep_mv_obs`` / ``nngp_bf_cross_mv_obs``: a location conditions on its neighbours'
 *observed* outcomes only, at most 64 of them over m <= 63 neighbour sites; :meth:`MultivariateNNGP.impute` predicts the
-missing entries.  A reference set other than the data, per-component kinds, per-point noise and the latent / Gibbs
+missing entries, and the analytic gradient on such data is ``nngp_bf_grad_mv_obs``:
+``loglik_grad(missing="packed")`` and ``fit(gradient=True)``.  A reference set other than the data, per-component kinds, per-point noise and the latent / Gibbs
 forms are not built.
 """
 import dataclasses
@@ -110,7 +111,8 @@ class MultivariateNNGP:
 
     NaN in ``Y`` means "not observed" (``self.obs`` (N,) uint8 holds the masks, bit a for outcome a).  Such an
     instance serves ``m <= 63`` and at most 64 observed neighbour rows per location; ``loglik``, ``compute_BF``,
-    ``predict``, ``fit()`` and :meth:`impute` work on it, the gradient sweep and ``simulate`` do not yet.  ``nbr``
+    ``predict``, ``fit()``, ``fit(gradient=True)``, ``loglik_grad(missing="packed")`` and :meth:`impute` work on it,
+    ``simulate`` does not yet.  ``nbr``
     (N, m) int32, -1 padded, replaces the m nearest prior sites as the conditioning sets (indices in the instance's
     row order, every entry below its row), e.g. with sets chosen per outcome."""
 
@@ -166,7 +168,8 @@ class MultivariateNNGP:
     def _refuse_misaligned(self, what):
         if self.misaligned:
             raise NotImplementedError(f"{what} is not built for outcomes missing at some sites (NaN in Y): the "
-                                      "packed-row sweep serves loglik, compute_BF, predict, impute and fit()")
+                                      "packed-row sweeps serve loglik, loglik_grad(missing=\"packed\"), compute_BF, "
+                                      "predict, impute and fit()")
 
     def _sweep(self, cov, cols, want_b=False, want_lf=False):
         """One sweep over every location with the value columns ``cols`` (N, q, c); raises on either flag."""
@@ -203,12 +206,19 @@ class MultivariateNNGP:
         ph = self._sweep(cov, resid[:, :, None])[3]
         return -0.5 * (self.n_obs * LOG_2PI + ph[0] + ph[1])
 
-    def loglik_grad(self, cov=None, mean=None):
+    def loglik_grad(self, cov=None, mean=None, missing=None):
         """:meth:`loglik` and its gradient (P,) in ``cov.theta``'s order (A's lower triangle row-major, phi, tau2) from
         one ``nngp_bf_grad_mv`` sweep: ``(loglik, grad)``.  ``mean`` as in :meth:`loglik`; for "constant" the GLS mean
         comes from the whitening sweep and the gradient sweep runs on Y - mu: the gradient of the profile likelihood
-        (mu maximises it, so its own derivative drops out), returned as ``(loglik, mu, grad)``."""
-        self._refuse_misaligned("loglik_grad")
+        (mu maximises it, so its own derivative drops out), returned as ``(loglik, mu, grad)``.
+
+        With NaN in ``Y`` pass ``missing="packed"``: the packed-row gradient sweep ``nngp_bf_grad_mv_obs`` over the
+        observed entries.  Without the keyword such data is refused, as before that sweep existed."""
+        if missing not in (None, "packed"):
+            raise ValueError(f"missing must be None or 'packed', got {missing!r}")
+        if self.misaligned and missing is None:
+            raise NotImplementedError("loglik_grad on outcomes missing at some sites (NaN in Y) runs the packed-row "
+                                      "gradient sweep on request: pass missing=\"packed\"")
         cov = self.cov if cov is None else cov
         n, q = self.Y.shape
         mu = None
@@ -217,10 +227,14 @@ class MultivariateNNGP:
         resid = self.Y - (0.0 if mean is None else np.broadcast_to(np.asarray(mu if mu is not None else mean,
                                                                               dtype=np.float64), (n, q)))
         vals = torch.as_tensor(np.ascontiguousarray(resid[:, :, None])).to(self.device)
-        p, g, _ = _lib.bf_grad_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals)
+        if self.misaligned:
+            p, g, _ = _lib.bf_grad_mv_obs(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, self._obs_dev,
+                                          self._rows_max, vals)
+        else:
+            p, g, _ = _lib.bf_grad_mv(self._t_dev, self._nbr, 0, cov.kind, cov.A, cov.phi, cov.tau2, vals)
         ph = p.cpu().numpy()
         _raise_on_bad(ph, cov)
-        ll, g = -0.5 * (n * q * LOG_2PI + ph[0] + ph[1]), g.cpu().numpy()
+        ll, g = -0.5 * (self.n_obs * LOG_2PI + ph[0] + ph[1]), g.cpu().numpy()
         return (ll, g) if mu is None else (ll, mu, g)
 
     def compute_BF(self, cov=None):
@@ -277,7 +291,8 @@ class MultivariateNNGP:
     def fit(self, start=None, tol=1e-6, maxiter=200, step=1e-5, gradient=False):
         """Maximum likelihood (zero mean) by L-BFGS-B on log diag A, raw off-diagonal A, log phi, log tau2, with
         central differences of the sweep (2 (q (q + 1) / 2 + 2 q) sweeps per gradient), or with ``gradient=True`` on
-        the analytic gradient: one :meth:`loglik_grad` sweep per evaluation gives the value and the gradient.  Sets and
+        the analytic gradient: one :meth:`loglik_grad` sweep per evaluation gives the value and the gradient (the
+        packed-row sweep when ``Y`` has NaN).  Sets and
         returns ``self.cov``; ``self.fit_result`` keeps scipy's result and ``self.fit_sweeps`` the number of sweep
         launches."""
         from scipy import optimize
@@ -289,7 +304,7 @@ class MultivariateNNGP:
             self.fit_sweeps += 1
             try:
                 cov = _from_theta(kind, q, x)
-                ll, g = self.loglik_grad(cov)
+                ll, g = self.loglik_grad(cov, missing="packed" if self.misaligned else None)
             except (NNGPNumericalError, ValueError, OverflowError):
                 return 1e300, np.zeros_like(x)
             # the optimiser's vector: x A_aa for log diag A, x phi_k, x tau2_a
@@ -297,7 +312,6 @@ class MultivariateNNGP:
             return -ll, -g * np.array(scale + list(cov.phi) + list(cov.tau2))
 
         if gradient:
-            self._refuse_misaligned("fit(gradient=True)")
             x0 = _to_theta(self.cov if start is None else start)
             self.fit_result = optimize.minimize(value_and_grad, x0, jac=True, method="L-BFGS-B",
                                                 options={"maxiter": maxiter, "ftol": tol, "gtol": tol})

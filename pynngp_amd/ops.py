@@ -49,6 +49,8 @@ for tracing.
         -> (B, LF, E, partials)  # outcomes missing at some sites: obs (N,) uint8 masks, m <= 63, rows_max <= 64
     torch.ops.nngp.bf_cross_mv_obs(ref, query, nbr, kind, A, phi, tau2, target_noise, ref_values, obs, rows_max)
         -> (B, LF, mean)
+    torch.ops.nngp.bf_grad_mv_obs(coords, nbr, order, i0, kind, A, phi, tau2, values, obs, rows_max, want_rows)
+        -> (partials, grad, G)   # bf_grad_mv on the packed rows: NaN allowed in values under a clear bit of obs
     torch.ops.nngp.row_order(coords, i0, rows, nbr) -> (order, nbr_sorted)
     torch.ops.nngp.order_maxmin(coords, seed) -> (perm, level)   # levelled max-min order (a setup call: it
         # synchronises once per round); perm int64 (n,) position -> row, level int32 (n,) by position
@@ -266,6 +268,12 @@ def _register_fakes() -> None:
         (rows, m), q = nbr.shape, len(phi)
         c = ref_values.shape[2] if ref_values is not None else 1
         return query.new_empty((rows, q, m * q)), query.new_empty((rows, q, q)), query.new_empty((rows, q, c))
+
+    @fake("bf_grad_mv_obs")
+    def _(coords, nbr, order, i0, kind, A, phi, tau2, values, obs, rows_max, want_rows):
+        npar = len(phi) * (len(phi) + 1) // 2 + 2 * len(phi)
+        return (coords.new_empty((4,)), coords.new_empty((npar,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, npar)))
 
     @fake("row_order")
     def _(coords, i0, rows, nbr):
