@@ -268,6 +268,45 @@ int nngp_bf_grad_sep(const double *coords, int64_t n_points, int32_t dim, const 
                      double *grad, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Spatially varying coefficients (added within revision 4; nothing earlier moved):
+ *   y(s) = x(s)' beta + sum_{k < r} z_k(s) w_k(s) + eps(s),  w_k ~ GP(0, sigma2[k] rho(phi[k] |.|)) independent,
+ *   C(a, b) = sum_k z_ak z_bk sigma2[k] rho(phi[k] d_ab) + tau2 delta_ab,   1 <= r <= NNGP_SVC_MAX_R.
+ * Z (n_points, r) on the device holds the covariates z of the points (a column of ones: the spatially varying
+ * intercept); sigma2 and phi are HOST arrays of r numbers; kind, NNGP_COV_EXPONENTIAL .. NNGP_COV_SPHERICAL, is the
+ * same for every component.  The neighbour sets are those of nngp_knn_prior on the raw coordinates.  Coincident points
+ * with different z are legal (rho = 1 between them).
+ *   nngp_bf_sweep_svc: the contract of nngp_bf_sweep_sep (B, F, R, partials[4] required, order, i0, -1 padding, the
+ *     two flags, NaN rows on a bad pivot, a fixed-order fold).  The diagonal entry of the point in a slot is
+ *     sum_k z_k^2 sigma2[k] + tau2; a slot without a point is decoupled and has B exactly 0.
+ *   nngp_bf_cross_svc: the contract of nngp_bf_cross_sep with query_Z (n_query, r), the covariates of the query
+ *     points.  target_noise != 0 adds tau2 to the query's own diagonal entry (predicting y), 0 leaves it out.  With
+ *     query_Z = e_k and target_noise = 0 the sweep is NNGP kriging of the coefficient surface w_k at the queries:
+ *     Cov(w_k(s0), y_j) = z_jk sigma2[k] rho(phi[k] d).
+ *   nngp_bf_grad_svc: the contract of nngp_bf_grad_sep with G (n_rows, 2 r + 1) and grad[2 r + 1] in
+ *     (sigma2[0..r), phi[0..r), tau2): dC_ab/dsigma2[k] = z_ak z_bk rho_k, the diagonal included;
+ *     dC_ab/dphi[k] = z_ak z_bk sigma2[k] (u_k rho'(u_k)) / phi[k], exactly 0 on the diagonal and for coincident points.
+ * Scope: 1 <= m <= 32, 1 <= r <= NNGP_SVC_MAX_R, 1 <= dim <= NNGP_MAX_DIM, no general-nu kind, else NNGP_EUNSUP.
+ * NNGP_EINVAL for a null pointer, a non-positive or non-finite phi[k], a negative or non-finite sigma2[k] or tau2.
+ * workspace: nngp_bf_sweep_svc_workspace_bytes(n_rows, m, r) serves all three (0 for unsupported arguments);
+ * 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+#define NNGP_SVC_MAX_R 4
+size_t nngp_bf_sweep_svc_workspace_bytes(int64_t n_rows, int32_t m, int32_t r);
+int nngp_bf_sweep_svc(const double *coords, int64_t n_points, int32_t dim, const double *Z, int32_t r,
+                      const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
+                      const double *sigma2, const double *phi, double tau2, const double *values, double *B, double *F,
+                      double *R, double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_svc(const double *ref, int64_t n_ref, int32_t dim, const double *Z, int32_t r, const double *query,
+                      const double *query_Z, int64_t n_query, const int32_t *nbr, const int32_t *order, int64_t n_rows,
+                      int32_t m, int64_t q0, int32_t kind, const double *sigma2, const double *phi, double tau2,
+                      int32_t target_noise, const double *ref_values, const double *query_values, double *B, double *F,
+                      double *R, double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_grad_svc(const double *coords, int64_t n_points, int32_t dim, const double *Z, int32_t r,
+                     const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
+                     const double *sigma2, const double *phi, double tau2, const double *values, double *G,
+                     double *partials, double *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Points in 4 .. NNGP_ND_MAX_DIM dimensions (added within revision 4; nothing earlier moved).  Every entry point
  * above keeps its 1 <= dim <= NNGP_MAX_DIM; these take 4 <= dim <= NNGP_ND_MAX_DIM and nothing else.
  *

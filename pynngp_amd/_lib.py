@@ -79,6 +79,10 @@ SYMBOLS = (
     "nngp_bf_sweep_sep",
     "nngp_bf_cross_sep",
     "nngp_bf_grad_sep",
+    "nngp_bf_sweep_svc_workspace_bytes",
+    "nngp_bf_sweep_svc",
+    "nngp_bf_cross_svc",
+    "nngp_bf_grad_svc",
     "nngp_knn_nd_workspace_bytes",
     "nngp_knn_prior_nd",
     "nngp_knn_query_nd",
@@ -221,6 +225,15 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_cross_sep.restype = ctypes.c_int
     lib.nngp_bf_grad_sep.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, I32, D, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_sep.restype = ctypes.c_int
+    lib.nngp_bf_sweep_svc_workspace_bytes.argtypes = [I64, I32, I32]
+    lib.nngp_bf_sweep_svc_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_svc.argtypes = [P, I64, I32, P, I32, P, P, I64, I32, I64, I32, P, P, D, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_svc.restype = ctypes.c_int
+    lib.nngp_bf_cross_svc.argtypes = [P, I64, I32, P, I32, P, P, I64, P, P, I64, I32, I64, I32, P, P, D, I32, P, P, P, P,
+                                      P, P, P, SZ, P]
+    lib.nngp_bf_cross_svc.restype = ctypes.c_int
+    lib.nngp_bf_grad_svc.argtypes = [P, I64, I32, P, I32, P, P, I64, I32, I64, I32, P, P, D, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_grad_svc.restype = ctypes.c_int
     lib.nngp_knn_nd_workspace_bytes.argtypes = [I64, I32, I32]
     lib.nngp_knn_nd_workspace_bytes.restype = SZ
     lib.nngp_knn_prior_nd.argtypes = [P, I64, I32, I32, I64, I64, P, P, SZ, P]
@@ -1381,6 +1394,147 @@ def bf_cross_sep(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind
                                  float(phi_t), float(tau2), _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F),
                                  _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_cross_sep")
+    return B, F, R, partials
+
+
+# ---------------------------------------------------------------- spatially varying coefficients (nngp_*_svc)
+SVC_MAX_R = 4  # NNGP_SVC_MAX_R
+SVC_KINDS = ("exponential", "matern32", "matern52", "gaussian", "spherical")
+
+
+def _svc_checks(kind: str, m: int, dim: int, sigma2, phi, tau2):
+    """The scope of the varying-coefficient sweeps (nngp_bf_*_svc) and their parameters; returns
+    ``(r, sigma2, phi)`` with the two as C arrays."""
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in SVC_KINDS:
+        raise NotImplementedError(f"the varying-coefficient sweeps serve the kinds {SVC_KINDS}, not {kind!r}")
+    sigma2, phi = [float(x) for x in np.ravel(sigma2)], [float(x) for x in np.ravel(phi)]
+    r = len(phi)
+    if not 1 <= r <= SVC_MAX_R:
+        raise NotImplementedError(f"the varying-coefficient sweeps serve 1 <= r <= {SVC_MAX_R} components (r={r})")
+    if not 1 <= dim <= MAX_DIM:
+        raise NotImplementedError(f"the varying-coefficient sweeps serve 1 <= dim <= {MAX_DIM} (dim={dim})")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the varying-coefficient sweeps serve 1 <= m <= {GRAD_MAX_M} (m={m})")
+    if len(sigma2) != r:
+        raise ValueError(f"sigma2 and phi must both hold r numbers, got {len(sigma2)} and {r}")
+    if not all(math.isfinite(x) and x >= 0.0 for x in sigma2):
+        raise ValueError("every sigma2_k must be non-negative and finite")
+    if not all(math.isfinite(x) and x > 0.0 for x in phi):
+        raise ValueError("every phi_k must be positive and finite")
+    if not (math.isfinite(tau2) and tau2 >= 0.0):
+        raise ValueError("tau2 must be non-negative and finite")
+    return r, (ctypes.c_double * r)(*sigma2), (ctypes.c_double * r)(*phi)
+
+
+def _svc_z(Z: torch.Tensor, n: int, r: int, name: str) -> torch.Tensor:
+    if Z is None or Z.dtype != torch.float64 or Z.shape != (n, r):
+        raise ValueError(f"{name} must be float64 ({n}, {r})")
+    return Z.contiguous()
+
+
+def _svc_front(coords, nbr, order, values, n_values, what):
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (n_values,):
+            raise ValueError(f"{what} must be float64 ({n_values},)")
+        values = values.contiguous()
+    if order is not None and (order.dtype != torch.int32 or order.shape != (nbr.shape[0],)):
+        raise ValueError("order must be int32 (rows,)")
+    return nbr.contiguous(), values
+
+
+def bf_sweep_svc(coords: torch.Tensor, Z: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2, phi, tau2: float,
+                 values: Optional[torch.Tensor] = None, want_bf: bool = True, order: Optional[torch.Tensor] = None,
+                 want_r: bool = False, workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep` under the spatially-varying-coefficient covariance (``nngp_bf_sweep_svc``, include/nngp.h):
+    ``sum_k z_ak z_bk sigma2_k rho(phi_k d_ab) + tau2 delta_ab`` with ``Z`` (N, r) the points' covariates and
+    ``sigma2``, ``phi`` sequences of r numbers, 1 <= r <= 4.  Returns ``(B, F, R, partials)`` (B, F None without
+    ``want_bf``; R None without ``want_r``, which needs ``values``).  Kinds exponential .. spherical, 1 <= m <= 32,
+    dim 1..3; ``order`` as in :func:`bf_sweep`."""
+    coords = _as_coords(coords)
+    n, d = coords.shape
+    nbr, values = _svc_front(coords, nbr, order, values, n, "values")
+    rows, m = nbr.shape
+    r, cs2, cphi = _svc_checks(kind, m, d, sigma2, phi, float(tau2))
+    Z = _svc_z(Z, n, r, "Z")
+    dev = _require_gpu(coords, Z, nbr, values, order)
+    if want_r and values is None:
+        raise ValueError("want_r needs values")
+    lib = load()
+    need = lib.nngp_bf_sweep_svc_workspace_bytes(rows, m, r)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev) if want_bf else None
+    F = torch.empty((rows,), dtype=torch.float64, device=dev) if want_bf else None
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_svc(_ptr(coords), n, d, _ptr(Z), r, _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                 KIND_CODES[kind], cs2, cphi, float(tau2), _ptr(values), _ptr(B), _ptr(F), _ptr(R),
+                                 _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_sweep_svc")
+    return B, F, R, partials
+
+
+def bf_grad_svc(coords: torch.Tensor, Z: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, sigma2, phi, tau2: float,
+                values: torch.Tensor, want_rows: bool = False, order: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """:func:`bf_grad` under the spatially-varying-coefficient covariance (``nngp_bf_grad_svc``):
+    ``(partials, grad, G)`` with grad (2 r + 1,) and G (rows, 2 r + 1) in (sigma2_1..r, phi_1..r, tau2)."""
+    coords = _as_coords(coords)
+    n, d = coords.shape
+    if values is None:
+        raise ValueError("values must be float64 (N,)")
+    nbr, values = _svc_front(coords, nbr, order, values, n, "values")
+    rows, m = nbr.shape
+    r, cs2, cphi = _svc_checks(kind, m, d, sigma2, phi, float(tau2))
+    Z = _svc_z(Z, n, r, "Z")
+    dev = _require_gpu(coords, Z, nbr, values, order)
+    lib = load()
+    need = lib.nngp_bf_sweep_svc_workspace_bytes(rows, m, r)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(need, dev)
+    npar = 2 * r + 1
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    grad = torch.empty(npar, dtype=torch.float64, device=dev)
+    G = torch.empty((rows, npar), dtype=torch.float64, device=dev) if want_rows else None
+    _check(lib.nngp_bf_grad_svc(_ptr(coords), n, d, _ptr(Z), r, _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                KIND_CODES[kind], cs2, cphi, float(tau2), _ptr(values), _ptr(G), _ptr(partials),
+                                _ptr(grad), _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_grad_svc")
+    return partials, grad, G
+
+
+def bf_cross_svc(ref: torch.Tensor, Z: torch.Tensor, query: torch.Tensor, query_Z: torch.Tensor, nbr: torch.Tensor,
+                 kind: str, sigma2, phi, tau2: float, ref_values: Optional[torch.Tensor] = None,
+                 query_values: Optional[torch.Tensor] = None, target_noise: bool = True, q0: int = 0,
+                 order: Optional[torch.Tensor] = None, want_r: bool = False):
+    """:func:`bf_cross` under the spatially-varying-coefficient covariance (``nngp_bf_cross_svc``): ``query_Z``
+    (n_query, r) holds the queries' covariates; ``target_noise`` adds tau2 to the query's own variance (predicting y)
+    or leaves it out.  ``query_Z`` = e_k without target noise is kriging of the coefficient w_k.  Returns
+    ``(B, F, R, partials)`` (R None without ``want_r``, which needs ``ref_values``)."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    nbr, ref_values = _svc_front(ref, nbr, order, ref_values, ref.shape[0], "ref_values")
+    _, query_values = _svc_front(ref, nbr, None, query_values, query.shape[0], "query_values")
+    rows, m = nbr.shape
+    r, cs2, cphi = _svc_checks(kind, m, d, sigma2, phi, float(tau2))
+    Z, query_Z = _svc_z(Z, ref.shape[0], r, "Z"), _svc_z(query_Z, query.shape[0], r, "query_Z")
+    dev = _require_gpu(ref, Z, query, query_Z, nbr, ref_values, query_values, order)
+    if want_r and ref_values is None:
+        raise ValueError("want_r needs ref_values")
+    lib = load()
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev)
+    F = torch.empty((rows,), dtype=torch.float64, device=dev)
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(lib.nngp_bf_sweep_svc_workspace_bytes(rows, m, r), dev)
+    _check(lib.nngp_bf_cross_svc(_ptr(ref), ref.shape[0], d, _ptr(Z), r, _ptr(query), _ptr(query_Z), query.shape[0],
+                                 _ptr(nbr), _ptr(order), rows, m, int(q0), KIND_CODES[kind], cs2, cphi, float(tau2),
+                                 int(bool(target_noise)), _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F),
+                                 _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_cross_svc")
     return B, F, R, partials
 
 

@@ -221,6 +221,74 @@ def loglik_sep(coords, nbr, kind_s, kind_t, theta4, values, order=None):
     return ll
 
 
+class _LogLikSvc(torch.autograd.Function):
+    """theta = (sigma2_1..r, phi_1..r, tau2): the varying-coefficient sweep (``torch.ops.nngp.bf_grad_svc``)."""
+
+    @staticmethod
+    def forward(ctx, coords, Z, nbr, theta, values, kind, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        r = (len(th) - 1) // 2
+        p, g, _ = torch.ops.nngp.bf_grad_svc(coords, Z, nbr, order, 0, _lib.KIND_CODES[kind], th[:r], th[r:2 * r],
+                                             th[-1], values.detach(), False)
+        ctx.save_for_backward(coords, Z, nbr, values, g)
+        ctx.meta = (kind, order, th, r, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, Z, nbr, values, g = ctx.saved_tensors
+        kind, order, th, r, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[3] else None
+        gvalues = None
+        if ctx.needs_input_grad[4]:
+            # as _LogLik: one ordinary sweep (B, F, R) of the same model
+            B, F, R, _ = _lib.bf_sweep_svc(coords, Z, nbr, 0, kind, th[:r], th[r:2 * r], th[-1],
+                                           values=values.detach(), order=order, want_r=True)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            gvalues = -w
+            ok = nat >= 0
+            gvalues = gvalues.index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, None, gtheta, gvalues, None, None
+
+
+def loglik_svc(coords, Z, nbr, kind, theta, values, order=None):
+    """NNGP log-likelihood of ``values`` on S = T under the spatially-varying-coefficient covariance
+    ``sum_k z_ak z_bk sigma2_k rho(phi_k d) + tau2 delta`` with ``Z`` (N, r) the covariates, at ``theta`` =
+    (sigma2_1..r, phi_1..r, tau2), a float64 (2 r + 1,) tensor; differentiable in ``theta`` and, when
+    ``values.requires_grad``, in ``values`` (not in ``Z``).
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_svc``) and synchronises with the host as
+    :func:`loglik` does; backward returns ``grad_out * grad`` for theta with no further launch.  ``nbr`` (N, m) int32
+    with 1 <= m <= 32; kinds exponential .. spherical; 1 <= r <= 4; the not-PD and bad-index flags raise.
+    """
+    if kind not in _lib.KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in _lib.SVC_KINDS:
+        raise NotImplementedError(f"loglik_svc serves the kinds {_lib.SVC_KINDS}")
+    if Z.dim() != 2 or not 1 <= Z.shape[1] <= _lib.SVC_MAX_R:
+        raise NotImplementedError(f"loglik_svc serves Z (N, r) with 1 <= r <= {_lib.SVC_MAX_R}")
+    if theta.dtype != torch.float64 or theta.shape != (2 * Z.shape[1] + 1,):
+        raise ValueError("theta must be a float64 (2 r + 1,) tensor (sigma2_1..r, phi_1..r, tau2)")
+    if coords.dim() != 2 or not 1 <= coords.shape[1] <= _lib.MAX_DIM:
+        raise NotImplementedError(f"loglik_svc serves 1 .. {_lib.MAX_DIM} coordinate columns")
+    if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
+        raise NotImplementedError(f"loglik_svc's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
+    if nbr.shape[0] != coords.shape[0]:
+        raise ValueError("loglik_svc is an S = T sweep: one nbr row per location")
+    ll, p = _LogLikSvc.apply(coords, Z, nbr, theta, values, kind, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 class _LogLikArd(torch.autograd.Function):
     """theta = (sigma2, phi_1 .. phi_dim, tau2): the n-dimensional sweep (``torch.ops.nngp.bf_grad_nd``)."""
 

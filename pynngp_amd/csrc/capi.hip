@@ -14,6 +14,7 @@
 #include "bf_grad.h"
 #include "bf_noise.h"
 #include "bf_sep.h"
+#include "bf_svc.h"
 #include "bf_nd.h"
 #include "bf_mv.h"
 #include "bf_mv_grad.h"
@@ -396,6 +397,102 @@ int nngp_bf_grad_sep(const double* coords, int64_t n_points, int32_t dim, const 
                     coords, values, nullptr, nullptr, nullptr, G, (double*)workspace};
     hipError_t e = nngp::bf_sep_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_sep launch");
+    return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- spatially varying coefficients (bf_svc.h)
+static bool svc_scope(int64_t n_rows, int32_t m, int32_t r) {
+    return n_rows >= 0 && m >= 1 && m <= 32 && r >= 1 && r <= nngp::kSvcMaxComp;
+}
+
+size_t nngp_bf_sweep_svc_workspace_bytes(int64_t n_rows, int32_t m, int32_t r) {
+    if (!svc_scope(n_rows, m, r)) return 0;
+    // at least one record; the gradient's records (kSvcRec doubles per block) cover the forward sweep's four
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return align256((size_t)nb * nngp::kSvcRec * sizeof(double));
+}
+
+// the checks the three entry points share (scope, theta, workspace)
+static int svc_common(const double* coords, int64_t n_points, int32_t dim, const double* Z, int32_t r, const int32_t* nbr,
+                      int64_t n_rows, int32_t m, int64_t i0, int64_t n_locs, int32_t kind, const double* sigma2,
+                      const double* phi, double tau2, double* partials, void* workspace, size_t workspace_bytes) {
+    if (dim < 1 || dim > NNGP_MAX_DIM)
+        return fail(NNGP_EUNSUP, "the varying-coefficient sweeps serve 1 <= dim <= %d (dim=%d)", NNGP_MAX_DIM, dim);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the varying-coefficient sweeps serve 1 <= m <= 32 (m=%d)", m);
+    if (r < 1 || r > nngp::kSvcMaxComp)
+        return fail(NNGP_EUNSUP, "the varying-coefficient sweeps serve 1 <= r <= %d components (r=%d)",
+                    nngp::kSvcMaxComp, r);
+    if (kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the varying-coefficient sweeps serve the kinds exponential .. spherical, not the "
+                                 "general-nu matern");
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EINVAL, "unknown kind %d", kind);
+    if (sigma2 == nullptr || phi == nullptr) return fail(NNGP_EINVAL, "sigma2 and phi must be non-null");
+    for (int k = 0; k < r; ++k)
+        if (!(sigma2[k] >= 0.0) || !(phi[k] > 0.0) || !isfinite(sigma2[k]) || !isfinite(phi[k]))
+            return fail(NNGP_EINVAL, "theta must satisfy sigma2[k] >= 0, phi[k] > 0 (finite), k=%d", k);
+    if (!(tau2 >= 0.0) || !isfinite(tau2)) return fail(NNGP_EINVAL, "theta must satisfy tau2 >= 0 (finite)");
+    if (coords == nullptr || Z == nullptr || workspace == nullptr)
+        return fail(NNGP_EINVAL, "coordinates, Z and workspace must be non-null");
+    if (partials == nullptr) return fail(NNGP_EINVAL, "partials must be non-null");
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_locs)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_locs);
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_sweep_svc_workspace_bytes(n_rows, m, r);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    return NNGP_OK;
+}
+
+static int svc_forward(const double* coords, int64_t n_points, int32_t dim, const double* Z, int32_t r,
+                       const double* qcoords, const double* qZ, int64_t n_locs, const int32_t* nbr, const int32_t* order,
+                       int64_t n_rows, int32_t m, int64_t i0, int32_t kind, const double* sigma2, const double* phi,
+                       double tau2, int32_t target_noise, const double* values, const double* qvalues, double* B,
+                       double* F, double* R, double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = svc_common(coords, n_points, dim, Z, r, nbr, n_rows, m, i0, n_locs, kind, sigma2, phi, tau2, partials,
+                              workspace, workspace_bytes);
+    if (rc != NNGP_OK) return rc;
+    if (qcoords == nullptr || qZ == nullptr) return fail(NNGP_EINVAL, "coordinates, Z and workspace must be non-null");
+    if (B != nullptr && F == nullptr) return fail(NNGP_EINVAL, "B given without F");
+    if (F != nullptr && B == nullptr && n_rows > 0) return fail(NNGP_EINVAL, "F given without B");
+    if (R != nullptr && values == nullptr) return fail(NNGP_EINVAL, "R (residuals) needs values");
+    nngp::SvcArgs a{coords, n_points, Z, nbr, order, n_rows, i0, m, kind, dim, r, sigma2, phi, tau2, target_noise != 0,
+                    values, qcoords, qZ, qvalues, B, F, R, nullptr, (double*)workspace};
+    hipError_t e = nngp::bf_svc_launch(a, partials, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_svc launch");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_svc(const double* coords, int64_t n_points, int32_t dim, const double* Z, int32_t r, const int32_t* nbr,
+                      const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind, const double* sigma2,
+                      const double* phi, double tau2, const double* values, double* B, double* F, double* R,
+                      double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    return svc_forward(coords, n_points, dim, Z, r, coords, Z, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2,
+                       1, values, values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_cross_svc(const double* ref, int64_t n_ref, int32_t dim, const double* Z, int32_t r, const double* query,
+                      const double* query_Z, int64_t n_query, const int32_t* nbr, const int32_t* order, int64_t n_rows,
+                      int32_t m, int64_t q0, int32_t kind, const double* sigma2, const double* phi, double tau2,
+                      int32_t target_noise, const double* ref_values, const double* query_values, double* B, double* F,
+                      double* R, double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    if (query_values != nullptr && ref_values == nullptr) return fail(NNGP_EINVAL, "query_values need ref_values");
+    return svc_forward(ref, n_ref, dim, Z, r, query, query_Z, n_query, nbr, order, n_rows, m, q0, kind, sigma2, phi, tau2,
+                       target_noise, ref_values, query_values, B, F, R, partials, workspace, workspace_bytes, stream);
+}
+
+int nngp_bf_grad_svc(const double* coords, int64_t n_points, int32_t dim, const double* Z, int32_t r, const int32_t* nbr,
+                     const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind, const double* sigma2,
+                     const double* phi, double tau2, const double* values, double* G, double* partials, double* grad,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = svc_common(coords, n_points, dim, Z, r, nbr, n_rows, m, i0, n_points, kind, sigma2, phi, tau2, partials,
+                              workspace, workspace_bytes);
+    if (rc != NNGP_OK) return rc;
+    if (values == nullptr || grad == nullptr) return fail(NNGP_EINVAL, "values, partials and grad must be non-null");
+    nngp::SvcArgs a{coords, n_points, Z, nbr, order, n_rows, i0, m, kind, dim, r, sigma2, phi, tau2, 1, values, coords, Z,
+                    values, nullptr, nullptr, nullptr, G, (double*)workspace};
+    hipError_t e = nngp::bf_svc_launch(a, partials, grad, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf_grad_svc launch");
     return NNGP_OK;
 }
 

@@ -470,6 +470,103 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_noise(const at::Tensor& 
     return {B, F, mean};
 }
 
+// ---------------------------------------------------------------- spatially varying coefficients (nngp_bf_*_svc)
+static int64_t check_svc(const at::Tensor& Z, int64_t n, const at::Tensor& like, at::ArrayRef<double> sigma2,
+                         at::ArrayRef<double> phi, const char* name) {
+    const int64_t r = (int64_t)phi.size();
+    TORCH_CHECK(r >= 1 && r <= NNGP_SVC_MAX_R && (int64_t)sigma2.size() == r,
+                "sigma2 and phi must hold r numbers each, 1 <= r <= ", NNGP_SVC_MAX_R);
+    check_f64(Z, {n, r}, like, name);
+    return r;
+}
+
+// (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_svc(
+    const at::Tensor& coords, const at::Tensor& Z, const at::Tensor& nbr, const c10::optional<at::Tensor>& order,
+    int64_t i0, int64_t kind, at::ArrayRef<double> sigma2, at::ArrayRef<double> phi, double tau2,
+    const c10::optional<at::Tensor>& values, bool want_bf) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    const int64_t r = check_svc(Z, n, coords, sigma2, phi, "Z");
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool wr = values.has_value();
+    at::Tensor B = at::empty({want_bf ? rows : 0, m}, f64), F = at::empty({want_bf ? rows : 0}, f64);
+    at::Tensor R = at::empty({wr ? rows : 0}, f64), p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_svc_workspace_bytes(rows, (int32_t)m, (int32_t)r), coords);
+    check_rc(nngp_bf_sweep_svc(coords.data_ptr<double>(), n, (int32_t)coords.size(1), Z.data_ptr<double>(), (int32_t)r,
+                               nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind,
+                               sigma2.data(), phi.data(), tau2, ptr<double>(values),
+                               want_bf ? B.data_ptr<double>() : nullptr, want_bf ? F.data_ptr<double>() : nullptr,
+                               wr ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(), ws.data_ptr(),
+                               (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_svc");
+    return {B, F, R, p};
+}
+
+// (partials (4,), grad (2 r + 1,) in (sigma2_1..r, phi_1..r, tau2), G (rows, 2 r + 1) or (0, 2 r + 1))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_grad_svc(const at::Tensor& coords, const at::Tensor& Z,
+                                                           const at::Tensor& nbr,
+                                                           const c10::optional<at::Tensor>& order, int64_t i0,
+                                                           int64_t kind, at::ArrayRef<double> sigma2,
+                                                           at::ArrayRef<double> phi, double tau2,
+                                                           const at::Tensor& values, bool want_rows) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    const int64_t r = check_svc(Z, n, coords, sigma2, phi, "Z");
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    at::Tensor p = at::empty({4}, f64), g = at::empty({2 * r + 1}, f64);
+    at::Tensor G = at::empty({want_rows ? rows : 0, 2 * r + 1}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_svc_workspace_bytes(rows, (int32_t)m, (int32_t)r), coords);
+    check_rc(nngp_bf_grad_svc(coords.data_ptr<double>(), n, (int32_t)coords.size(1), Z.data_ptr<double>(), (int32_t)r,
+                              nbr.data_ptr<int32_t>(), ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind,
+                              sigma2.data(), phi.data(), tau2, values.data_ptr<double>(),
+                              want_rows ? G.data_ptr<double>() : nullptr, p.data_ptr<double>(), g.data_ptr<double>(),
+                              ws.data_ptr(), (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_grad_svc");
+    return {p, g, G};
+}
+
+// (B, F, kriging mean), as bf_cross; query_Z the queries' covariates, target_noise as nngp_bf_cross_mv
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_svc(const at::Tensor& ref, const at::Tensor& Z,
+                                                            const at::Tensor& query, const at::Tensor& query_Z,
+                                                            const at::Tensor& nbr, int64_t kind,
+                                                            at::ArrayRef<double> sigma2, at::ArrayRef<double> phi,
+                                                            double tau2, bool target_noise,
+                                                            const c10::optional<at::Tensor>& ref_values) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1);
+    const int64_t r = check_svc(Z, ref.size(0), ref, sigma2, phi, "Z");
+    check_svc(query_Z, query.size(0), ref, sigma2, phi, "query_Z");
+    check_f64(ref_values, {ref.size(0)}, ref, "ref_values");
+    auto f64 = ref.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64), R = at::empty({rows}, f64);
+    at::Tensor p = at::empty({4}, f64);
+    auto ws = workspace((int64_t)nngp_bf_sweep_svc_workspace_bytes(rows, (int32_t)m, (int32_t)r), ref);
+    check_rc(nngp_bf_cross_svc(ref.data_ptr<double>(), ref.size(0), (int32_t)d, Z.data_ptr<double>(), (int32_t)r,
+                               query.data_ptr<double>(), query_Z.data_ptr<double>(), query.size(0),
+                               nbr.data_ptr<int32_t>(), nullptr, rows, (int32_t)m, 0, (int32_t)kind, sigma2.data(),
+                               phi.data(), tau2, target_noise ? 1 : 0, ptr<double>(ref_values), nullptr,
+                               B.data_ptr<double>(), F.data_ptr<double>(),
+                               ref_values.has_value() ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(),
+                               ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_svc");
+    at::Tensor mean = ref_values.has_value() ? R.neg() : at::zeros({rows}, f64);
+    return {B, F, mean};
+}
+
 // ---------------------------------------------------------------- separable space-time (nngp_bf_*_sep)
 // (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_sep(
@@ -1339,6 +1436,12 @@ TORCH_LIBRARY(nngp, m) {
           "float phi_s, float phi_t, float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_cross_sep(Tensor ref, Tensor query, Tensor nbr, int kind_s, int kind_t, float sigma2, float phi_s, "
           "float phi_t, float tau2, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_svc(Tensor coords, Tensor Z, Tensor nbr, Tensor? order, int i0, int kind, float[] sigma2, "
+          "float[] phi, float tau2, Tensor? values, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_grad_svc(Tensor coords, Tensor Z, Tensor nbr, Tensor? order, int i0, int kind, float[] sigma2, "
+          "float[] phi, float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_cross_svc(Tensor ref, Tensor Z, Tensor query, Tensor query_Z, Tensor nbr, int kind, float[] sigma2, "
+          "float[] phi, float tau2, bool target_noise, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
     m.def("knn_prior_nd(Tensor coords, int m, int q0, int q1) -> Tensor");
     m.def("knn_query_nd(Tensor ref, Tensor query, int k) -> Tensor");
     m.def("bf_sweep_nd(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, float sigma2, float[] phi, "
@@ -1381,6 +1484,9 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_sep", &bf_sweep_sep);
     m.impl("bf_grad_sep", &bf_grad_sep);
     m.impl("bf_cross_sep", &bf_cross_sep);
+    m.impl("bf_sweep_svc", &bf_sweep_svc);
+    m.impl("bf_grad_svc", &bf_grad_svc);
+    m.impl("bf_cross_svc", &bf_cross_svc);
     m.impl("knn_prior_nd", &knn_prior_nd);
     m.impl("knn_query_nd", &knn_query_nd);
     m.impl("bf_sweep_nd", &bf_sweep_nd);

@@ -33,6 +33,12 @@ for tracing.
         -> (partials, grad, G)                                         # grad (4,), G (rows, 4): sigma2, phi_s, phi_t, tau2
     torch.ops.nngp.bf_cross_sep(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values)
         -> (B, F, mean)                                                # bf_cross of that model
+    torch.ops.nngp.bf_sweep_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
+        -> (B, F, R, partials)   # spatially varying coefficients: Z (N, r), sigma2 and phi lists of r <= 4 numbers
+    torch.ops.nngp.bf_grad_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
+        -> (partials, grad, G)   # grad (2 r + 1,), G (rows, 2 r + 1): sigma2_1..r, phi_1..r, tau2
+    torch.ops.nngp.bf_cross_svc(ref, Z, query, query_Z, nbr, kind, sigma2, phi, tau2, target_noise, ref_values)
+        -> (B, F, mean)          # query_Z = e_k without target noise: kriging of the coefficient w_k
     torch.ops.nngp.knn_prior_nd(coords, m, q0, q1) -> nbr              # 4 <= dim <= 16: exact, tiled brute force
     torch.ops.nngp.knn_query_nd(ref, query, k) -> nbr
     torch.ops.nngp.bf_sweep_nd(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
@@ -209,6 +215,23 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_sep")
     def _(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_svc")
+    def _(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_grad_svc")
+    def _(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows):
+        npar = 2 * len(phi) + 1
+        return (coords.new_empty((4,)), coords.new_empty((npar,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, npar)))
+
+    @fake("bf_cross_svc")
+    def _(ref, Z, query, query_Z, nbr, kind, sigma2, phi, tau2, target_noise, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 
