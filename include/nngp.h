@@ -307,6 +307,41 @@ int nngp_bf_grad_svc(const double *coords, int64_t n_points, int32_t dim, const 
                      double *partials, double *grad, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Nonseparable space-time covariance of Gneiting's (2002) class (added within revision 4; nothing earlier moved).
+ * With h = |a_s - b_s|, u = |a_t - b_t|, psi = 1 + (a u)^2:
+ *   C(a, b) = sigma2 rho(c h psi^(-beta/2)) / psi + tau2 delta_ab,   0 <= beta <= 1.
+ * The points are (n, dim) with dim = 2 or 3: the last column is time, the first dim - 1 columns are space.  kind is
+ * the spatial correlation, NNGP_COV_EXPONENTIAL, MATERN32, MATERN52 or GAUSSIAN (NNGP_COV_SPHERICAL is refused with
+ * NNGP_EUNSUP: as a function of h^2 it is not completely monotone, so the class's validity theorem does not cover
+ * it).  c and a are decay rates of space and time; beta = 0 is separable, beta = 1 fully nonseparable.
+ *   nngp_bf_sweep_gneiting: the contract of nngp_bf_sweep_sep (B, F, R, partials[4] required, order, i0, -1 padding,
+ *     the two flags, NaN rows on a bad pivot, a fixed-order fold).
+ *   nngp_bf_cross_gneiting: the contract of nngp_bf_cross_sep (reference points, query points).
+ *   nngp_bf_grad_gneiting: the contract of nngp_bf_grad_sep with G (n_rows, 5) and grad[5] in
+ *     (sigma2, c, a, beta, tau2).  With dv = v rho'(v), v = c h psi^(-beta/2): dC/dc = sigma2 dv / (psi c),
+ *     dC/da = -2 sigma2 (psi - 1) / (a psi^2) (rho + beta dv / 2), dC/dbeta = -sigma2 dv ln(psi) / (2 psi).  d/dc is
+ *     exactly 0 between coincident sites, d/da and d/dbeta exactly 0 at a zero time lag.
+ * Scope: 1 <= m <= 32, dim 2 or 3, kinds as above, else NNGP_EUNSUP.  NNGP_EINVAL for sigma2 <= 0, tau2 < 0, a
+ * non-positive or non-finite c or a, or beta outside [0, 1].
+ * workspace: nngp_bf_sweep_gneiting_workspace_bytes(n_rows, m) serves all three (0 for unsupported arguments);
+ * 256-B aligned, no initialisation needed.
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_gneiting_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_sweep_gneiting(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr,
+                           const int32_t *order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2,
+                           double c, double a, double beta, double tau2, const double *values, double *B, double *F,
+                           double *R, double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_gneiting(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                           const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t q0,
+                           int32_t kind, double sigma2, double c, double a, double beta, double tau2,
+                           const double *ref_values, const double *query_values, double *B, double *F, double *R,
+                           double *partials, void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_grad_gneiting(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr,
+                          const int32_t *order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind, double sigma2,
+                          double c, double a, double beta, double tau2, const double *values, double *G,
+                          double *partials, double *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Points in 4 .. NNGP_ND_MAX_DIM dimensions (added within revision 4; nothing earlier moved).  Every entry point
  * above keeps its 1 <= dim <= NNGP_MAX_DIM; these take 4 <= dim <= NNGP_ND_MAX_DIM and nothing else.
  *

@@ -11,7 +11,9 @@ from .nngp import AnisotropicCovariance  # noqa: F401
 from .autograd import loglik, loglik_matern  # noqa: F401
 from .nngp import MaternCovariance  # noqa: F401
 from .nngp import SeparableCovariance, NNGPIndexError  # noqa: F401
+from .nngp import GneitingCovariance  # noqa: F401
 from .autograd import loglik_sep  # noqa: F401
+from .autograd import loglik_gneiting  # noqa: F401
 from .nd import ARDCovariance, NNGPnd  # noqa: F401
 from .autograd import loglik_ard  # noqa: F401
 from .multivariate import LMCCovariance, MultivariateNNGP  # noqa: F401

@@ -221,6 +221,70 @@ def loglik_sep(coords, nbr, kind_s, kind_t, theta4, values, order=None):
     return ll
 
 
+class _LogLikGneiting(torch.autograd.Function):
+    """theta = (sigma2, c, a, beta, tau2): the Gneiting space-time sweep (``torch.ops.nngp.bf_grad_gneiting``)."""
+
+    @staticmethod
+    def forward(ctx, coords, nbr, theta, values, kind, order):
+        from . import load_ops
+
+        load_ops()
+        th = [float(x) for x in theta.detach().cpu().tolist()]  # host synchronisation (the flags are the other)
+        p, g, _ = torch.ops.nngp.bf_grad_gneiting(coords, nbr, order, 0, _lib.KIND_CODES[kind], *th, values.detach(),
+                                                  False)
+        ctx.save_for_backward(coords, nbr, values, g)
+        ctx.meta = (kind, order, th, theta.device)
+        ctx.mark_non_differentiable(p)
+        ll = -0.5 * (nbr.shape[0] * math.log(2.0 * math.pi) + p[0] + p[1])
+        return ll, p
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_p):
+        coords, nbr, values, g = ctx.saved_tensors
+        kind, order, th, tdev = ctx.meta
+        gtheta = (grad_out * g).to(tdev) if ctx.needs_input_grad[2] else None
+        gvalues = None
+        if ctx.needs_input_grad[3]:
+            # as _LogLikSep: one ordinary sweep (B, F, R) of the same model
+            B, F, R, _ = _lib.bf_sweep_gneiting(coords, nbr, 0, kind, *th, values=values.detach(), order=order,
+                                                want_r=True)
+            w = R / F
+            nat = nbr if order is None else torch.empty_like(nbr).index_copy_(0, order.long(), nbr)
+            ok = nat >= 0
+            gvalues = (-w).index_add(0, nat.clamp(min=0).long().reshape(-1), (B * w[:, None] * ok).reshape(-1))
+            gvalues = grad_out * gvalues
+        return None, None, gtheta, gvalues, None, None
+
+
+def loglik_gneiting(coords, nbr, kind, theta5, values, order=None):
+    """NNGP log-likelihood of ``values`` on S = T under the nonseparable (Gneiting) space-time covariance
+    ``sigma2 rho(c h psi^(-beta/2)) / psi + tau2 delta``, ``psi = 1 + (a u)^2`` (time in the last column of
+    ``coords``, dim 2 or 3) at ``theta5`` = (sigma2, c, a, beta, tau2), a float64 (5,) tensor, differentiable in
+    ``theta5`` and, when ``values.requires_grad``, in ``values``.
+
+    Forward runs one gradient sweep (``torch.ops.nngp.bf_grad_gneiting``) and synchronises with the host as
+    :func:`loglik_sep` does; backward returns ``grad_out * grad`` for theta with no further launch.  ``nbr`` (N, m)
+    int32 with 1 <= m <= 32; kinds exponential, matern32, matern52, gaussian; the not-PD and bad-index flags raise.
+    """
+    if kind not in _lib.KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in _lib.GNEITING_KINDS:
+        raise NotImplementedError(f"loglik_gneiting serves the kinds {_lib.GNEITING_KINDS}")
+    if theta5.dtype != torch.float64 or theta5.shape != (5,):
+        raise ValueError("theta5 must be a float64 (5,) tensor (sigma2, c, a, beta, tau2)")
+    if coords.dim() != 2 or coords.shape[1] not in (2, 3):
+        raise NotImplementedError("loglik_gneiting serves 2 or 3 coordinate columns (space, then time)")
+    if nbr.dim() != 2 or not 1 <= nbr.shape[1] <= _lib.GRAD_MAX_M:
+        raise NotImplementedError(f"loglik_gneiting's gradient serves 1 <= m <= {_lib.GRAD_MAX_M}")
+    if nbr.shape[0] != coords.shape[0]:
+        raise ValueError("loglik_gneiting is an S = T sweep: one nbr row per location")
+    ll, p = _LogLikGneiting.apply(coords, nbr, theta5, values, kind, order)
+    from .nngp import _raise_on_bad
+
+    _raise_on_bad(p.detach().cpu().numpy())
+    return ll
+
+
 class _LogLikSvc(torch.autograd.Function):
     """theta = (sigma2_1..r, phi_1..r, tau2): the varying-coefficient sweep (``torch.ops.nngp.bf_grad_svc``)."""
 

@@ -254,7 +254,79 @@ class SeparableCovariance:
         return self.sigma2 * cs * ct
 
 
+@dataclasses.dataclass(frozen=True)
+class GneitingCovariance:
+    """The nonseparable space-time covariance of Gneiting's (2002) class,
+    ``sigma2 rho(c h psi^(-beta/2)) / psi + tau2 delta_ab`` with ``psi = 1 + (a u)^2``, h the spatial and u the time
+    lag: the last coordinate column is time, the first dim - 1 columns (dim 2 or 3) are space.  ``kind`` names the
+    spatial correlation (exponential, matern32, matern52, gaussian; the spherical kind is not completely monotone in
+    h^2 and is refused), c and a are the decay rates of space and time, ``beta`` in [0, 1] the space-time
+    interaction: 0 is separable (rho(c h) times a Cauchy factor in time), 1 fully nonseparable.  The sweeps evaluate
+    it fused (``nngp_bf_sweep_gneiting``, ``nngp_bf_cross_gneiting``, ``nngp_bf_grad_gneiting``); the gradient is in
+    (sigma2, c, a, beta, tau2).  Called as ``cov(a, b)`` on coordinate rows it returns the cross-covariance matrix
+    without the nugget.
+
+    Neighbour sets come from the ordinary search on the coordinates scaled column by column by :meth:`scaled`
+    (c, .., c, a): a heuristic, as for a :class:`SeparableCovariance`."""
+
+    kind: str
+    sigma2: float
+    c: float
+    a: float
+    beta: float
+    tau2: float = 0.0
+
+    def __post_init__(self):
+        if self.kind not in _lib.GNEITING_KINDS:
+            raise ValueError(f"GneitingCovariance serves the kinds {_lib.GNEITING_KINDS}, got {self.kind!r}")
+        th = (self.sigma2, self.c, self.a, self.beta, self.tau2)
+        if not all(isinstance(x, (int, float, np.floating, np.integer)) and math.isfinite(x) for x in th):
+            raise ValueError(f"sigma2, c, a, beta, tau2 must be finite numbers, got {th}")
+        if not (self.sigma2 > 0 and self.c > 0 and self.a > 0 and 0 <= self.beta <= 1 and self.tau2 >= 0):
+            raise ValueError("need sigma2 > 0, c > 0, a > 0, 0 <= beta <= 1, tau2 >= 0")
+
+    nu = None
+    nu_arg = None
+
+    @property
+    def theta(self):
+        return (float(self.sigma2), float(self.c), float(self.a), float(self.beta), float(self.tau2))
+
+    def replace(self, **kw) -> "GneitingCovariance":
+        return dataclasses.replace(self, **kw)
+
+    def scaled(self, dim: int = 3):
+        """The per-column scales (c, .., c, a) for ``dim`` coordinate columns: the metric of the neighbour search."""
+        if dim not in (2, 3):
+            raise ValueError(f"GneitingCovariance serves 2 or 3 coordinate columns (space, then time), got {dim}")
+        return np.array([self.c] * (dim - 1) + [self.a], dtype=np.float64)
+
+    def __call__(self, a, b):
+        d = a.shape[-1] if a.ndim > 1 else b.shape[-1]
+        if d not in (2, 3) or (a.ndim > 1 and a.shape[-1] != d) or (b.ndim > 1 and b.shape[-1] != d):
+            raise ValueError("coordinate rows must have 2 or 3 columns (space, then time)")
+        a, b = a.reshape(-1, d), b.reshape(-1, d)
+        u = a[:, None, d - 1] - b[None, :, d - 1]
+        psi = 1.0 + (self.a * u) ** 2
+        h = ((a[:, None, :d - 1] - b[None, :, :d - 1]) ** 2).sum(-1) ** 0.5
+        v = self.c * h * psi ** (-0.5 * self.beta)
+        exp = torch.exp if isinstance(v, torch.Tensor) else np.exp
+        if self.kind == "gaussian":
+            rho = exp(-v * v)
+        else:
+            poly = {"exponential": 1.0, "matern32": 1.0 + v, "matern52": 1.0 + v + v * v / 3.0}[self.kind]
+            rho = poly * exp(-v)
+        return self.sigma2 * rho / psi
+
+
+_SPACE_TIME = (SeparableCovariance, GneitingCovariance)
+
+
 def _refuse_sep(cov, what: str) -> None:
+    if isinstance(cov, GneitingCovariance):
+        raise TypeError(f"{what} does not serve a GneitingCovariance (nonseparable space-time): use loglik / "
+                        "compute_BF / predict(query=) / profile_loglik / profile_loglik_grad / gls / loglik_grad / fit "
+                        "on refType='S=T'")
     if isinstance(cov, SeparableCovariance):
         raise TypeError(f"{what} does not serve a SeparableCovariance (space x time product): use loglik / "
                         "compute_BF / predict(query=) / profile_loglik / profile_loglik_grad / gls / loglik_grad / fit "
@@ -560,6 +632,17 @@ def _sweep_any(cv, coords, nbr, i0=0, values=None, want_bf=True, algo="auto", or
     given: the cross sweep of those query points against ``coords`` (prediction); ``qvalues``: the
     values at the locations (S = T sweep: pass ``values``).  A :class:`SeparableCovariance` runs on its own fused
     sweeps (nngp_bf_sweep_sep / nngp_bf_cross_sep; ``algo`` is not used)."""
+    if isinstance(cv, GneitingCovariance):  # its own fused sweeps (nngp_bf_sweep_gneiting / nngp_bf_cross_gneiting)
+        want_r = R is not None
+        if qcoords is not None:
+            B, F, Rn, p = _lib.bf_cross_gneiting(coords, qcoords, nbr, cv.kind, *cv.theta, ref_values=values,
+                                                 query_values=qvalues, q0=i0, order=order, want_r=want_r)
+        else:
+            B, F, Rn, p = _lib.bf_sweep_gneiting(coords, nbr, i0, cv.kind, *cv.theta, values=values,
+                                                 want_bf=want_bf, order=order, want_r=want_r)
+        if want_r:
+            R.copy_(Rn)
+        return B, F, p
     if isinstance(cv, SeparableCovariance):
         want_r = R is not None
         if qcoords is not None:
@@ -788,9 +871,9 @@ class NNGP:
             _refuse_sep(cov, f"refType={self.refType!r}")
         d = self._s_dev.shape[1]
         if d not in (2, 3):
-            raise ValueError(f"a SeparableCovariance needs 2 or 3 coordinate columns (space, then time), got {d}")
+            raise ValueError(f"a {type(cov).__name__} needs 2 or 3 coordinate columns (space, then time), got {d}")
         if not 1 <= self.m <= _lib.GRAD_MAX_M:
-            raise NotImplementedError(f"the separable sweeps serve 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
+            raise NotImplementedError(f"the space-time sweeps serve 1 <= m <= {_lib.GRAD_MAX_M} (m={self.m})")
         return cov
 
     def _metric_phi(self, cov):
@@ -798,7 +881,7 @@ class NNGP:
         :class:`SeparableCovariance`'s (phi_s, .., phi_s, phi_t), else None (the coordinates themselves)."""
         if isinstance(cov, AnisotropicCovariance):
             return self._aniso_phi(cov)
-        if isinstance(cov, SeparableCovariance):
+        if isinstance(cov, _SPACE_TIME):
             return tuple(self._sep_model(cov).scaled(self._s_dev.shape[1]).tolist())
         return None
 
@@ -824,7 +907,7 @@ class NNGP:
         c = self.cov if cov is None else cov
         if isinstance(c, AnisotropicCovariance):
             return c.scaled()[0], self._scaled_s(self._aniso_phi(c))
-        if isinstance(c, SeparableCovariance):  # its own fused sweeps, on the raw coordinates (_sweep_any)
+        if isinstance(c, _SPACE_TIME):  # its own fused sweeps, on the raw coordinates (_sweep_any)
             return self._sep_model(c), self._s_dev
         return self._covariance(c), self._s_dev
 
@@ -984,7 +1067,7 @@ class NNGP:
             k = min(self.m, self._s_dev.shape[0])
             nbr = None
         q = self._query_scale(cov, q)  # an AnisotropicCovariance: the query points in the scaled coordinates too
-        if nbr is None and isinstance(cv, SeparableCovariance):
+        if nbr is None and isinstance(cv, _SPACE_TIME):
             # the search in the (phi_s, .., phi_s, phi_t) metric, the cross sweep on the coordinates themselves
             ph = self._metric_phi(cv)
             nbr = _lib.knn_query(self._scaled_s(ph), q * self._phi_dev(ph), k)
@@ -1235,7 +1318,7 @@ class NNGP:
     def _grad_cov(self, cov, aniso: bool = True):
         """The covariance of a gradient sweep: a fused kind other than the general-nu Matern, m >= 1."""
         cv = self.cov if cov is None else cov
-        if isinstance(cv, SeparableCovariance):
+        if isinstance(cv, _SPACE_TIME):
             if not aniso:
                 _refuse_sep(cv, "the Fisher information (fisher_information, fit(method='fisher'), stderr=True)")
             return self._sep_model(cv)
@@ -1286,6 +1369,11 @@ class NNGP:
             return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:7].copy()
         cv = self._grad_cov(cov)
         v = self._values_dev(values)
+        if isinstance(cv, GneitingCovariance):  # (sigma2, c, a, beta, tau2) from one nngp_bf_grad_gneiting sweep
+            p, g, _ = _lib.bf_grad_gneiting(self._s_dev, self._nbr_sorted, 0, cv.kind, *cv.theta, v, order=self._order)
+            h = torch.cat([p, g]).cpu().numpy()
+            _raise_on_bad(h[:4], cv)
+            return -0.5 * (self.nbr.shape[0] * LOG_2PI + h[0] + h[1]), h[4:].copy()
         if isinstance(cv, SeparableCovariance):  # (sigma2, phi_s, phi_t, tau2) from one nngp_bf_grad_sep sweep
             p, g, _ = _lib.bf_grad_sep(self._s_dev, self._nbr_sorted, 0, cv.kind_s, cv.kind_t, *cv.theta, v,
                                        order=self._order)
@@ -1487,7 +1575,7 @@ class NNGP:
             gradient: Optional[bool] = None, X=None, reml: bool = False, stderr: bool = False,
             tol: Optional[float] = None,
             anisotropic: bool = False, reneighbor: int = 0, estimate_nu: Optional[bool] = None,
-            nu_bounds=(0.05, 50.0), noise=None):
+            nu_bounds=(0.05, 50.0), noise=None, fix_beta: Optional[float] = None):
         """Maximum-likelihood (sigma2, phi, tau2) of the NNGP response model on S = T, each
         objective evaluation one or two fused GPU sweeps (scipy.optimize on log-parameters).
         ``x0`` defaults to ``cov``'s theta; ``fix_tau2`` holds the nugget fixed (e.g. 0 for the
@@ -1555,10 +1643,18 @@ class NNGP:
         the free log-parameters at the reported ``theta``), ``loglik``, ``n_evals``, ``n_grad_evals``, ``converged`` and
         ``message``.  A neighbour index out of range raises :class:`NNGPIndexError` from this model's methods: an
         ``NNGPNumericalError`` and an ``IndexError`` (what every other model raises) at once.
-        Every other option raises ``TypeError``."""
+        Every other option raises ``TypeError``.
+
+        A model built with a :class:`GneitingCovariance`: the same fit over (log sigma2, log c, log a, beta, log tau2)
+        on ``nngp_bf_grad_gneiting``, the interaction ``beta`` itself (not its log) boxed to [0, 1] by L-BFGS-B's
+        bounds; ``gradient=False`` is Nelder-Mead with ``beta`` clipped to the box.  ``x0`` = (sigma2, c, a, beta, tau2);
+        ``fix_beta`` holds the interaction at a value as ``fix_tau2`` holds the nugget (``fix_beta`` with any other
+        model raises ``TypeError``).  The result names the interaction ``beta_st`` (``theta[3]``): ``beta`` stays the
+        regression coefficients' key of ``mean='linear'``; ``grad`` is in the free (log sigma2, log c, log a, beta,
+        log tau2)."""
         gradient_asked = gradient
         gradient = bool(gradient)
-        if isinstance(getattr(self, "cov", None), SeparableCovariance):
+        if isinstance(getattr(self, "cov", None), _SPACE_TIME):
             # a SeparableCovariance model: L-BFGS-B on the analytic gradient over the free log-parameters of
             # (sigma2, phi_s, phi_t, tau2) (nngp_bf_grad_sep), the kinds fixed to the model's; fix_tau2, mean, X, tol
             # (L-BFGS-B's gtol), maxiter and reneighbor=r as for anisotropic=True.  gradient=False: Nelder-Mead on the
@@ -1573,8 +1669,15 @@ class NNGP:
                 raise ValueError("mean='linear' needs the design matrix X")
             if mean != "linear" and X is not None:
                 raise ValueError("X is the design of mean='linear'")
+            if isinstance(self.cov, GneitingCovariance):
+                return self._fit_gneiting(x0, mean, fix_tau2, fix_beta, method, maxiter, X, int(reneighbor), algo, tol,
+                                          gradient_asked is None or gradient)
+            if fix_beta is not None:
+                raise TypeError("fix_beta is an option of a GneitingCovariance model")
             return self._fit_sep(x0, mean, fix_tau2, method, maxiter, X, int(reneighbor), algo, tol,
                                  gradient_asked is None or gradient)
+        if fix_beta is not None:
+            raise TypeError("fix_beta is an option of a GneitingCovariance model")
         if noise is not None:
             for on, what in ((stderr, "stderr=True"), (method == "fisher", "method='fisher'"),
                              (anisotropic, "anisotropic=True"), (estimate_nu is not None, "estimate_nu"),
@@ -1904,6 +2007,115 @@ class NNGP:
             else:
                 best["ll"], best["mu"] = self.profile_loglik(start, mean=mean, algo=algo)
         out = {"theta": start.theta, "sigma2": start.sigma2, "phi_s": start.phi_s, "phi_t": start.phi_t,
+               "tau2": start.tau2, "mu": best["mu"], "loglik": best["ll"], "n_evals": n_evals, "n_grad_evals": n_grad,
+               "converged": bool(res.success) and not last_failed[0], "message": str(res.message),
+               "rounds": reneighbor + 1, **self._fit_beta(X if linear else None, algo)}
+        if gradient:
+            out["grad"] = best["grad"]  # at the reported theta (the best point seen, the last round's)
+        return out
+
+    def _fit_gneiting(self, x0, mean, fix_tau2, fix_beta, method, maxiter, X, reneighbor: int, algo: str, tol,
+                      gradient: bool) -> dict:
+        """``fit`` of a :class:`GneitingCovariance` model: _fit_sep's scaffolding over (log sigma2, log c, log a, beta,
+        log tau2) with beta boxed to [0, 1] (L-BFGS-B on ``nngp_bf_grad_gneiting``), or Nelder-Mead on the forward
+        sweep with beta clipped to the box (``gradient`` False).  ``fix_beta`` / ``fix_tau2`` hold one fixed."""
+        from scipy.optimize import minimize
+
+        if reneighbor < 0:
+            raise ValueError("reneighbor must be >= 0")
+        base = self._sep_model(self.cov)
+        if x0 is not None and len(x0) != 5:
+            raise ValueError("x0 must be (sigma2, c, a, beta, tau2)")
+        s0, c0, a0, b0, t0 = (float(v) for v in (x0 if x0 is not None else base.theta))
+        free_tau, free_beta = fix_tau2 is None, fix_beta is None
+        linear = mean == "linear"
+        if mean not in ("constant", "zero", "linear"):
+            raise ValueError("mean must be 'constant', 'zero' or 'linear'")
+        if linear:
+            from . import regression
+
+            X = regression.design(self, X, self.nbr.shape[0])
+        if method is None:
+            method = "L-BFGS-B" if gradient else "Nelder-Mead"
+        # z: the three logs, then beta and log tau2 where free; idx: each z's place in theta, logs: taken as a log
+        idx = [0, 1, 2] + ([3] if free_beta else []) + ([4] if free_tau else [])
+        logs = [k != 3 for k in idx]
+
+        def cov_of(z):
+            th = [0.0, 0.0, 0.0, float(b0 if free_beta else fix_beta), float(t0 if free_tau else fix_tau2)]
+            for zk, k, lg in zip(z, idx, logs):
+                th[k] = math.exp(zk) if lg else min(max(float(zk), 0.0), 1.0)
+            return GneitingCovariance(base.kind, *th)
+
+        start = GneitingCovariance(base.kind, s0, c0, a0, min(max(b0, 0.0), 1.0) if free_beta else float(fix_beta),
+                                   max(t0, 1e-6) if free_tau else float(fix_tau2))
+        n_evals = n_grad = 0
+        options = {"maxiter": maxiter}
+        if gradient and tol is not None and method == "L-BFGS-B":
+            options.update(gtol=float(tol), ftol=1e-15)  # the gradient rule alone
+        elif gradient and tol is not None:
+            options["gtol"] = float(tol)
+        elif method == "Nelder-Mead":
+            options.update(xatol=1e-6 if tol is None else float(tol), fatol=1e-9)
+        for rnd in range(reneighbor + 1):
+            if rnd > 0:
+                self.rebuild_neighbors(start)
+            best, seen, last_failed = {"ll": -math.inf}, {}, [False]
+
+            def evaluate(z, with_grad):
+                try:
+                    cv = cov_of(z)
+                    out = self.profile_loglik_grad(cv, mean=mean, X=X) if with_grad else \
+                        self.profile_loglik(cv, mean=mean, X=X)
+                except NNGPIndexError:  # a bad neighbour index is no property of theta
+                    raise
+                except (OverflowError, ValueError, NNGPNumericalError):
+                    last_failed[0] = True
+                    return None, None
+                last_failed[0] = False
+                return cv, out
+
+            def obj_grad(z):
+                cv, out = evaluate(z, True)
+                if cv is None:
+                    return 1e300, np.zeros(len(z))
+                ll, mu, g = out
+                gz = np.array([(cv.theta[k] if lg else 1.0) * g[k] for k, lg in zip(idx, logs)])
+                seen[tuple(z)] = gz
+                if ll > best["ll"]:
+                    best.update(ll=ll, mu=None if linear else mu, cov=cv, grad=gz)
+                return -ll, -gz
+
+            def obj(z):
+                cv, out = evaluate(z, False)
+                if cv is None:
+                    return 1e300
+                if out[0] > best["ll"]:
+                    best.update(ll=out[0], mu=None if linear else out[1], cov=cv)
+                return -out[0]
+
+            z0 = np.array([math.log(start.theta[k]) if lg else start.theta[k] for k, lg in zip(idx, logs)])
+            if gradient:
+                bounds = [(None, None) if lg else (0.0, 1.0) for lg in logs] if method == "L-BFGS-B" else None
+                res = minimize(obj_grad, z0, jac=True, method=method, bounds=bounds, options=options)
+            else:
+                res = minimize(obj, z0, method=method, options=options)
+            n_evals += int(res.nfev)
+            n_grad += len(seen)
+            if "cov" not in best:
+                raise NNGPNumericalError("fit (GneitingCovariance): no parameter value the optimiser tried was "
+                                         "positive definite")
+            start = best["cov"]
+        self.cov = start
+        self._B = self._F = None
+        if reneighbor > 0:
+            self.rebuild_neighbors(start)
+            if linear:
+                best["ll"] = self.gls(start, X, algo=algo).loglik
+            else:
+                best["ll"], best["mu"] = self.profile_loglik(start, mean=mean, algo=algo)
+        # (the interaction is "beta_st": "beta" is the regression coefficients' key of every fit, _fit_beta)
+        out = {"theta": start.theta, "sigma2": start.sigma2, "c": start.c, "a": start.a, "beta_st": start.beta,
                "tau2": start.tau2, "mu": best["mu"], "loglik": best["ll"], "n_evals": n_evals, "n_grad_evals": n_grad,
                "converged": bool(res.success) and not last_failed[0], "message": str(res.message),
                "rounds": reneighbor + 1, **self._fit_beta(X if linear else None, algo)}
@@ -2263,7 +2475,7 @@ class NNGPIndexError(NNGPNumericalError, IndexError):
 
 
 def _raise_on_bad(partials_host, cov=None) -> None:
-    if partials_host[3] >= 0 and isinstance(cov, SeparableCovariance):
+    if partials_host[3] >= 0 and isinstance(cov, _SPACE_TIME):
         raise NNGPIndexError(f"neighbour index out of range at location {int(partials_host[3])}")
     if partials_host[3] >= 0:
         raise IndexError(f"neighbour index out of range at location {int(partials_host[3])}")

@@ -33,6 +33,12 @@ for tracing.
         -> (partials, grad, G)                                         # grad (4,), G (rows, 4): sigma2, phi_s, phi_t, tau2
     torch.ops.nngp.bf_cross_sep(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values)
         -> (B, F, mean)                                                # bf_cross of that model
+    torch.ops.nngp.bf_sweep_gneiting(coords, nbr, order, i0, kind, sigma2, c, a, beta, tau2, values, want_bf)
+        -> (B, F, R, partials)   # nonseparable (Gneiting) space-time; B, F empty without want_bf
+    torch.ops.nngp.bf_grad_gneiting(coords, nbr, order, i0, kind, sigma2, c, a, beta, tau2, values, want_rows)
+        -> (partials, grad, G)                                         # grad (5,), G (rows, 5): sigma2, c, a, beta, tau2
+    torch.ops.nngp.bf_cross_gneiting(ref, query, nbr, kind, sigma2, c, a, beta, tau2, ref_values)
+        -> (B, F, mean)                                                # bf_cross of that model
     torch.ops.nngp.bf_sweep_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
         -> (B, F, R, partials)   # spatially varying coefficients: Z (N, r), sigma2 and phi lists of r <= 4 numbers
     torch.ops.nngp.bf_grad_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
@@ -215,6 +221,22 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_sep")
     def _(ref, query, nbr, kind_s, kind_t, sigma2, phi_s, phi_t, tau2, ref_values):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_gneiting")
+    def _(coords, nbr, order, i0, kind, sigma2, c, a, beta, tau2, values, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_grad_gneiting")
+    def _(coords, nbr, order, i0, kind, sigma2, c, a, beta, tau2, values, want_rows):
+        return (coords.new_empty((4,)), coords.new_empty((5,)),
+                coords.new_empty((nbr.shape[0] if want_rows else 0, 5)))
+
+    @fake("bf_cross_gneiting")
+    def _(ref, query, nbr, kind, sigma2, c, a, beta, tau2, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 
