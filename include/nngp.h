@@ -342,6 +342,41 @@ int nngp_bf_grad_gneiting(const double *coords, int64_t n_points, int32_t dim, c
                           double *partials, double *grad, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Nonstationary covariance: per-point variance, decay and nugget (added within revision 4; nothing earlier moved).
+ * sigma2, phi and tau2 are DEVICE arrays of one double per point: sigma2_i > 0, phi_i > 0 (range 1 / phi_i),
+ * tau2_i >= 0.  The Paciorek-Schervish (2006) form with kernel matrices phi_i^-2 I, d = dim:
+ *   C(i, j) = sigma_i sigma_j x^(d/2) rho(u) + tau2_i delta_ij,
+ *   x = 2 phi_i phi_j / (phi_i^2 + phi_j^2),   u^2 = 2 |s_i - s_j|^2 phi_i^2 phi_j^2 / (phi_i^2 + phi_j^2),
+ * rho the correlation of kind at scaled distance u.  Constant fields give the model of nngp_bf_sweep_noise at
+ * noise_var = 1.  kind: NNGP_COV_EXPONENTIAL, MATERN32, MATERN52 or GAUSSIAN, each a scale mixture of gaussians in
+ * u^2; NNGP_COV_SPHERICAL (no such mixture: the construction's validity does not cover it), NNGP_COV_MATERN and
+ * unknown kinds are refused with NNGP_EUNSUP, as are m outside 1 .. 32 and dim outside 1 .. NNGP_MAX_DIM.
+ *   nngp_bf_sweep_ns: the contract of nngp_bf_sweep_noise (B, F, R, partials[4] required, order, i0, -1 padding, the
+ *     two flags, NaN rows on a bad pivot, a fixed-order fold whose bits do not depend on `order`).
+ *   nngp_bf_cross_ns: the contract of nngp_bf_cross_noise; the *_ref fields (n_ref,) belong to the reference points,
+ *     the *_query fields (n_query,) to the query points (tau2_query enters the query's own variance F).
+ * The fields are checked on the device, nothing is read back: a point with a non-finite or non-positive sigma2 or
+ * phi, or a negative or non-finite tau2, is replaced by (1, 1, 1), and every row that holds it -- as the location or
+ * as a neighbour -- reports itself in partials[3] like a row with an out-of-range index.  A slot without a point is
+ * decoupled and has B exactly 0.
+ * workspace: nngp_bf_sweep_ns_workspace_bytes(n_rows, m) bytes at least (0 for unsupported arguments), 256-B
+ * aligned, no initialisation needed.  The sweep packs one 32-byte record per point first; a workspace with
+ * 32 n_points more bytes rounded up to 256 (cross: n_ref, and 32 n_query rounded up to 256 more) holds them, a smaller
+ * one makes the call take them from the stream-ordered allocator (hipMallocAsync / hipFreeAsync on `stream`).
+ * ------------------------------------------------------------------------- */
+size_t nngp_bf_sweep_ns_workspace_bytes(int64_t n_rows, int32_t m);
+int nngp_bf_sweep_ns(const double *coords, int64_t n_points, int32_t dim, const int32_t *nbr, const int32_t *order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind, const double *sigma2, const double *phi,
+                     const double *tau2, const double *values, double *B, double *F, double *R, double *partials,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int nngp_bf_cross_ns(const double *ref, int64_t n_ref, int32_t dim, const double *query, int64_t n_query,
+                     const int32_t *nbr, const int32_t *order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                     const double *sigma2_ref, const double *phi_ref, const double *tau2_ref,
+                     const double *sigma2_query, const double *phi_query, const double *tau2_query,
+                     const double *ref_values, const double *query_values, double *B, double *F, double *R,
+                     double *partials, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Points in 4 .. NNGP_ND_MAX_DIM dimensions (added within revision 4; nothing earlier moved).  Every entry point
  * above keeps its 1 <= dim <= NNGP_MAX_DIM; these take 4 <= dim <= NNGP_ND_MAX_DIM and nothing else.
  *

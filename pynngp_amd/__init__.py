@@ -20,6 +20,7 @@ from .multivariate import LMCCovariance, MultivariateNNGP  # noqa: F401
 from .autograd import loglik_lmc  # noqa: F401
 from .svc import SVCCovariance, SVCNNGP  # noqa: F401
 from .autograd import loglik_svc  # noqa: F401
+from .nonstationary import NonstationaryCovariance, NonstationaryNNGP  # noqa: F401
 from .sweep import ShardedLogLik, shard_range, combine_partials  # noqa: F401
 from .gibbs import SeqNNGP, SeqNNGPChains, Priors  # noqa: F401
 from .gibbs_sharded import ShardedSeqNNGP  # noqa: F401

@@ -83,6 +83,9 @@ SYMBOLS = (
     "nngp_bf_sweep_gneiting",
     "nngp_bf_cross_gneiting",
     "nngp_bf_grad_gneiting",
+    "nngp_bf_sweep_ns_workspace_bytes",
+    "nngp_bf_sweep_ns",
+    "nngp_bf_cross_ns",
     "nngp_bf_sweep_svc_workspace_bytes",
     "nngp_bf_sweep_svc",
     "nngp_bf_cross_svc",
@@ -238,6 +241,13 @@ def load() -> ctypes.CDLL:
     lib.nngp_bf_cross_gneiting.restype = ctypes.c_int
     lib.nngp_bf_grad_gneiting.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, D, D, D, D, D, P, P, P, P, P, SZ, P]
     lib.nngp_bf_grad_gneiting.restype = ctypes.c_int
+    lib.nngp_bf_sweep_ns_workspace_bytes.argtypes = [I64, I32]
+    lib.nngp_bf_sweep_ns_workspace_bytes.restype = SZ
+    lib.nngp_bf_sweep_ns.argtypes = [P, I64, I32, P, P, I64, I32, I64, I32, P, P, P, P, P, P, P, P, P, SZ, P]
+    lib.nngp_bf_sweep_ns.restype = ctypes.c_int
+    lib.nngp_bf_cross_ns.argtypes = [P, I64, I32, P, I64, P, P, I64, I32, I64, I32, P, P, P, P, P, P, P, P, P, P, P, P,
+                                     P, SZ, P]
+    lib.nngp_bf_cross_ns.restype = ctypes.c_int
     lib.nngp_bf_sweep_svc_workspace_bytes.argtypes = [I64, I32, I32]
     lib.nngp_bf_sweep_svc_workspace_bytes.restype = SZ
     lib.nngp_bf_sweep_svc.argtypes = [P, I64, I32, P, I32, P, P, I64, I32, I64, I32, P, P, D, P, P, P, P, P, P, SZ, P]
@@ -1539,6 +1549,111 @@ def bf_cross_gneiting(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor,
                                       float(beta), float(tau2), _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F),
                                       _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
            "nngp_bf_cross_gneiting")
+    return B, F, R, partials
+
+
+# ---------------------------------------------------------------- nonstationary fields (nngp_bf_*_ns)
+NS_KINDS = ("exponential", "matern32", "matern52", "gaussian")
+
+
+def _ns_checks(kind: str, m: int) -> None:
+    """The scope of the nonstationary sweeps (nngp_bf_*_ns): kinds exponential, matern32, matern52, gaussian,
+    1 <= m <= 32."""
+    if kind not in KIND_CODES:
+        raise ValueError(f"unknown covariance kind {kind!r}")
+    if kind not in NS_KINDS:
+        raise NotImplementedError(f"the nonstationary sweeps serve the kinds {NS_KINDS}, not {kind!r}")
+    if not 1 <= m <= GRAD_MAX_M:
+        raise NotImplementedError(f"the nonstationary sweeps serve 1 <= m <= {GRAD_MAX_M} (m={m})")
+
+
+def _ns_fields(fields, n: int, name: str):
+    out = tuple(_noise_var(f, n, f"{name}[{k}]") for k, f in enumerate(fields))
+    if len(out) != 3:
+        raise ValueError(f"{name} must be the three fields (sigma2, phi, tau2)")
+    return out
+
+
+def _ns_workspace_bytes(lib, rows: int, m: int, *n_points: int) -> int:
+    """The block records and, after them, the 32-byte per-point records of each point set (include/nngp.h)."""
+    return lib.nngp_bf_sweep_ns_workspace_bytes(rows, m) + sum((32 * n + 255) // 256 * 256 for n in n_points)
+
+
+def bf_sweep_ns(coords: torch.Tensor, nbr: torch.Tensor, i0: int, kind: str, fields, values=None,
+                want_bf: bool = True, order: Optional[torch.Tensor] = None, want_r: bool = False,
+                workspace: Optional[torch.Tensor] = None):
+    """:func:`bf_sweep_noise` under the nonstationary covariance (``nngp_bf_sweep_ns``, include/nngp.h): ``fields`` =
+    (sigma2, phi, tau2), float64 (N,) device tensors of the per-point variance, decay and nugget.  Returns
+    ``(B, F, R, partials)`` (B, F None without ``want_bf``; R None without ``want_r``, which needs ``values``)."""
+    coords = _as_coords(coords)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    n = coords.shape[0]
+    if values is not None:
+        if values.dtype != torch.float64 or values.shape != (n,):
+            raise ValueError("values must be float64 (N,)")
+        values = values.contiguous()
+    s2, ph, t2 = _ns_fields(fields, n, "fields")
+    rows, m = nbr.shape
+    _ns_checks(kind, m)
+    dev = _require_gpu(coords, nbr, values, s2, ph, t2, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and values is None:
+        raise ValueError("want_r needs values")
+    lib = load()
+    if workspace is None or workspace.numel() < lib.nngp_bf_sweep_ns_workspace_bytes(rows, m):
+        workspace = _workspace(_ns_workspace_bytes(lib, rows, m, n), dev)
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev) if want_bf else None
+    F = torch.empty((rows,), dtype=torch.float64, device=dev) if want_bf else None
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    _check(lib.nngp_bf_sweep_ns(_ptr(coords), n, coords.shape[1], _ptr(nbr), _ptr(order), rows, m, int(i0),
+                                KIND_CODES[kind], _ptr(s2), _ptr(ph), _ptr(t2), _ptr(values), _ptr(B), _ptr(F),
+                                _ptr(R), _ptr(partials), _ptr(workspace), workspace.numel(), _stream(dev)),
+           "nngp_bf_sweep_ns")
+    return B, F, R, partials
+
+
+def bf_cross_ns(ref: torch.Tensor, query: torch.Tensor, nbr: torch.Tensor, kind: str, fields_ref, fields_query,
+                ref_values: Optional[torch.Tensor] = None, query_values: Optional[torch.Tensor] = None, q0: int = 0,
+                order: Optional[torch.Tensor] = None, want_r: bool = False):
+    """:func:`bf_cross_noise` under the nonstationary covariance (``nngp_bf_cross_ns``): ``fields_ref`` and
+    ``fields_query`` are the (sigma2, phi, tau2) fields at the reference and at the query points.  Returns
+    ``(B, F, R, partials)`` (R None without ``want_r``, which needs ``ref_values``)."""
+    ref, query = _as_coords(ref), _as_coords(query)
+    d = _same_dim(ref, query)
+    if nbr.dtype != torch.int32 or nbr.dim() != 2:
+        raise ValueError(f"nbr must be int32 (rows, m), got {nbr.dtype} {tuple(nbr.shape)}")
+    nbr = nbr.contiguous()
+    if ref_values is not None:
+        if ref_values.dtype != torch.float64 or ref_values.shape != (ref.shape[0],):
+            raise ValueError("ref_values must be float64 (n_ref,)")
+        ref_values = ref_values.contiguous()
+    if query_values is not None:
+        if query_values.dtype != torch.float64 or query_values.shape != (query.shape[0],):
+            raise ValueError("query_values must be float64 (n_query,)")
+        query_values = query_values.contiguous()
+    fr = _ns_fields(fields_ref, ref.shape[0], "fields_ref")
+    fq = _ns_fields(fields_query, query.shape[0], "fields_query")
+    rows, m = nbr.shape
+    _ns_checks(kind, m)
+    dev = _require_gpu(ref, query, nbr, ref_values, query_values, *fr, *fq, order)
+    if order is not None and (order.dtype != torch.int32 or order.shape != (rows,)):
+        raise ValueError("order must be int32 (rows,)")
+    if want_r and ref_values is None:
+        raise ValueError("want_r needs ref_values")
+    lib = load()
+    B = torch.empty((rows, m), dtype=torch.float64, device=dev)
+    F = torch.empty((rows,), dtype=torch.float64, device=dev)
+    R = torch.empty((rows,), dtype=torch.float64, device=dev) if want_r else None
+    partials = torch.empty(4, dtype=torch.float64, device=dev)
+    workspace = _workspace(_ns_workspace_bytes(lib, rows, m, ref.shape[0], query.shape[0]), dev)
+    _check(lib.nngp_bf_cross_ns(_ptr(ref), ref.shape[0], d, _ptr(query), query.shape[0], _ptr(nbr), _ptr(order), rows,
+                                m, int(q0), KIND_CODES[kind], *(_ptr(f) for f in fr), *(_ptr(f) for f in fq),
+                                _ptr(ref_values), _ptr(query_values), _ptr(B), _ptr(F), _ptr(R), _ptr(partials),
+                                _ptr(workspace), workspace.numel(), _stream(dev)), "nngp_bf_cross_ns")
     return B, F, R, partials
 
 

@@ -13,6 +13,7 @@
 #include "nbr_cert.h"
 #include "bf_grad.h"
 #include "bf_noise.h"
+#include "bf_ns.h"
 #include "bf_gneiting.h"
 #include "bf_sep.h"
 #include "bf_svc.h"
@@ -312,6 +313,91 @@ int nngp_bf_grad_noise(const double* coords, int64_t n_points, int32_t dim, cons
     hipError_t e = nngp::bf_noise_launch(a, partials, grad, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf_grad_noise launch");
     return NNGP_OK;
+}
+
+static size_t ns_rec_bytes(int64_t n_blocks) { return align256((size_t)n_blocks * 4 * sizeof(double)); }
+
+size_t nngp_bf_sweep_ns_workspace_bytes(int64_t n_rows, int32_t m) {
+    if (n_rows < 0 || m < 1 || m > 32) return 0;
+    const int64_t nb = n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1;
+    return ns_rec_bytes(nb) + align256((size_t)n_rows * sizeof(double2));  // block records, the rows' two sums
+}
+
+// The nonstationary sweep and its cross form (bf_ns.h).  q*: the locations' own coordinates, values and fields --
+// the points' (S = T) or the query points' (cross).  The per-point records follow the block records in
+// the workspace when it is large enough for them, else they live in stream-ordered memory for the call.
+static int ns_forward(const double* coords, int64_t n_points, int32_t dim, const double* qcoords, int64_t n_locs,
+                      const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t i0, int32_t kind,
+                      const double* sigma2, const double* phi, const double* tau2, const double* qsigma2,
+                      const double* qphi, const double* qtau2, const double* values, const double* qvalues, double* B,
+                      double* F, double* R, double* partials, void* workspace, size_t workspace_bytes, bool cross,
+                      void* stream) {
+    if (coords == nullptr || qcoords == nullptr || workspace == nullptr)
+        return fail(NNGP_EINVAL, "coordinates and workspace must be non-null");
+    if (sigma2 == nullptr || phi == nullptr || tau2 == nullptr || qsigma2 == nullptr || qphi == nullptr ||
+        qtau2 == nullptr || partials == nullptr)
+        return fail(NNGP_EINVAL, "the sigma2, phi and tau2 fields and partials must be non-null");
+    if (dim < 1 || dim > NNGP_MAX_DIM) return fail(NNGP_EUNSUP, "dim=%d outside [1, %d]", dim, NNGP_MAX_DIM);
+    if (m < 1 || m > 32) return fail(NNGP_EUNSUP, "the nonstationary sweeps serve 1 <= m <= 32 (m=%d)", m);
+    if (kind == NNGP_COV_SPHERICAL || kind == NNGP_COV_MATERN)
+        return fail(NNGP_EUNSUP, "the nonstationary sweeps serve kinds exponential, matern32, matern52 and gaussian "
+                                 "(spherical is no scale mixture of gaussians), kind=%d", kind);
+    if (kind < NNGP_COV_EXPONENTIAL || kind > NNGP_COV_MATERN) return fail(NNGP_EUNSUP, "unknown kind %d", kind);
+    if (n_rows > 0 && nbr == nullptr) return fail(NNGP_EINVAL, "nbr must be non-null");
+    if (n_points < 1 || n_rows < 0 || i0 < 0 || i0 + n_rows > n_locs)
+        return fail(NNGP_EINVAL, "rows [%lld, %lld) outside [0, %lld)", (long long)i0, (long long)(i0 + n_rows),
+                    (long long)n_locs);
+    if (B != nullptr && F == nullptr) return fail(NNGP_EINVAL, "B given without F");
+    if (F != nullptr && B == nullptr && n_rows > 0) return fail(NNGP_EINVAL, "F given without B");
+    if (R != nullptr && values == nullptr) return fail(NNGP_EINVAL, "R (residuals) needs values");
+    if (((uintptr_t)workspace & 255) != 0) return fail(NNGP_EINVAL, "workspace must be 256-byte aligned");
+    const size_t need = nngp_bf_sweep_ns_workspace_bytes(n_rows, m);
+    if (workspace_bytes < need) return fail(NNGP_EINVAL, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+
+    hipStream_t s = (hipStream_t)stream;
+    const size_t pbytes = align256((size_t)n_points * sizeof(double4));
+    const size_t rbytes = pbytes + (cross ? align256((size_t)n_locs * sizeof(double4)) : 0);
+    void* owned = nullptr;
+    char* recs = (char*)workspace + need;
+    if (workspace_bytes < need + rbytes) {
+        const hipError_t e = hipMallocAsync(&owned, rbytes, s);
+        if (e != hipSuccess) return hip_fail(e, "bf_sweep_ns records");
+        recs = (char*)owned;
+    }
+    double4* prec = (double4*)recs;
+    double4* qrec = cross ? (double4*)(recs + pbytes) : prec;
+    hipError_t e = nngp::bf_ns_pack_launch(sigma2, phi, tau2, n_points, prec, s);
+    if (e == hipSuccess && cross) e = nngp::bf_ns_pack_launch(qsigma2, qphi, qtau2, n_locs, qrec, s);
+    if (e == hipSuccess) {
+        double2* lfq = (double2*)((char*)workspace + ns_rec_bytes(n_rows > 0 ? nngp::bf_grad_blocks(n_rows, m) : 1));
+        nngp::NsArgs a{coords, n_points, nbr, order, n_rows, i0, m, kind, dim, values, prec, qcoords, qvalues, qrec,
+                       B, F, R, (double*)workspace, lfq};
+        e = nngp::bf_ns_launch(a, partials, s);
+    }
+    const hipError_t ef = owned != nullptr ? hipFreeAsync(owned, s) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, "bf_sweep_ns launch");
+    if (ef != hipSuccess) return hip_fail(ef, "bf_sweep_ns records release");
+    return NNGP_OK;
+}
+
+int nngp_bf_sweep_ns(const double* coords, int64_t n_points, int32_t dim, const int32_t* nbr, const int32_t* order,
+                     int64_t n_rows, int32_t m, int64_t i0, int32_t kind, const double* sigma2, const double* phi,
+                     const double* tau2, const double* values, double* B, double* F, double* R, double* partials,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return ns_forward(coords, n_points, dim, coords, n_points, nbr, order, n_rows, m, i0, kind, sigma2, phi, tau2,
+                      sigma2, phi, tau2, values, values, B, F, R, partials, workspace, workspace_bytes, false, stream);
+}
+
+int nngp_bf_cross_ns(const double* ref, int64_t n_ref, int32_t dim, const double* query, int64_t n_query,
+                     const int32_t* nbr, const int32_t* order, int64_t n_rows, int32_t m, int64_t q0, int32_t kind,
+                     const double* sigma2_ref, const double* phi_ref, const double* tau2_ref,
+                     const double* sigma2_query, const double* phi_query, const double* tau2_query,
+                     const double* ref_values, const double* query_values, double* B, double* F, double* R,
+                     double* partials, void* workspace, size_t workspace_bytes, void* stream) {
+    if (query_values != nullptr && ref_values == nullptr) return fail(NNGP_EINVAL, "query_values need ref_values");
+    return ns_forward(ref, n_ref, dim, query, n_query, nbr, order, n_rows, m, q0, kind, sigma2_ref, phi_ref, tau2_ref,
+                      sigma2_query, phi_query, tau2_query, ref_values, query_values, B, F, R, partials, workspace,
+                      workspace_bytes, true, stream);
 }
 
 size_t nngp_bf_sweep_sep_workspace_bytes(int64_t n_rows, int32_t m) {

@@ -723,6 +723,81 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_gneiting(const at::Tenso
     return {B, F, mean};
 }
 
+// ---------------------------------------------------------------- nonstationary fields (nngp_bf_*_ns)
+// the block records and, after them, the 32-byte per-point records of n_a (+ n_b) points (include/nngp.h); no
+// part of it needs initialising
+at::Tensor ns_workspace(int64_t rows, int64_t m, int64_t n_a, int64_t n_b, const at::Tensor& like) {
+    const int64_t bytes = (int64_t)nngp_bf_sweep_ns_workspace_bytes(rows, (int32_t)m) + (32 * n_a + 255) / 256 * 256 +
+                          (32 * n_b + 255) / 256 * 256;
+    return at::empty({bytes > 256 ? bytes : 256}, like.options().dtype(at::kByte));
+}
+
+// (B (rows, m), F (rows,), R (rows,), partials (4,)); B, F empty without want_bf, R empty without values
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bf_sweep_ns(
+    const at::Tensor& coords, const at::Tensor& nbr, const c10::optional<at::Tensor>& order, int64_t i0, int64_t kind,
+    const at::Tensor& sigma2, const at::Tensor& phi, const at::Tensor& tau2, const c10::optional<at::Tensor>& values,
+    bool want_bf) {
+    check_coords(coords, "coords");
+    const at::OptionalDeviceGuard guard(coords.device());
+    check_nbr(nbr, coords);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), n = coords.size(0);
+    check_f64(sigma2, {n}, coords, "sigma2");
+    check_f64(phi, {n}, coords, "phi");
+    check_f64(tau2, {n}, coords, "tau2");
+    check_f64(values, {n}, coords, "values");
+    check_order(order, rows, coords);
+    auto f64 = coords.options();
+    const bool wr = values.has_value();
+    at::Tensor B = at::empty({want_bf ? rows : 0, m}, f64), F = at::empty({want_bf ? rows : 0}, f64);
+    at::Tensor R = at::empty({wr ? rows : 0}, f64), p = at::empty({4}, f64);
+    auto ws = ns_workspace(rows, m, n, 0, coords);
+    check_rc(nngp_bf_sweep_ns(coords.data_ptr<double>(), n, (int32_t)coords.size(1), nbr.data_ptr<int32_t>(),
+                              ptr<int32_t>(order), rows, (int32_t)m, i0, (int32_t)kind, sigma2.data_ptr<double>(),
+                              phi.data_ptr<double>(), tau2.data_ptr<double>(), ptr<double>(values),
+                              want_bf ? B.data_ptr<double>() : nullptr, want_bf ? F.data_ptr<double>() : nullptr,
+                              wr ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(), ws.data_ptr(),
+                              (size_t)ws.nbytes(), stream(coords)),
+             "nngp_bf_sweep_ns");
+    return {B, F, R, p};
+}
+
+// (B, F, kriging mean), as bf_cross; the *_q fields are the query points'
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bf_cross_ns(const at::Tensor& ref, const at::Tensor& query,
+                                                           const at::Tensor& nbr, int64_t kind,
+                                                           const at::Tensor& sigma2, const at::Tensor& phi,
+                                                           const at::Tensor& tau2, const at::Tensor& sigma2_q,
+                                                           const at::Tensor& phi_q, const at::Tensor& tau2_q,
+                                                           const c10::optional<at::Tensor>& ref_values) {
+    check_coords(ref, "ref");
+    const at::OptionalDeviceGuard guard(ref.device());
+    check_coords(query, "query");
+    check_same_device(ref, query, "query");
+    TORCH_CHECK(ref.size(1) == query.size(1), "ref and query have different dimensions");
+    check_nbr(nbr, ref);
+    const int64_t rows = nbr.size(0), m = nbr.size(1), d = ref.size(1), nr = ref.size(0), nq = query.size(0);
+    check_f64(sigma2, {nr}, ref, "sigma2");
+    check_f64(phi, {nr}, ref, "phi");
+    check_f64(tau2, {nr}, ref, "tau2");
+    check_f64(sigma2_q, {nq}, ref, "sigma2_q");
+    check_f64(phi_q, {nq}, ref, "phi_q");
+    check_f64(tau2_q, {nq}, ref, "tau2_q");
+    check_f64(ref_values, {nr}, ref, "ref_values");
+    auto f64 = ref.options();
+    at::Tensor B = at::empty({rows, m}, f64), F = at::empty({rows}, f64), R = at::empty({rows}, f64);
+    at::Tensor p = at::empty({4}, f64);
+    auto ws = ns_workspace(rows, m, nr, nq, ref);
+    check_rc(nngp_bf_cross_ns(ref.data_ptr<double>(), nr, (int32_t)d, query.data_ptr<double>(), nq,
+                              nbr.data_ptr<int32_t>(), nullptr, rows, (int32_t)m, 0, (int32_t)kind,
+                              sigma2.data_ptr<double>(), phi.data_ptr<double>(), tau2.data_ptr<double>(),
+                              sigma2_q.data_ptr<double>(), phi_q.data_ptr<double>(), tau2_q.data_ptr<double>(),
+                              ptr<double>(ref_values), nullptr, B.data_ptr<double>(), F.data_ptr<double>(),
+                              ref_values.has_value() ? R.data_ptr<double>() : nullptr, p.data_ptr<double>(),
+                              ws.data_ptr(), ws.nbytes(), stream(ref)),
+             "nngp_bf_cross_ns");
+    at::Tensor mean = ref_values.has_value() ? R.neg() : at::zeros({rows}, f64);
+    return {B, F, mean};
+}
+
 // ---------------------------------------------------------------- points in 4 .. 16 dimensions (nngp_*_nd)
 void check_coords_nd(const at::Tensor& c, const char* name) {
     TORCH_CHECK(c.is_cuda(), name, " must be a ROCm GPU tensor (there is no CPU fallback)");
@@ -1520,6 +1595,10 @@ TORCH_LIBRARY(nngp, m) {
           "float a, float beta, float tau2, Tensor values, bool want_rows) -> (Tensor, Tensor, Tensor)");
     m.def("bf_cross_gneiting(Tensor ref, Tensor query, Tensor nbr, int kind, float sigma2, float c, float a, "
           "float beta, float tau2, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
+    m.def("bf_sweep_ns(Tensor coords, Tensor nbr, Tensor? order, int i0, int kind, Tensor sigma2, Tensor phi, "
+          "Tensor tau2, Tensor? values, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bf_cross_ns(Tensor ref, Tensor query, Tensor nbr, int kind, Tensor sigma2, Tensor phi, Tensor tau2, "
+          "Tensor sigma2_q, Tensor phi_q, Tensor tau2_q, Tensor? ref_values) -> (Tensor, Tensor, Tensor)");
     m.def("bf_sweep_svc(Tensor coords, Tensor Z, Tensor nbr, Tensor? order, int i0, int kind, float[] sigma2, "
           "float[] phi, float tau2, Tensor? values, bool want_bf) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("bf_grad_svc(Tensor coords, Tensor Z, Tensor nbr, Tensor? order, int i0, int kind, float[] sigma2, "
@@ -1571,6 +1650,8 @@ TORCH_LIBRARY_IMPL(nngp, CUDA, m) {
     m.impl("bf_sweep_gneiting", &bf_sweep_gneiting);
     m.impl("bf_grad_gneiting", &bf_grad_gneiting);
     m.impl("bf_cross_gneiting", &bf_cross_gneiting);
+    m.impl("bf_sweep_ns", &bf_sweep_ns);
+    m.impl("bf_cross_ns", &bf_cross_ns);
     m.impl("bf_sweep_svc", &bf_sweep_svc);
     m.impl("bf_grad_svc", &bf_grad_svc);
     m.impl("bf_cross_svc", &bf_cross_svc);

@@ -39,6 +39,10 @@ for tracing.
         -> (partials, grad, G)                                         # grad (5,), G (rows, 5): sigma2, c, a, beta, tau2
     torch.ops.nngp.bf_cross_gneiting(ref, query, nbr, kind, sigma2, c, a, beta, tau2, ref_values)
         -> (B, F, mean)                                                # bf_cross of that model
+    torch.ops.nngp.bf_sweep_ns(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
+        -> (B, F, R, partials)   # nonstationary: sigma2, phi, tau2 float64 (N,) tensors, one value per point
+    torch.ops.nngp.bf_cross_ns(ref, query, nbr, kind, sigma2, phi, tau2, sigma2_q, phi_q, tau2_q, ref_values)
+        -> (B, F, mean)          # bf_cross of that model; the *_q fields (n_query,) are the query points'
     torch.ops.nngp.bf_sweep_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf)
         -> (B, F, R, partials)   # spatially varying coefficients: Z (N, r), sigma2 and phi lists of r <= 4 numbers
     torch.ops.nngp.bf_grad_svc(coords, Z, nbr, order, i0, kind, sigma2, phi, tau2, values, want_rows)
@@ -237,6 +241,17 @@ def _register_fakes() -> None:
 
     @fake("bf_cross_gneiting")
     def _(ref, query, nbr, kind, sigma2, c, a, beta, tau2, ref_values):
+        rows, m = nbr.shape
+        return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
+
+    @fake("bf_sweep_ns")
+    def _(coords, nbr, order, i0, kind, sigma2, phi, tau2, values, want_bf):
+        rows, m = nbr.shape
+        return (coords.new_empty((rows if want_bf else 0, m)), coords.new_empty((rows if want_bf else 0,)),
+                coords.new_empty((rows if values is not None else 0,)), coords.new_empty((4,)))
+
+    @fake("bf_cross_ns")
+    def _(ref, query, nbr, kind, sigma2, phi, tau2, sigma2_q, phi_q, tau2_q, ref_values):
         rows, m = nbr.shape
         return query.new_empty((rows, m)), query.new_empty((rows,)), query.new_empty((rows,))
 
